@@ -9,9 +9,14 @@ Workload at N=1 = BASELINE.json configs[1]: batch 8, 192x640, 49 planes, --use_m
 Multi-GPU: the path shards over batch elements with no data-path collective: every rank runs its own
 shard (weak scaling); ranks only meet in the timing barrier and the max-over-ranks reduction.
 
-One JSON line is printed by rank 0.  Besides the driver's contract it carries
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times --steps steps and prints the driver's contract
+(metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step) with how the steps were issued.
+--full adds everything else, each leg in the same process:
   "roofline":     HBM roofline of the dominant kernel (algorithmic bytes / measured kernel time, HIP events)
   "cpu_baseline": the CPU oracle (a port of the reference's op sequence) timed on this box's host cores
+  "windows", "hbm_copy_measured", "fast_rows_option", "next_rows", "ddp_step": spread, copy-rate yardstick, the opt-in
+                  approximation, the SURVEY 8f operators and the end-to-end DDP training step
+--dump-outputs DIR writes what the timed path computed in its last timed step (DIR/<name>.npy, float32; see dump_outputs).
 """
 import argparse
 import ctypes
@@ -34,7 +39,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6290 GB/
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (>= 1): `value` and `ms_per_step` come from these")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8, help="images per GPU (BASELINE configs[1]: 8)")
     ap.add_argument("--planes", type=int, default=49)
@@ -78,6 +83,14 @@ def parse():
                          "(depth_decoder.py:209-252) — a genuinely dense [B,N,H,W] map: the general forward + the row-dense backward")
     ap.add_argument("--no_padding_mask", action="store_true", help="never pass a padding mask (diagnostics)")
     ap.add_argument("--no_plane_grad", action="store_true", help="diagnostics: disparities do not require grad")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline window: the roofline / kernel-timing legs, the copy-rate yardstick, the spread "
+                         "windows, the fast-rows option, the SURVEY 8f operators, the CPU baseline and the DDP training-step block "
+                         "(the --no_* / --skip_context switches below take single legs out of a --full run)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (rgb_rec, ph_map, ph_mean per "
+                         "target view; the gradients of the decoder-side leaves) as DIR/<name>.npy, float32, at most 64 MB in all: "
+                         "an array beyond its share is a fixed, seeded sample of its flattened elements (dump_outputs)")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_next_rows", action="store_true", help="skip the timings of the SURVEY 8f operators")
     ap.add_argument("--skip_context", default="", help="comma list of context measurements to skip: copy")
@@ -92,8 +105,12 @@ def parse():
                          "around the launch probe and the timed windows — one process per GPU has no use for the hand-over of every "
                          "backward to another thread, which costs the host 0.1 ms per step whenever the two threads sit on distant cores "
                          "(scripts/diag_step_host.py: 97-116 us per step against 118-210)")
-    ap.add_argument("--windows", type=int, default=7, help="further timed windows of --steps steps after the one `value` reports (spread)")
-    return ap.parse_args()
+    ap.add_argument("--windows", type=int, default=7,
+                    help="--full: further timed windows of --steps steps after the one `value` reports (spread)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_batch(args, device, seed):
@@ -219,9 +236,45 @@ def build_step(args, c, device):
         # ph_mean = ph_map.mean() (trainer.py:742), accumulated by the sweep kernel
         heads = [outputs[(k, sd)] for sd in sides for k in ("ph_mean", "rgb_rec")]
         torch.autograd.backward(heads, [one, g_rgb] * len(sides))
+        if record["on"]:   # --dump-outputs: what a caller of the path receives from this step (references, no copies)
+            got = {"%s_%s" % (k, str(sd).replace("-", "m")): outputs[(k, sd)] for sd in sides
+                   for k in ("rgb_rec", "ph_map", "ph_mean") if torch.is_tensor(outputs.get((k, sd)))}
+            leaves = {"g_logits": logits, "g_sigma": sigma, "g_disp_pp": disp_pp, "g_dists": dists,
+                      "g_distance": distance if args.warp_type == "homography_warp" else None}
+            got.update({k: v.grad for k, v in leaves.items() if v is not None and v.grad is not None})
+            record["out"] = got
         return heads[0]
 
+    record = {"on": False, "out": None}
+    step.record = record
     return step, (logits, sigma, disp_pp, distance)
+
+
+DUMP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(got, limit_bytes=DUMP_BYTES):
+    """Host copies (float32 numpy) of the step outputs in `got`, at most `limit_bytes` in all as .npy files: every array
+    has an equal share of the budget (at most 2^21 elements); one larger than its share is reduced to a fixed sample of
+    its flattened elements — indices drawn from numpy's generator seeded 0, sorted, duplicates dropped — so that runs with
+    the same arguments dump the same positions."""
+    import numpy as np
+    share = min(2 ** 21, limit_bytes // 4 // max(1, len(got)) - 64)   # elements (64 of them cover a .npy header)
+    host = {}
+    for name, t in sorted(got.items()):
+        t = t.detach()
+        if t.numel() > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), size=share))
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+        host[name] = t.float().cpu().numpy()
+    return host
+
+
+def write_outputs(host, out_dir):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class _DecoderSide(torch.autograd.Function):
@@ -799,6 +852,21 @@ def cpu_baseline(args, budget_s):
                                  "what": "same pass with the oracle's gather-based bilinear_sample instead of F.grid_sample, one run"}}
 
 
+def load_library(entry):
+    """The product library for this run.  build() when the library on disk is missing or was built from other sources (or
+    PD_FORCE_BUILD is set); otherwise it is only loaded: no lock file, nothing written, so the benchmark also runs in a
+    tree that another user built and this one may not write to.  entry.BUILD_INFO is filled as build() fills it."""
+    want = entry.source_hash()
+    if os.environ.get("PD_FORCE_BUILD") or entry.embedded_hash() != want:
+        entry.build()
+        return
+    from planedepth_amd import _capi
+    loaded = _capi.load().pd_source_hash().decode()
+    entry.BUILD_INFO.update(build="reused", source_hash=want, library_hash=loaded)
+    if not os.environ.get("PD_LIB") and loaded != want:
+        raise RuntimeError("libplanedepth_hip.so reports source hash %s, the tree is %s" % (loaded, want))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU over RCCL
     (what the reference's `torchrun --nproc_per_node=K train.py` does, train_ResNet.sh:1 / trainer.py:50-55).  On a box
@@ -839,7 +907,7 @@ def main():
     device = torch.device("cuda", 0 if os.environ.get("PD_BENCH_SHARE_GPU") else local_rank)
     torch.cuda.set_device(device)
     import __graft_entry__ as entry
-    entry.build()
+    load_library(entry)
 
     from planedepth_amd import _capi as _C0
     build_flags = int(_C0.load().pd_build_flags())
@@ -849,6 +917,8 @@ def main():
     c = make_batch(args, device, seed=rank)  # every rank draws its own shard: no data-path collective
     step, _ = build_step(args, c, device)
     eager_step = step
+    dump = bool(args.dump_outputs) and rank == 0
+    graph_outputs = {}
 
     def capture_step():
         # whole-step capture (the pattern torch documents for graphs with a backward): warm up on a side stream so every
@@ -862,8 +932,14 @@ def main():
         torch.cuda.current_stream(device).wait_stream(side)
         torch.cuda.synchronize(device)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            eager_step()
+        eager_step.record["on"] = dump   # the captured step's outputs are the graph's static tensors: every replay rewrites them
+        try:
+            with torch.cuda.graph(graph):
+                eager_step()
+        finally:
+            eager_step.record["on"] = False
+        graph_outputs.update(eager_step.record["out"] or {})
+        eager_step.record["out"] = None
         return graph.replay
 
     if args.hip_graph:
@@ -878,21 +954,26 @@ def main():
         except Exception as e:   # a capture that fails must not take the bench line with it
             torch.cuda.synchronize(device)
             launch_probe = {"graph_capture_failed": type(e).__name__}
-    # The kernel-timing legs of the roofline block run BEFORE the timed window, on every rank: a process's first ~50
+    # --full: the kernel-timing legs of the roofline block run BEFORE the timed window, on every rank: a process's first ~50
     # steps run ~10 % slower than its steady state (the same 20 steps take 0.355 ms after 5 warm-up steps, 0.316 ms after
     # 200: scripts/gpu_r3_warm.sh, DESIGN.md section 6 — the device's power state, not the host: a HIP-graph replay shows
     # the same ramp), and a training run lives in the steady state.  ~400 launches of the same kernels, ~100 ms;
-    # the in-step kernel figures are averaged over the second half of their leg for the same reason.
-    leg_iters = max(50, min(args.steps, 100))
-    kt = in_step_kernel_times(eager_step, device, iters=2 * leg_iters, skip=leg_iters)   # the figure the roofline uses
-    iso = kernel_times(args, c, device, iters=leg_iters)
+    # the in-step kernel figures are averaged over the second half of their leg for the same reason.  A plain run reaches
+    # the steady state through the launch probe's 124 steps (--launch auto) and --warmup.
+    kt = iso = None
+    leg_iters = 0
+    if args.full:
+        leg_iters = max(50, min(args.steps, 100))
+        kt = in_step_kernel_times(eager_step, device, iters=2 * leg_iters, skip=leg_iters)   # the figure the roofline uses
+        iso = kernel_times(args, c, device, iters=leg_iters)
     pre_timed = {"in_step_kernel_timing_steps": 2 * leg_iters, "isolated_fwd_launches": (leg_iters + 1) if iso else 0,
                  "isolated_bwd_launches": (leg_iters + 1) if iso else 0, "warmup_steps": args.warmup,
                  "hip_graph_capture_steps": 0,
                  "why": "steady state: a fresh process runs its first ~50 steps ~10 % slower (device power state; DESIGN.md "
-                        "section 6), and the roofline legs need the kernel times anyway"}
+                        "section 6)" + (", and the roofline legs (--full) need the kernel times anyway" if args.full else "")}
     pre_timed["steps_total"] = pre_timed["in_step_kernel_timing_steps"] + args.warmup + pre_timed["hip_graph_capture_steps"]
-    if "copy" not in args.skip_context:
+    copy_legs = args.full and "copy" not in args.skip_context
+    if copy_legs:
         hbm_copy = measured_copy_rate(device)
     # Host hygiene for the 5 ms windows: an eager step costs the host 0.10-0.12 ms (0.20-0.25 in the bad mode of torch's device thread, NOTEBOOK 11.6) of the 0.26 ms the device needs, so a pause of
     # Python's cyclic collector (a generation-2 pass walks everything the set-up legs left behind) lands in a window twice: as
@@ -941,17 +1022,26 @@ def main():
         step()
     parallel.barrier(device)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    if dump and not used_graph:
+        eager_step.record["on"] = True   # the last timed step keeps references to what it computed
+    step()
     parallel.barrier(device)
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0, device)
+    dumped = None
+    if dump:
+        eager_step.record["on"] = False
+        dumped = dump_outputs(graph_outputs if used_graph else eager_step.record["out"])
+        eager_step.record["out"] = None
+        write_outputs(dumped, args.dump_outputs)
 
     value = parallel.throughput(args.batch, args.steps, world, elapsed)   # images (not image-views) per second
     # Spread: `value` above is the contract's window; the same K steps are timed again --windows times, each
     # window bracketed the same way (barrier + synchronize, max over ranks), so the line shows how far one 5 ms window is from
     # the next on THIS box.  The device-to-device copy rate is taken before and after as the box's own yardstick.
     window_rates = []
-    for _ in range(max(0, args.windows)):
+    for _ in range(max(0, args.windows) if args.full else 0):
         parallel.barrier(device)
         tw = time.perf_counter()
         for _ in range(args.steps):
@@ -961,7 +1051,7 @@ def main():
     if not args.keep_gc:
         gc.enable()
         gc.unfreeze()
-    hbm_copy_after = measured_copy_rate(device) if "copy" not in args.skip_context else None
+    hbm_copy_after = measured_copy_rate(device) if copy_legs else None
     result = {
         "metric": METRIC, "value": round(value, 2), "unit": "images/sec",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -1001,13 +1091,16 @@ def main():
                                              "(synthetic.decoder_plane_geometry = networks/depth_decoder.py:146-207) instead of frontal normals for "
                                              "every plane: BASELINE configs[3] as SURVEY 8d (4) specifies it; the default workload is unchanged"}},
     }
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "from": "the last timed step",
+                                    "arrays": {k: list(a.shape) for k, a in dumped.items()}}
     if world > 1:
         import torch.distributed as dist
         result["comm"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                           "devices": "shared cuda:0 (PD_BENCH_SHARE_GPU)" if os.environ.get("PD_BENCH_SHARE_GPU")
                           else "one per rank"}
     if rank == 0:
-        if "copy" not in args.skip_context:
+        if copy_legs:
             result["hbm_copy_measured"] = hbm_copy
             result["hbm_copy_measured_after"] = hbm_copy_after
         if kt:
@@ -1045,7 +1138,7 @@ def main():
                 "bwd_frac_of_peak": round(bwd_b * args.batch / (kt["bwd"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
             if iso:
                 result["kernels"].update(isolated_fwd_ms=round(iso["fwd"], 4), isolated_bwd_ms=round(iso["bwd"], 4))
-        if world == 1 and args.warp_type == "disp_warp" and not args.no_next_rows:
+        if args.full and world == 1 and args.warp_type == "disp_warp" and not args.no_next_rows:
             # The opt-in approximation next to the reported (exact) number: PD_IMPL_FAST_ROWS drops the second source row of the
             # rows whose y round trip is inexact (weight eps <= 8e-6) in forward and backward — all the traffic the headline
             # kernels move above the algorithmic bytes; rejected as the default by the parity suite.
@@ -1075,14 +1168,14 @@ def main():
                         "forward and backward.  NOT the default and not `value`: the parity suite, run under both row modes, finds it beyond "
                         "BASELINE's 1e-4 on white-noise inputs at the benchmark sizes (worst 3.1e-4, profiles/r05_parity.md) and inside it on "
                         "the golden fixtures, the KATs and band-limited inputs; eager launches, 60 steps each"}
-        if world == 1 and not args.no_next_rows:
+        if args.full and world == 1 and not args.no_next_rows:
             result["next_rows"] = next_rows_times(args, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
             result["speedup_vs_cpu_baseline"] = round(value / result["cpu_baseline"]["value"], 1)
     if not args.autograd_threads:
         torch.autograd.set_multithreading_enabled(True)   # the DDP step block runs under torch's default
-    if not args.no_ddp_step and args.warp_type == "disp_warp" and not (args.xz_levels or args.yz_levels):
+    if args.full and not args.no_ddp_step and args.warp_type == "disp_warp" and not (args.xz_levels or args.yz_levels):
         # The headline line must not die with the secondary block — neither by an exception nor by a collective that never
         # returns (a rank that failed while the others wait in an all-reduce: RCCL's watchdog would abort the process before
         # anything is printed).  A timer thread prints the line without the block and ends the process if it overruns.

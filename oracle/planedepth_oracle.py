@@ -27,9 +27,8 @@ Pinning: the reference ships no tests or golden vectors for thi
 path.  The oracle is pinned instead against outputs of the reference itself,
 imported in the build container by ``tests/golden/make_golden.py`` (stand-in
 modules for the packages the image lacks); the resulting vectors live in
-``tests/golden/`` and are checked by ``tests/test_oracle.py`` on every run, and
-``tests/test_oracle_vs_reference.py`` re-runs the live comparison whenever
-``/root/reference`` is present.
+``tests/golden/`` and are checked by ``tests/test_oracle.py`` and
+``tests/test_oracle_vs_reference.py`` (fresh seeds) on every run.
 
 Gradients come from autograd through this restatement, i.e. they are the
 gradients the reference's own autograd graph would produce (same op structure,

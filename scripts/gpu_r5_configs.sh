@@ -6,7 +6,7 @@ REPO=$PWD
 O=gpurun_out/r5/cfg; mkdir -p $O
 SPEC="--warp_type homography_warp --mono_sides --automask --xz_levels 14"
 rows=""
-b() { name=$1; flags=$2; timeout 500 python bench.py --steps ${STEPS:-100} --warmup 20 --no_cpu_baseline --no_next_rows --no_ddp_step $flags > $O/c_$name.log 2>&1
+b() { name=$1; flags=$2; timeout 500 python bench.py --full --steps ${STEPS:-100} --warmup 20 --no_cpu_baseline --no_next_rows --no_ddp_step $flags > $O/c_$name.log 2>&1
       python - "$name" "$flags" $O/c_$name.log <<'PY'
 import json, sys
 name, flags, path = sys.argv[1:4]

@@ -4,7 +4,7 @@ O=gpurun_out/r6/ddp_ab.txt; : > $O
 for i in 1 2; do
   for lib in ${ARMS:-old product bnp bp1}; do
     L=""; [ $lib != product ] && L=$PWD/planedepth_amd/lib/libpd_var_$lib.so
-    PD_LIB=$L timeout 300 python bench.py --steps 50 --warmup 10 --no_cpu_baseline --no_next_rows > gpurun_out/r6/ddp_$lib$i.json 2>/dev/null
+    PD_LIB=$L timeout 300 python bench.py --full --steps 50 --warmup 10 --no_cpu_baseline --no_next_rows > ${O%/*}/ddp_$lib$i.json 2>/dev/null
     python - $lib $i gpurun_out/r6/ddp_$lib$i.json <<'PY' | tee -a $O
 import json, sys
 lib, i, p = sys.argv[1:4]

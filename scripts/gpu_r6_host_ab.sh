@@ -5,7 +5,7 @@ O=gpurun_out/r6/host_ab.txt; : > $O
 for i in 1 2 3; do
   for arm in "threads:--autograd_threads:1" "single::1" "single_slowstream::0"; do
     name=${arm%%:*}; rest=${arm#*:}; flag=${rest%%:*}; raw=${rest##*:}
-    PD_RAW_STREAM=$raw timeout 300 python bench.py --steps 100 --warmup 20 --no_cpu_baseline --no_next_rows --no_ddp_step $flag > gpurun_out/r6/h_$name$i.json 2>/dev/null
+    PD_RAW_STREAM=$raw timeout 300 python bench.py --full --steps 100 --warmup 20 --no_cpu_baseline --no_next_rows --no_ddp_step $flag > ${O%/*}/h_$name$i.json 2>/dev/null
     python - $name $i gpurun_out/r6/h_$name$i.json <<'PY' | tee -a $O
 import json, sys
 lib, i, p = sys.argv[1:4]

@@ -5,7 +5,7 @@ O=gpurun_out/r6/oldnew.txt; : > $O
 for i in 1 2 3; do
   for lib in old product; do
     L=""; [ $lib = old ] && L=$PWD/planedepth_amd/lib/libpd_var_old.so
-    PD_LIB=$L timeout 300 python bench.py --steps 100 --warmup 20 --no_cpu_baseline --no_next_rows --no_ddp_step > gpurun_out/r6/on_$lib$i.json 2>/dev/null
+    PD_LIB=$L timeout 300 python bench.py --full --steps 100 --warmup 20 --no_cpu_baseline --no_next_rows --no_ddp_step > ${O%/*}/on_$lib$i.json 2>/dev/null
     python - $lib $i gpurun_out/r6/on_$lib$i.json <<'PY' | tee -a $O
 import json, sys
 lib, i, p = sys.argv[1:4]

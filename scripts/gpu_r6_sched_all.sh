@@ -5,7 +5,7 @@ REPO=$PWD
 O=gpurun_out/r6/schedall; rm -rf $O; mkdir -p $O
 run() { tag=$1; lib=$2; shift 2
   (cd /tmp && PD_LIB=${lib:+$REPO/planedepth_amd/lib/libpd_var_$lib.so} timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/$tag -o k -- \
-     python $REPO/bench.py --steps 30 --warmup 5 --no_cpu_baseline --no_ddp_step --launch eager "$@" > $REPO/$O/$tag.log 2>&1); echo "$tag rc=$?"
+     python $REPO/bench.py --full --steps 30 --warmup 5 --no_cpu_baseline --no_ddp_step --launch eager "$@" > $REPO/$O/$tag.log 2>&1); echo "$tag rc=$?"
   cp $O/$tag/k_kernel_stats.csv $O/$tag.csv 2>/dev/null; rm -rf $O/$tag; }
 for lib in "" allilp allitilp; do
   run default_${lib:-product} "$lib"

@@ -11,6 +11,11 @@ It imports the reference's ``trainer.py`` / ``layers.py`` from where they lie
 every gradient as small ``.npz`` fixtures, and full-size (192x640x49) cases as
 scalar known answers in ``kat_fullsize.json``.  Only data is written — no
 reference source text.
+
+``--only-live`` writes just the vectors of tests/test_oracle_vs_reference.py
+(``live_<i>.npz``, ``add_flip_right_inputs.npz``, ``pair_transforms.npz``);
+``--check`` writes nothing and checks what only the reference itself can tell
+(the committed fixtures are current; see ``check_against_reference``).
 """
 import json
 import os
@@ -121,6 +126,96 @@ SMALL_CASES = [
     ("disp_mix_render", dict(B=2, N=5, H=8, W=16, seed=24, disp_min=0.5, disp_max=9.0, render_probability=True),
      dict(render_probability=True)),
 ]
+
+# tests/test_oracle_vs_reference.py: fresh seeds, away from SMALL_CASES' sizes, stored as live_<i>.npz (same layout)
+LIVE_CASES = [
+    (dict(B=2, N=6, H=10, W=24, seed=101, disp_min=0.5, disp_max=14.0), dict()),
+    (dict(B=1, N=9, H=16, W=32, seed=102, disp_min=0.5, disp_max=20.0, n_xz=3), dict(automask=True)),
+    (dict(B=2, N=5, H=10, W=24, seed=103, disp_min=0.5, disp_max=9.0, stereo_T=False),
+     dict(warp_type="homography_warp")),
+    (dict(B=1, N=5, H=10, W=24, seed=104, disp_min=0.5, disp_max=9.0), dict(use_mixture_loss=False, target_side="l")),
+    (dict(B=1, N=5, H=10, W=24, seed=105, disp_min=0.5, disp_max=9.0, render_probability=True),
+     dict(render_probability=True, automask=True)),
+]
+
+
+def flip_inputs(seed=8, B=2, H=6, W=10):
+    """The batch Trainer.add_flip_right_inputs is fed in tests/test_oracle_vs_reference.py (seeded: rebuilt there)."""
+    g = torch.Generator().manual_seed(seed)
+    inputs = {(k, s): torch.rand(B, 3, H, W, generator=g) for k in ("color", "color_aug") for s in ("l", "r", 1)}
+    inputs.update({("depth_gt", s): torch.rand(B, 1, H, W, generator=g) for s in ("l", "r")})
+    inputs["grid"] = torch.randn(B, 2, H, W, generator=g)
+    inputs.update({k: torch.randn(B, 4, 4, generator=g) for k in ("K", "inv_K", ("Rt", "l"), ("Rt", "r"))})
+    return inputs
+
+
+def flip_vectors(ref):
+    """trainer.py:252-276 on flip_inputs(): every output tensor as key_<i>, the dict keys (tuples as lists) in `meta`."""
+    import types
+    ns = types.SimpleNamespace(opt=types.SimpleNamespace(novel_frame_ids=[1]))
+    want = ref.trainer.Trainer.add_flip_right_inputs(ns, flip_inputs())
+    keys = list(want)
+    out = {"key_%d" % i: want[k].numpy() for i, k in enumerate(keys)}
+    out["meta"] = np.frombuffer(json.dumps([list(k) if isinstance(k, tuple) else k for k in keys]).encode(), dtype=np.uint8)
+    return out
+
+
+PAIR_H, PAIR_W, PAIR_FH, PAIR_FW, PAIR_SEED = 24, 80, 60, 200, 5
+
+
+def pair_transform_vectors(ref):
+    """The crop grids of datasets/pair_transforms.py: Resize((H, W)) of a 37x123 pair, and RandomResizeCrop((H, W),
+    factor=(0.75, 1.5)) of a FHxFW pair with numpy's and python's generators seeded PAIR_SEED (the test replays the draws)."""
+    import importlib
+    import random
+    pt = importlib.import_module("datasets.pair_transforms")
+    H, W, FH, FW = PAIR_H, PAIR_W, PAIR_FH, PAIR_FW
+    out = pt.Resize((H, W))({("color", "r", -1): torch.rand(3, 37, 123), ("color", "l", -1): torch.rand(3, 37, 123)})
+    resize_grid = out["grid"]
+    src = {("color", "r", -1): torch.rand(3, FH, FW), ("color", "l", -1): torch.rand(3, FH, FW)}
+    np.random.seed(PAIR_SEED)
+    random.seed(PAIR_SEED)
+    out = pt.RandomResizeCrop((H, W), factor=(0.75, 1.5))(dict(src))
+    return {"resize_grid": resize_grid.numpy(), "random_resize_crop_grid": out["grid"].numpy()}
+
+
+def check_against_reference(ref):
+    """What needs the reference tree itself and so is no test: the committed decoder-tail and post-process fixtures are
+    what the reference produces now (stale fixtures), and the reference's DepthDecoder raises with render_probability
+    (networks/depth_decoder.py:94-95, 259: the dispconv has all_levels - 1 channels, `logits * padding_mask` does not
+    broadcast), which is why --render_probability is served for PladeNet's outputs only."""
+    for fname, fresh in (("decoder_tail.npz", decoder_tail_vectors(ref)), ("post_process.npz", post_process_vectors(ref))):
+        stored = np.load(os.path.join(HERE, fname))
+        assert set(stored.files) == set(fresh), fname
+        for k in stored.files:
+            np.testing.assert_allclose(stored[k], fresh[k], rtol=1e-6, atol=1e-7, err_msg="%s:%s" % (fname, k))
+    B, H, W = 1, 64, 64
+    for xz in (0, 2):
+        dec = ref.networks.DepthDecoder([64, 64, 128, 256, 512], use_denseaspp=False, no_levels=4, xz_levels=xz,
+                                        use_mixture_loss=True, render_probability=True)
+        feats = [torch.randn(B, c, H >> (i + 1), W >> (i + 1)) for i, c in enumerate([64, 64, 128, 256, 512])]
+        ys = torch.linspace(-1, 1, H)[None, None, :, None].expand(B, 1, H, W)
+        xs = torch.linspace(-1, 1, W)[None, None, None, :].expand(B, 1, H, W)
+        try:
+            dec(feats, torch.cat([xs, ys], 1).contiguous())
+        except RuntimeError as e:
+            assert "must match the size" in str(e), e
+        else:
+            raise AssertionError("the reference DepthDecoder ran with render_probability (xz_levels=%d)" % xz)
+    print("check: fixtures current, DepthDecoder + render_probability raises")
+
+
+def write_live_vectors(ref):
+    for i, (bkw, rkw) in enumerate(LIVE_CASES):
+        case = build_case(**bkw)
+        res = run_reference(ref, case, **rkw)
+        blob = {"in_" + k: (v.numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in case.items()}
+        blob.update({"out_" + k: v.numpy() for k, v in res.items()})
+        blob["meta"] = np.frombuffer(json.dumps(dict(build=bkw, run=rkw)).encode(), dtype=np.uint8)
+        np.savez_compressed(os.path.join(HERE, "live_%d.npz" % i), **blob)
+    np.savez_compressed(os.path.join(HERE, "add_flip_right_inputs.npz"), **flip_vectors(ref))
+    np.savez_compressed(os.path.join(HERE, "pair_transforms.npz"), **pair_transform_vectors(ref))
+
 
 FULL_CASES = [
     ("full_disp_mix", dict(), dict()),
@@ -501,6 +596,12 @@ def main():
     if "--only-pipeline" in sys.argv:
         np.savez_compressed(os.path.join(HERE, "pipeline.npz"), **pipeline_vectors(ref))
         return
+    if "--only-live" in sys.argv:
+        write_live_vectors(ref)
+        return
+    if "--check" in sys.argv:
+        check_against_reference(ref)
+        return
     for name, bkw, rkw in SMALL_CASES:
         case = build_case(**bkw)
         res = run_reference(ref, case, **rkw)
@@ -516,6 +617,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "trainer_mono.npz"), **trainer_mono_vectors(ref))
     np.savez_compressed(os.path.join(HERE, "pipeline.npz"), **pipeline_vectors(ref))
     np.savez_compressed(os.path.join(HERE, "homography_pinned_fullsize.npz"), **fullsize_pinned_homography(ref))
+    write_live_vectors(ref)
     kat = {}
     for name, _, rkw in FULL_CASES:
         case = survey_fullsize_case()

@@ -1,8 +1,8 @@
 """Import the PlaneDepth reference (read-only, /root/reference) in THIS container.
 
 Test infrastructure only.  Used by ``make_golden.py`` to generate the golden
-vectors committed next to it, and by ``tests/test_oracle_vs_reference.py``
-(skipped automatically when /root/reference is absent, e.g. on the GPU box).
+vectors committed next to it (the tests read those vectors, never the
+reference).
 Nothing from the reference is copied: its modules are imported from where they
 lie.  The reference needs packages this image lacks, so a few
 empty stand-in modules are registered in ``sys.modules`` and ``.cuda()`` is

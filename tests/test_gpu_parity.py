@@ -1257,7 +1257,7 @@ def test_post_process_row_kernels_on_ragged_shapes(H, W, N, dmax):
 
 @pytest.mark.parametrize("H,W,N,dmax", [(4, 2, 3, 1.5), (6, 128, 20, 60.0), (5, 130, 33, 140.0), (9, 256, 63, 300.0), (3, 258, 64, 400.0),
                                         (4, 384, 70, 300.0)])
-def test_post_process_segment_kernels_vs_oracle_and_row_kernels(H, W, N, dmax):
+def test_post_process_segment_kernels_vs_oracle_and_row_kernels(H, W, N, dmax, tmp_path):
     """Round 6: the segment form of the post-process warps (two pixels per lane, 12-byte taps, all planes' samples in registers:
     N <= 32 and N <= 64 instantiations; N = 70 keeps the row kernels' softmax with the segment sum) on even widths below, at and
     beyond a 128-pixel segment, with integer disparities (the irregular planes' per-pixel path), disparities beyond the row, the
@@ -1291,7 +1291,7 @@ def test_post_process_segment_kernels_vs_oracle_and_row_kernels(H, W, N, dmax):
     for sign, flip in ((1.0, False), (-1.0, False), (-1.0, True), (1.0, True)):
         here[(sign, flip)] = (ops.warp_softmax(logits[:B].cuda(), dl[:B].cuda(), sign, flip_src=flip).cpu(),
                               ops.warp_sum(prob[:B].cuda(), dl[:B].cuda(), sign, flip_src=flip).cpu())
-    path = "/tmp/pd_pp_seg_%d_%d.pt" % (W, N)
+    path = str(tmp_path / ("pd_pp_seg_%d_%d.pt" % (W, N)))
     torch.save({"logits": logits[:B], "prob": prob[:B], "dl": lv[:B]}, path)
     code = ("import torch, sys; sys.path.insert(0, %r); from planedepth_amd import ops; z = torch.load(%r); "
             "dl = z['dl'].expand(-1, -1, %d, %d).cuda(); out = {}\n"
@@ -1426,7 +1426,7 @@ def test_bench_spawns_its_own_ranks(gpus, ddp_model):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
-                          "--no_cpu_baseline", "--no_next_rows", "--batch", "2", "--height", "64", "--width", "128", "--planes", "9",
+                          "--full", "--no_cpu_baseline", "--no_next_rows", "--batch", "2", "--height", "64", "--width", "128", "--planes", "9",
                           "--ddp_model", ddp_model],
                          env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
