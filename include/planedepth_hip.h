@@ -16,9 +16,9 @@
  *   - safe to call from any thread (e.g. the autograd thread) and for any device: the entry points work on the CURRENT
  *     device (hipSetDevice / torch.cuda.device by the caller) and keep nothing between calls except per-device caches of
  *     device facts — the LDS a workgroup can be given, the dynamic-LDS limit already granted to a kernel — held in
- *     atomics indexed by the device ordinal (the rare raise is serialised by a mutex).  The few process-environment
- *     tuning switches (PD_NO_ROWPAIR, PD_ROW_WAVES, PD_UNI_CHUNK, PD_PP_ROWS, PD_PP_SEG, PD_PP_CHAIN, PD_FWD_STREAM, PD_ROW_EPS) are read ONCE, when
- *     the library is first used, never on the launch path; kernel selection per call goes through pd_sweep_desc.impl.
+ *     atomics indexed by the device ordinal (the rare raise is serialised by a mutex).  The two process-environment
+ *     switches (PD_PP_SEG, PD_ROW_EPS) are read ONCE, when the library is first used, never on the launch path; kernel
+ *     selection per call goes through pd_sweep_desc.impl.
  */
 #ifndef PLANEDEPTH_HIP_H
 #define PLANEDEPTH_HIP_H
@@ -105,12 +105,10 @@ enum pd_sweep_impl {
                             reference's y round trip, <= 6e-6) is dropped: ~11% faster, results within 1e-4 of the
                             tensors' range on random inputs instead of 1e-6 (opt-in) */
   ,
-  PD_IMPL_TILE = 3       /* EXPERIMENTS BUILD ONLY (-DPD_EXPERIMENTS, pd_experiments() == 1; otherwise PD_ERR_UNSUPPORTED):
-                            as GENERAL, and homography_warp's backward runs the owned-tile kernel (pd_plane_sweep_tile.hip:
-                            LDS accumulators per source tile, plain stores, no zero-fill) instead of the atomic scatter.
-                            Exact and atomic-free in HBM, but 2-2.5x SLOWER on gfx950 (ds_add_f32 costs ~110 cycles per
-                            wave instruction: NOTEBOOK.md 3.4.6) - kept as an in-suite cross-check and as the record of
-                            that measurement */
+  PD_IMPL_TILE = 3       /* REMOVED: the backward returns PD_ERR_UNSUPPORTED (the value stays reserved).  It selected the
+                            owned-tile homography backward (LDS accumulators per source tile, plain stores, no zero-fill):
+                            exact and atomic-free in HBM, but 2-2.5x SLOWER on gfx950 (ds_add_f32 costs ~110 cycles per
+                            wave instruction: NOTEBOOK.md 3.4.6) */
   ,
   PD_IMPL_ROWS1 = 4      /* as AUTO, but forward and backward are the target-ordered, one-pixel-per-lane row-shift kernels
                             (pd_plane_sweep_rowshift.hip, the headline kernels of rounds 1-2) instead of the segment-stream
@@ -144,14 +142,11 @@ const char* pd_last_error(void);
 /* sha256[:16] over the kernel sources and headers this library was compiled from (the .hip and .h files under csrc/ and
  * include/: __graft_entry__.source_hash), baked in at build time (-DPD_SRC_HASH); "unknown" for a build without it. */
 const char* pd_source_hash(void);
-/* 1 if the library was built with -DPD_EXPERIMENTS: the kernels measured SLOWER than the defaults (four-pixels-per-lane
- * row kernels, owned-tile backward, one-kernel plane-uniform backward; NOTEBOOK.md 3.5) are then compiled in and selectable
- * (PD_IMPL_TILE; PD_QUAD_FWD / PD_QUAD_BWD / PD_UNI_FUSED in the environment).  The product library returns 0. */
+/* Always 0.  It reported a library built with the kernels that lost their A/B runs, which are no longer part of the
+ * sources; kept so that callers that check it keep working. */
 int pd_experiments(void);
-/* What else this binary was compiled with, as bits: 1 = -DPD_EXPERIMENTS (as pd_experiments()); 2 = -DPD_DIAGNOSTICS — a
- * timing-ablation or trace build of the headline kernels (PD_FS_ABL, PD_STREAM_ABL, PD_ABLATE, PD_FS_TRACE, ...: parts of the
- * arithmetic or of the memory traffic compiled OUT, results WRONG by design; those switches refuse to compile without
- * -DPD_DIAGNOSTICS).  The product library returns 0; tests/test_capi.py and bench.py's `library` block check it. */
+/* Always 0.  It reported experiments (1) and timing-ablation / trace builds (2, results wrong by design), neither of which
+ * can be built any more; kept because bench.py's `library` block and tests/test_capi.py read it. */
 int pd_build_flags(void);
 
 /* 1 if pd_plane_sweep_bwd adds into a pre-zeroed g_plane under PD_BWD_PLANE_ZEROED for this descriptor (see the flag; a
@@ -355,7 +350,7 @@ int pd_smooth_loss_bwd_padded(int B, int C, int H, int W, int x_pad, const float
  * [B,N,H,W]; PD_PP_FLIP_SRC reads `planes` mirrored along x (the .flip(-1) of
  * trainer.py:451) without a flipped copy.  Per-plane disparities with an even W and N <= 64 (pd_warp_sum: any N) take the segment
  * form (two pixels per lane, 12-byte taps, the softmax's samples of all planes in registers: sampled once); PD_PP_SEG=0 keeps
- * the one-pixel-per-lane row kernels, PD_PP_ROWS=0 the per-pixel gather form (both exact: cross-checks).
+ * the one-pixel-per-lane row kernels (exact: cross-check); dense disparities take the per-pixel gather form.
  */
 enum pd_pp_flags { PD_PP_DISP_DENSE = 1, PD_PP_FLIP_SRC = 2, PD_PP_DISP_ROWS = 4 };
 int pd_warp_softmax(int B, int N, int H, int W, float sign, int flags, const float* planes, const float* disp,
@@ -370,7 +365,7 @@ int pd_pp_combine(int B, int H, int W, const float* disp, const float* o_fr, con
 
 /* trainer.py:443-465 behind ONE call (three launches on `stream` where a row's softmax fits the CU's LDS — per-plane disparities,
  * even W <= 1024, N <= 64: the "row chains" keep softmax(warp(logits)) in LDS and take the second warp's plane sum from there, the
- * [B,N,H,W] intermediate never reaches memory; PD_PP_CHAIN=0 or any other shape: the six launches of the single warps): logits / probability [2B,N,H,W] and disp [2B,1,H,W] are the fixed
+ * [B,N,H,W] intermediate never reaches memory; PD_PP_SEG=0 or any other shape: the six launches of the single warps): logits / probability [2B,N,H,W] and disp [2B,1,H,W] are the fixed
  * model's outputs for cat([image, mirrored image]) (B = half of that batch; of `probability` only the first B images are read),
  * disp_layered [2B,N], PD_PP_DISP_ROWS [2B,N,H] or PD_PP_DISP_DENSE [2B,N,H,W]; workspace: pd_post_process_workspace_floats floats;
  * -> disp_pp, mask_novel [B,1,H,W]. */

@@ -85,7 +85,7 @@ def _zero_block(device, shape):
     n = 1
     for k in shape:
         n *= int(k)
-    if torch.cuda.is_current_stream_capturing() or not S.ZERO_POOL or n > _ZERO_BLOCK_FLOATS // 8:
+    if torch.cuda.is_current_stream_capturing() or n > _ZERO_BLOCK_FLOATS // 8:
         return torch.zeros(shape, device=device, dtype=torch.float32)
     key = (device.index, C.raw_stream(device))
     st = _ZERO_BLOCKS.get(key)

@@ -180,7 +180,7 @@ def on_device(device):
     return torch.cuda.device(device)
 
 
-_RAW_STREAM = None if os.environ.get("PD_RAW_STREAM") == "0" else getattr(torch._C, "_cuda_getCurrentRawStream", None)   # (PD_RAW_STREAM=0: A/B)
+_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # (absent from some torch builds: the Stream object then)
 
 
 def raw_stream(device=None):

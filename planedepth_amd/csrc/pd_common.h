@@ -22,13 +22,7 @@ int check_launch(const char* what);
 // first launch), never on the launch path: an entry point's behaviour cannot change between two calls of a process, and
 // workspace sizing and launch always agree.  Kernel selection that tests need per call goes through pd_sweep_desc.impl.
 struct Switches {
-  bool no_rowpair;    // PD_NO_ROWPAIR=1: forward without row pairs
-  bool pp_rows_off;   // PD_PP_ROWS=0: post-process kernels in per-pixel gather form
   bool pp_seg_off;    // PD_PP_SEG=0: post-process kernels without the segment form (one pixel per lane, planes sampled twice)
-  bool pp_chain_off;  // PD_PP_CHAIN=0: pd_post_process through the single warps (the softmax's [B,N,H,W] intermediate in memory)
-  int row_waves;      // PD_ROW_WAVES=n: waves per row workgroup of the row-shift kernels (0 = default)
-  int uni_chunk;      // PD_UNI_CHUNK=n: images per launch of the plane-uniform backward passes (0 = whole batch)
-  bool fwd_stream;    // PD_FWD_STREAM=0: the headline forward on the plane-group row-shift kernel instead of the segment-stream one
 };
 const Switches& switches();
 
@@ -65,15 +59,10 @@ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 // Measured at 8x49x192x640 (scripts/gpu_r2_band.sh): plane-uniform kernels fwd 0.161 -> 0.148 ms, bwd 0.538 -> 0.518 ms;
 // the general per-plane kernels do NOT want it (disp_warp forward 0.233 -> 0.571 ms: their taps stay in the row, and
 // a band per XCD takes the DRAM-page sharing between concurrently running neighbours away), so only the former use it.
-#ifndef PD_XCD_BAND
-#define PD_XCD_BAND 1
-#endif
 constexpr int kXcds = 8;
 __device__ __forceinline__ int xcd_banded(int bx, int nblk) {
-#if PD_XCD_BAND
   const int per = nblk / kXcds;   // blocks per band; a remainder keeps its place at the end
   if (bx < per * kXcds) return (bx % kXcds) * per + bx / kXcds;
-#endif
   return bx;
 }
 

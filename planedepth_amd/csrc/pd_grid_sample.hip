@@ -58,9 +58,7 @@ __global__ __launch_bounds__(kBlock) void grid_sample_bwd_kernel(int C, int Hi, 
   for (int c = 0; c < C; ++c) {
     const long plane = ((long)m * C + c) * Hi * Wi;
     const float go = live ? g_out[((long)m * C + c) * HWo + pix] : 0.0f;
-#ifndef PD_GS_NOSCATTER  // diagnostics: the kernel without its atomics
     if (g_in) bilinear_scatter_wave(g_in + plane, t, Wi, go, live, sp);
-#endif
     if (g_grid && live) {
       float dx, dy;
       bilinear_grad(in + plane, t, Wi, dx, dy);

@@ -232,13 +232,9 @@ __global__ __launch_bounds__(kBlock) void sweep_bwd_kernel(SweepArgs a, BwdOut o
       }
     } else {  // adjoint of the bilinear gather, all 64 lanes together (pd_common.h: neighbours share their atomics)
       const long pl = ((long)b * a.N + n) * HW;
-#ifdef PD_GEN_NOSCATTER  // diagnostics: the kernel without its atomics (keeps the values alive through one lane's store)
-      if (sg_l + sg_s == 123.456f) o.g_logits[pl] = sg_l;
-#else
       const ScatterPlan sp = plan_scatter(st, a.W, live);
       if (MIX && o.g_sigma) bilinear_scatter_wave(o.g_sigma + pl, st, a.W, sg_s, live, sp);
       if (o.g_logits) bilinear_scatter_wave(o.g_logits + pl, st, a.W, sg_l, live, sp);
-#endif
     }
     if (reduce_plane) {
       const int ln = threadIdx.x & (kWave - 1);
@@ -440,9 +436,9 @@ static SweepArgs make_args(const pd_sweep_desc* d, const float* src, const float
   a.row_eps = (d->impl == PD_IMPL_FAST_ROWS) ? kFastRowWeight : (d->impl == PD_IMPL_EXACT_ROWS) ? 0.0f : auto_row_eps();
   a.fast_rows = a.row_eps > 0.0f ? 1 : 0;
   // row pairs need one scalar disparity per plane (the sampling column is then the same in both rows) and no per-pixel
-  // or per-row mask; PD_NO_ROWPAIR=1 (environment) switches them off for A/B runs
+  // or per-row mask
   a.pairs = (d->mode == PD_WARP_DISP && !(d->flags & (PD_DISP_DENSE | PD_DISP_ROWS | PD_MASK_ROWS | PD_RENDER_PROB)) &&
-             padding_mask == nullptr && !a.fast_rows && !switches().no_rowpair) ? 1 : 0;
+             padding_mask == nullptr && !a.fast_rows) ? 1 : 0;
   a.has_mask = (d->mode == PD_WARP_DISP && padding_mask != nullptr && !mask_rows) ? 1 : 0;
   a.src = src; a.tgt = tgt; a.logits = logits; a.sigma = sigma;
   a.plane = plane; a.plane_aux = plane_aux; a.inv_K3 = inv_K3;
@@ -469,9 +465,6 @@ extern "C" int pd_sweep_bwd_accumulates(const pd_sweep_desc* d) {
   if (!d) return 0;
   if (wants_rowshift(d) && rowshift_applicable(d)) return 0;   // owner-computes ring stores: no read-modify-write form
   if (d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM)) return 1;
-#ifdef PD_EXPERIMENTS
-  if (tile_bwd_applicable(d)) return 0;
-#endif
   return 1;                                                    // the atomic scatter accumulates by nature
 }
 
@@ -489,15 +482,9 @@ extern "C" size_t pd_sweep_bwd_workspace_floats(const pd_sweep_desc* d) {
   const size_t K = (d->mode == PD_WARP_DISP) ? 1 : 9;
   const size_t general = (size_t)d->B * bwd_blocks(d->H * d->W) * d->N * K;
   const size_t rows = rowshift_applicable(d) ? rowshift_bwd_workspace_floats(d) : 0;
-#ifdef PD_EXPERIMENTS
-  const size_t tiles = tile_bwd_applicable(d) ? tile_bwd_workspace_floats(d) : 0;
-#else
-  const size_t tiles = 0;
-#endif
   const size_t uni = (d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM)) ? uniform_bwd_workspace_floats(d) : 0;
   const size_t gat = gather_bwd_applicable(d) ? gather_bwd_workspace_floats(d) : 0;
   size_t m = general > rows ? general : rows;
-  m = m > tiles ? m : tiles;
   m = m > gat ? m : gat;
   return m > uni ? m : uni;
 }
@@ -532,10 +519,6 @@ extern "C" int pd_plane_sweep_fwd(const pd_sweep_desc* d, const float* src, cons
     // default for the headline shape: one wave per 128-pixel segment streams over the planes (pd_plane_sweep_fwdstream.hip);
     // PD_IMPL_ROWS1 keeps the plane-group row-shift forward (cross-check, A/B)
     if (d->impl != PD_IMPL_ROWS1 && fwdstream_applicable(d, a)) return fwdstream_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
-#ifdef PD_EXPERIMENTS   // wide-access forward (2 / 4 pixels per lane): faster isolated, slower inside the step (NOTEBOOK.md 3.5.6)
-    if (rowquad_applicable(d, a.has_mask != 0) && getenv("PD_QUAD_FWD"))
-      return rowquad_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
-#endif
     return rowshift_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
   }
   if (d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM))
@@ -573,9 +556,6 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   o.rgb_rec = rgb_rec; o.stash = stash; o.g_rgb_rec = g_rgb_rec; o.g_ph_map = g_ph_map; o.g_ph_mean = g_ph_mean;
   if (wants_rowshift(d) && rowshift_applicable(d)) {
     PD_REQUIRE(workspace, "the row-shift backward needs workspace (pd_sweep_bwd_workspace_floats)");
-#ifdef PD_EXPERIMENTS
-    if (rowquad_applicable(d, ak.has_mask != 0) && getenv("PD_QUAD_BWD")) return rowquad_bwd(d, ak, o, stream);
-#endif
     // default: lanes own aligned source slots, waves stream along plane rows (pd_plane_sweep_rowstream.hip);
     // PD_IMPL_ROWS1 keeps the target-ordered row-shift backward (cross-check, A/B)
     if (tail) {   // pd_plane_sweep_bwd_tail: the row-stream backward with the decoder tail's backward riding along
@@ -599,17 +579,10 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
     PD_REQUIRE(workspace, "the plane-uniform backward needs workspace (pd_sweep_bwd_workspace_floats)");
     return uniform_bwd(d, ak, o, workspace, stream);
   }
-#ifdef PD_EXPERIMENTS
-  if (tile_bwd_applicable(d)) {   // PD_IMPL_TILE: source tiles owned by workgroups, no atomics, no zero-fill
-    PD_REQUIRE(workspace, "the tile backward needs workspace (pd_sweep_bwd_workspace_floats)");
-    return tile_bwd(d, ak, o, workspace, stream);
-  }
-#else
   if (d->impl == PD_IMPL_TILE) {
-    set_error("PD_IMPL_TILE (the owned-tile backward) is built with -DPD_EXPERIMENTS only: it is slower than the default kernels");
+    set_error("PD_IMPL_TILE (the owned-tile backward) was removed: it was slower than the default kernels");
     return PD_ERR_UNSUPPORTED;
   }
-#endif
   if (gather_bwd_applicable(d) && (g_logits || g_sigma)) {   // one homography per plane: two passes, no atomics (pd_plane_sweep_gather.hip)
     PD_REQUIRE(workspace, "the gather backward needs workspace (pd_sweep_bwd_workspace_floats)");
     const GatherPlan gp = gather_bwd_plan(d, workspace);
@@ -733,10 +706,6 @@ extern "C" int pd_uniform_bwd_pair(const pd_sweep_desc* d, const float* src, con
   PD_REQUIRE(va->workspace && vb->workspace, "view: workspace (pd_sweep_bwd_workspace_floats) must not be NULL");
   const bool mix = (d->flags & PD_MIXTURE) != 0;
   PD_REQUIRE(!g_logits || !mix || g_sigma, "PD_MIXTURE needs g_sigma next to g_logits");
-  if (switches().uni_chunk && switches().uni_chunk < d->B) {
-    set_error("pd_uniform_bwd_pair needs the whole batch's scratch (PD_UNI_CHUNK is set)");
-    return PD_ERR_UNSUPPORTED;
-  }
   SweepArgs a = make_args(d, src, va->tgt, logits, sigma, va->plane, va->plane_aux, va->inv_K3, va->padding_mask, va->dists);
   SweepArgs b = make_args(d, src, vb->tgt, logits, sigma, vb->plane, vb->plane_aux, vb->inv_K3, vb->padding_mask, vb->dists);
   BwdOut oa{}, ob{};

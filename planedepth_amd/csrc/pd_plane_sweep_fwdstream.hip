@@ -49,73 +49,21 @@ namespace pd {
 // all that ever fits and the allocator may use the 128 VGPRs that four waves per SIMD leave (launch bound = the 1024-thread
 // maximum).  Rounds 4's 96-register cap (five waves per SIMD) bought nothing — two such workgroups never fitted a CU.
 
-#ifndef PD_FS_REVERSE
-#define PD_FS_REVERSE 0   // row groups dispatched bottom-up (the backward then walks top-down: PD_BWD_REVERSE 0)
-#endif
-#ifndef PD_FS_ABL
-#define PD_FS_ABL 0   // timing experiments only (wrong results; scripts/gpu_r5_ladder.sh): 1 colour cells at a 16-byte lane stride,
-#endif                // 2 no LDS colour reads, 4 no softmax / mixture arithmetic, 8 no output / stash stores, 16 every row as one
-                      // source row, 32 no coordinate chain, 64 no tap loads, 128 no tap interpolation, 256 no staging loads
-#ifndef PD_FS_SHRING
-#define PD_FS_SHRING 1  // 1: a plane's staged shift is read from LDS ONE iteration before its tap loads are issued and kept in
-#endif                  // scalar registers until the plane is reduced (one LDS read per iteration, off the critical path, instead of
-                        // two round trips at the head of every iteration)
-#ifndef PD_FS_PRIO
-#define PD_FS_PRIO 1    // 1: wave priority rotating every PD_FS_PRIO_PERIOD x 4 planes (every wave of a SIMD leads for a quarter of them)
-#endif
-#ifndef PD_FS_PRIO_PERIOD
-#define PD_FS_PRIO_PERIOD 1
-#endif
-#ifndef PD_FS_FIXREF
-#define PD_FS_FIXREF 1  // 1: softmax with a FIXED per-pixel reference (the first plane's scaled logit) on the regular planes: no
-#endif                  // lazy-rescale branch per pixel and plane (a compare, an exec-mask branch and the copies of all seven running
-                        // sums at its join: a sixth of the loop's VALU instructions).  The largest exponent a pixel used is tracked
-                        // (one v_max per plane); a wave in which any pixel went beyond 2^kFixRefLimit redoes its planes with the
-                        // rescaling accumulator (per-pixel general path) — exact for any input, never taken for logits within
-                        // +-60 of each other
-#ifndef PD_FS_TRACE
-#define PD_FS_TRACE 0   // diagnostics build: s_memtime stamps per wave (entry, staged, loop end, exit) + HW_ID / XCC_ID into a device
-#endif                  // array read back through pd_debug_fs_trace (scripts/diag_fwd_trace.py)
-#ifndef PD_FS_LDS_PAD
-#define PD_FS_LDS_PAD 0   // timing experiments: extra LDS bytes per workgroup (caps the workgroups per CU)
-#endif
 #ifndef PD_FS_ROWS
 #define PD_FS_ROWS 3   // consecutive target rows per workgroup where its 16 waves allow (each row: one wave per segment).  Measured
 #endif                 // at 8x49x192x640, isolated / in the step: 1 row 0.114 / 0.128 ms, 2 rows 0.119 / 0.131, 3 rows 0.104 / 0.122
                        // — 15 waves that read three adjacent rows (7.5 KB) of every plane at about the same time
-#ifndef PD_DIAGNOSTICS   // timing-ablation / trace code (results wrong by design) compiles only into a library that says so: pd_build_flags()
-#if PD_FS_ABL || PD_FS_TRACE || PD_FS_LDS_PAD
-#error "timing-ablation / trace switches need -DPD_DIAGNOSTICS as well (pd_build_flags() then reports the build)"
-#endif
-#endif
-constexpr float kFixRefLimit = 90.0f;  // PD_FS_FIXREF: largest base-2 exponent of a softmax term before the wave falls back
+// Softmax with a FIXED per-pixel reference (the first plane's scaled logit) on the regular planes: no lazy-rescale branch per
+// pixel and plane (a compare, an exec-mask branch and the copies of all seven running sums at its join: a sixth of the loop's
+// VALU instructions).  The largest exponent a pixel used is tracked (one v_max per plane); a wave in which any pixel went
+// beyond 2^kFixRefLimit redoes its planes with the rescaling accumulator (per-pixel general path) — exact for any input, never
+// taken for logits within +-60 of each other.
+constexpr float kFixRefLimit = 90.0f;  // largest base-2 exponent of a softmax term before the wave falls back
 constexpr int kFsSeg = 2 * kWave;      // target pixels per wave
 constexpr int kFsGuard = 4;            // zero cells on each side of the colour row
 constexpr int kFsThreadsMax = 1024;    // 16 waves: rows up to 2048 pixels
 
 typedef float v3f __attribute__((ext_vector_type(3)));
-
-#if PD_FS_TRACE
-constexpr int kFsTraceWgs = 4096, kFsTraceWords = 6;   // per wave: 4 stamps, hw ids, (image << 16 | first row)
-__device__ unsigned long long g_fs_trace[kFsTraceWgs * 16 * kFsTraceWords];
-__device__ __forceinline__ void fs_stamp(int slot) {
-  const int wg = blockIdx.y * gridDim.x + blockIdx.x;
-  if (wg < kFsTraceWgs && (threadIdx.x & (kWave - 1)) == 0)
-    g_fs_trace[((long)wg * 16 + (threadIdx.x >> 6)) * kFsTraceWords + slot] = __builtin_amdgcn_s_memtime();
-}
-__device__ __forceinline__ void fs_stamp_ids(int b, int y) {
-  const int wg = blockIdx.y * gridDim.x + blockIdx.x;
-  if (wg < kFsTraceWgs && (threadIdx.x & (kWave - 1)) == 0) {
-    const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    unsigned long long* p = g_fs_trace + ((long)wg * 16 + (threadIdx.x >> 6)) * kFsTraceWords;
-    p[4] = ((unsigned long long)xcc << 32) | hw;
-    p[5] = ((unsigned long long)b << 32) | (unsigned)y;
-  }
-}
-#else
-__device__ __forceinline__ void fs_stamp(int) {}
-__device__ __forceinline__ void fs_stamp_ids(int, int) {}
-#endif
 
 __device__ __forceinline__ v3f fs_load3(Rsrc r, unsigned byte_off) {
   return __builtin_bit_cast(v3f, __builtin_amdgcn_raw_buffer_load_b96(r, (int)byte_off, 0, 0));
@@ -209,7 +157,6 @@ __device__ __forceinline__ void fs_stage_row(const SweepArgs& a, const RowSel& r
   auto blended = [&](int x) {   // source colour at column x of the (vertically blended) row; zero outside the row
     float4 cc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (x >= 0 && x < W) {
-      if (PD_FS_ABL & 256) return make_float4((float)x, 0.5f, 0.25f, 0.0f);
       const float* p = srcb + (long)row.yA * W + x;
       cc = make_float4(p[0], p[HW], p[2 * HW], 0.0f);
       if (two) {   // fl(B*wB + fl(A*wA)): the rounding the row-stream backward stages (its knife-edge note applies here too)
@@ -272,30 +219,20 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
   }
   FwdAcc acc[2];
   RenderState rs[2];
-  float dmax[2] = {-INFINITY, -INFINITY};   // PD_FS_FIXREF: largest exponent used so far
+  float dmax[2] = {-INFINITY, -INFINITY};   // fixed-reference softmax: largest exponent used so far
   FsTaps<NROWS> g[D + 1];
   int pn = 0;
-#if PD_FS_SHRING
+  // A plane's staged shift is read from LDS ONE iteration before its tap loads are issued and kept in scalar registers until
+  // the plane is reduced (one LDS read per iteration, off the critical path, instead of two round trips at the head of every
+  // iteration).
   int sh_sd[D + 1], sh_kk[D + 1];          // wave-uniform (SGPRs): the shifts of the planes whose taps are in flight
   int2 sh_next = shift[0];       // LDS read in flight: the shift of the next plane to be prefetched
-#endif
   auto prefetch = [&](FsTaps<NROWS>& grp, int slot) {
     const int n = min(pn, N - 1);   // past the end: re-load the last plane (unused) — unconditional issue keeps the wait counts right
-#if PD_FS_SHRING
     sh_sd[slot] = __builtin_amdgcn_readfirstlane(sh_next.x);
     sh_kk[slot] = __builtin_amdgcn_readfirstlane(sh_next.y);
     sh_next = shift[min(pn + 1, N - 1)];
     const int k = sh_kk[slot] >> 1;
-#else
-    const int k = __builtin_amdgcn_readfirstlane(shift[n].y) >> 1;
-#endif
-    if (PD_FS_ABL & 64) {   // timing only: no tap loads, lane- and plane-dependent stand-ins
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        grp.l[0][q] = grp.l[NROWS - 1][q] = xt0f * 1e-3f + (float)(k + q) * 1e-2f;
-        grp.s[0][q] = grp.s[NROWS - 1][q] = 0.5f + xt0f * 1e-4f + (float)(k - q) * 1e-4f;
-      }
-    } else
     fs_issue<MIX, NROWS>(grp, a, r, n, (unsigned)(xt0 + k) << 2, HW);
     if (RENDER) {   // unshifted, coalesced: read where the pixels are, not where they sample (the last plane has none: alpha = 1)
       const float2 d2 = *reinterpret_cast<const float2*>(a.dists + ((long)r.b * (N - 1) + min(n, N - 2)) * HW + pix);
@@ -304,14 +241,8 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
     ++pn;
   };
   auto step = [&](const FsTaps<NROWS>& grp, int n, int slot, int next_slot) {
-#if PD_FS_SHRING
     const float sd = __int_as_float(sh_sd[slot]);
     const int kk = sh_kk[slot];
-#else
-    const int2 sh = shift[n];
-    const float sd = __int_as_float(__builtin_amdgcn_readfirstlane(sh.x));
-    const int kk = __builtin_amdgcn_readfirstlane(sh.y);
-#endif
     const int k = kk >> 1;
     const int c0 = seg * kFsSeg + k;   // source column of the segment's first left tap (wave-uniform); lane i loads c0 + 2i ..
     // 12-byte form: regular plane, and no lane's load starts at column -3, -2 or -1: a load that starts left of the row reads
@@ -322,28 +253,18 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
       fs_general_plane<MIX, NROWS, RENDER>(a, r, col, n, sd, xt0f, HW, Wm1, rcpWm1, t, ea, automask, acc, rs, grp.dist);
       return;
     }
-    float4 cv0, cv1, cv2;
-    {
-      const int cell = min(max(xt0 + k, -kFsGuard), W + 1) + kFsGuard;
-      if (PD_FS_ABL & 2) {   // timing only: no LDS colour reads
-        cv0 = make_float4(xt0f * 1e-3f, 0.25f, 0.5f, 0.0f); cv1 = make_float4(0.75f, xt0f * 1e-3f, 0.5f, 0.0f); cv2 = make_float4(0.1f, 0.2f, xt0f * 1e-3f, 0.0f);
-      } else {
-        cv0 = col[cell]; cv1 = col[cell + 1]; cv2 = col[cell + 2];
-      }
-    }
+    const int cell = min(max(xt0 + k, -kFsGuard), W + 1) + kFsGuard;
+    const float4 cv0 = col[cell], cv1 = col[cell + 1], cv2 = col[cell + 2];
     const float kf = (float)k;
     const float xs0 = xt0f + kf, xs1 = xs0 + 1.0f, xs2 = xs1 + 1.0f;   // integers below 2^24: exact in any order
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const float xtf = xt0f + (float)i;
       const float xsf = (i == 0) ? xs0 : xs1;
-      const float ix = (PD_FS_ABL & 32) ? xsf + (sd - kf) : stream_ix(xtf, sd, Wm1, rcpWm1);
+      const float ix = stream_ix(xtf, sd, Wm1, rcpWm1);
       const float w1 = ix - xsf, w0 = ((i == 0) ? xs1 : xs2) - ix;   // torch's (ix - x0), (x1 - ix) with x0 = xt + k
       float l, s = 0.0f;
-      if (PD_FS_ABL & 128) {   // timing only: the loaded values are consumed, not interpolated
-        l = grp.l[0][i] + grp.l[0][i + 1] + grp.l[NROWS - 1][i] * r.wB;
-        if (MIX) s = grp.s[0][i] + grp.s[0][i + 1] + grp.s[NROWS - 1][i + 1] * r.wB;
-      } else if (NROWS == 1) {
+      if (NROWS == 1) {
         l = grp.l[0][i] * w0 + grp.l[0][i + 1] * w1;
         if (MIX) s = grp.s[0][i] * w0 + grp.s[0][i + 1] * w1;
       } else {
@@ -353,9 +274,7 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
       }
       const float4 ca = (i == 0) ? cv0 : cv1, cb = (i == 0) ? cv1 : cv2;
       const float c0v = ca.x * w0 + cb.x * w1, c1v = ca.y * w0 + cb.y * w1, c2v = ca.z * w0 + cb.z * w1;
-      if (PD_FS_ABL & 4) {   // timing only: no softmax / mixture arithmetic
-        acc[i].Z += l; acc[i].S += s; acc[i].C0 += c0v; acc[i].C1 += c1v; acc[i].C2 += c2v; acc[i].Mx += w0; acc[i].m = 0.0f;
-      } else if (PD_FS_FIXREF && !RENDER) {
+      if (!RENDER) {
         const float d = l * kLog2e - acc[i].m;   // (m = -inf until a plane set it: d = +inf trips the limit below)
         asm("v_max_f32 %0, %1, %2" : "=v"(dmax[i]) : "v"(dmax[i]), "v"(d));   // (fmaxf adds a canonicalising v_max of the running value)
         mixture_accumulate<MIX>(acc[i], exp2_fast(d), s, c0v, c1v, c2v, t[i], t[2 + i], t[4 + i], ea[i], automask);
@@ -365,7 +284,7 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
   };
 #pragma unroll
   for (int j = 0; j < D; ++j) prefetch(g[j], j);
-  if (PD_FS_FIXREF && !RENDER) {   // the reference: plane 0's scaled logit at the lane's two pixels (when plane 0 takes the 12-byte form;
+  if (!RENDER) {   // the reference: plane 0's scaled logit at the lane's two pixels (when plane 0 takes the 12-byte form;
     const int2 sh0 = shift[0];   // otherwise the general path's rescaling accumulator sets it when it reduces that plane)
     const float sd = __int_as_float(__builtin_amdgcn_readfirstlane(sh0.x));
     const int kk = __builtin_amdgcn_readfirstlane(sh0.y), k = kk >> 1, c0 = seg * kFsSeg + k;
@@ -388,14 +307,12 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
   }
   int n = 0;
   for (; n + (D + 1) <= N; n += D + 1) {
-#if PD_FS_PRIO == 1   // every wave of a SIMD leads for a quarter of the planes
-    switch (((threadIdx.x >> 8) + (n / ((D + 1) * PD_FS_PRIO_PERIOD))) & 3) {
+    switch (((threadIdx.x >> 8) + n / (D + 1)) & 3) {   // wave priority rotating every D + 1 planes: every wave of a SIMD leads for a quarter of them
       case 0: __builtin_amdgcn_s_setprio(0); break;
       case 1: __builtin_amdgcn_s_setprio(1); break;
       case 2: __builtin_amdgcn_s_setprio(2); break;
       default: __builtin_amdgcn_s_setprio(3); break;
     }
-#endif
 #pragma unroll
     for (int j = 0; j <= D; ++j) {
       prefetch(g[(j + D) % (D + 1)], (j + D) % (D + 1));
@@ -409,7 +326,7 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
       step(g[j], n + j, j, (j + 1) % (D + 1));
     }
   }
-  if (PD_FS_FIXREF && !RENDER) {
+  if (!RENDER) {
     const bool beyond = dmax[0] > kFixRefLimit || dmax[1] > kFixRefLimit;
     if (__builtin_amdgcn_ballot_w64(beyond) != 0) {   // rare: this wave again, every plane through the rescaling accumulator
       acc[0] = FwdAcc(); acc[1] = FwdAcc();
@@ -418,15 +335,11 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
                                              rcpWm1, t, ea, automask, acc, rs, g[0].dist);
     }
   }
-#if PD_FS_PRIO == 1
   __builtin_amdgcn_s_setprio(0);   // (the rotating priority of the plane loop ends with it)
-#endif
-  fs_stamp(2);
   if (!live) return 0.0f;
   // ---- finish the two pixels: outputs + the backward's stash, 8-byte stores -------------------------------------------
   const FwdResult r0 = fwd_finish<MIX>(acc[0], t[0], t[2], t[4], ea[0], automask, !RENDER);   // (compositing weights are used as they are)
   const FwdResult r1 = fwd_finish<MIX>(acc[1], t[1], t[3], t[5], ea[1], automask, !RENDER);
-  if ((PD_FS_ABL & 8) && r0.ph != 123.456f) return r0.ph + r1.ph;   // timing only: no output / stash stores
   float* st = stash + (long)r.b * a.stash_k * HW + pix;
   *reinterpret_cast<float2*>(st) = make_float2(r0.lse2, r1.lse2);
   *reinterpret_cast<float2*>(st + HW) = make_float2(r0.Sn, r1.Sn);
@@ -446,8 +359,7 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
 // staging stores; the fences keep the compiler from moving LDS accesses across.
 // INVARIANT: every wave of a team runs the round loop of fwdstream_kernel the same number of times and reaches this barrier
 // in every round — the loop's only exits (`pos >= T`) are workgroup-uniform.  A per-wave early exit or `continue` before the
-// barrier would leave the team's other waves polling for ever, with no diagnostic (PD_FS_ROUNDS=1 builds, one item per
-// workgroup and a plain __syncthreads, are the fallback).
+// barrier would leave the team's other waves polling for ever, with no diagnostic.
 __device__ __forceinline__ void fs_team_barrier(int* cnt, int target) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   if ((threadIdx.x & (kWave - 1)) == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -510,27 +422,22 @@ __global__ __launch_bounds__(kFsThreadsMax) void fwdstream_kernel(SweepArgs a, f
     const int pos = r * nbk + k;
     if (pos >= T) break;                                         // (workgroup-uniform)
     const int item = order.n ? (int)order.it[pos] : pos;
-    const int b = item % a.B, gsel = item / a.B;
-    const int grp = PD_FS_REVERSE ? groups - 1 - gsel : gsel;
+    const int b = item % a.B, grp = item / a.B;
     const int seg = cb * segs + (wave - slot * segs);            // which segment of the row
     const int y = rowtab.n ? (int)rowtab.y[grp * rows + slot] : grp * rows + slot;
     const bool active = y < a.H && seg < nseg;
     const RowSel row = two_row_form(make_row_sel(y < a.H ? y : 0, a.H), a.row_eps);
     float4* col = lds4 + (slot * nbuf + (r & 1)) * row_f4;
     int2* shift = reinterpret_cast<int2*>(col + CWk);
-    fs_stamp(0);
-    fs_stamp_ids(b, y);
     fs_stage_row(a, row, b, y, tix, nthr, col, shift);
     // rounds == 1: the kernel's only barrier before the outputs, every wave reaches it whatever its row needs; persistent: the
     // team's own (the buffer written here was last read two rounds ago, and every wave of the team has passed the barrier of
     // the round in between since)
     if (!RENDER && rounds > 1) fs_team_barrier(team + slot, segs * (r + 1));
     else __syncthreads();
-    fs_stamp(1);
     if (!active) {}
-    else if (row.nrows == 2 && !(PD_FS_ABL & 16)) ph_sum += fwdstream_body<MIX, AUTO, 2, RENDER>(a, row, b, y, seg, col, shift, rgb_rec, ph_map, stash);
-    else                                          ph_sum += fwdstream_body<MIX, AUTO, 1, RENDER>(a, row, b, y, seg, col, shift, rgb_rec, ph_map, stash);
-    fs_stamp(3);
+    else if (row.nrows == 2) ph_sum += fwdstream_body<MIX, AUTO, 2, RENDER>(a, row, b, y, seg, col, shift, rgb_rec, ph_map, stash);
+    else                     ph_sum += fwdstream_body<MIX, AUTO, 1, RENDER>(a, row, b, y, seg, col, shift, rgb_rec, ph_map, stash);
   }
   if (a.ph_mean) {  // fused `.mean()` of trainer.py:742: wave totals -> LDS -> ONE atomic per workgroup
     const float v = wave_sum_hi(ph_sum);
@@ -549,12 +456,6 @@ __global__ __launch_bounds__(kFsThreadsMax) void fwdstream_kernel(SweepArgs a, f
 // ---------------------------------------------------------------------------------------------------------------
 // Workgroup shape: rows of up to 5 segments (640 pixels) go whole, wider ones in column blocks of equal size; PD_FS_ROWS rows
 // per workgroup where their waves fit its 16, else what fits.
-#ifndef PD_FS_BALANCE
-#define PD_FS_BALANCE 1   // 0: the persistent workgroups take the items in launch order (A/B)
-#endif
-#ifndef PD_FS_ROUNDS
-#define PD_FS_ROUNDS 0   // items per (persistent) workgroup: 0 = as many as give every CU one workgroup, 1 = one item per workgroup
-#endif
 struct FsShape { int rows, cblocks, segs, rounds, nbk; size_t lds; };
 static int device_cu_count() {
   static std::atomic<int> cus[kMaxDevices];
@@ -580,18 +481,18 @@ static FsShape fwdstream_shape(const pd_sweep_desc* d) {
   // walk its share of the items; smaller workgroups (several resident per CU) keep the dispatcher's one item per workgroup
   const int items = ceil_div(d->H, s.rows) * s.cblocks * d->B;
   const int waves = s.rows * s.segs;
-  s.rounds = PD_FS_ROUNDS ? PD_FS_ROUNDS : (2 * waves > kFsThreadsMax / kWave ? ceil_div(items, device_cu_count()) : 1);
+  s.rounds = 2 * waves > kFsThreadsMax / kWave ? ceil_div(items, device_cu_count()) : 1;
   if (d->flags & PD_RENDER_PROB) s.rounds = 1;
   if (s.rounds < 1) s.rounds = 1;
   if (s.rounds > 8) s.rounds = 8;
   s.nbk = ceil_div(ceil_div(d->H, s.rows) * d->B, s.rounds);   // blocks per column block
   const size_t row_f4 = (size_t)d->W + 2 * kFsGuard + ((size_t)d->N + 1) / 2;
   s.lds = s.rows * (s.rounds > 1 ? 2 : 1) * row_f4 * sizeof(float4) + (size_t)(kFsThreadsMax / kWave) * sizeof(float) +
-          (size_t)(kFsThreadsMax / kWave) * sizeof(int) + PD_FS_LDS_PAD;
+          (size_t)(kFsThreadsMax / kWave) * sizeof(int);
   if (s.rounds > 1 && s.lds > device_lds_bytes()) {   // the second row buffers do not fit: one item per workgroup
     s.rounds = 1;
     s.nbk = ceil_div(d->H, s.rows) * d->B;
-    s.lds = s.rows * row_f4 * sizeof(float4) + (size_t)(kFsThreadsMax / kWave) * (sizeof(float) + sizeof(int)) + PD_FS_LDS_PAD;
+    s.lds = s.rows * row_f4 * sizeof(float4) + (size_t)(kFsThreadsMax / kWave) * (sizeof(float) + sizeof(int));
   }
   return s;
 }
@@ -617,9 +518,6 @@ static bool host_row_is_heavy(int y, int H, float row_eps, int* partner = nullpt
 // 41 MB of excess reads).  Groups need not be consecutive rows — each team has its own row buffer — so: chains of linked rows are
 // cut into pieces of at most `rows`, the pieces go first-fit (longest first) into the G groups, single rows fill the holes in order.
 // H = 192, rows = 3: two links left cut (the chains 24-28 and 30-33) instead of fifteen.
-#ifndef PD_FS_REGROUP
-#define PD_FS_REGROUP 1   // 0: consecutive rows (A/B)
-#endif
 static FsRows fwdstream_rows(int H, int R, float row_eps) {
   struct Cache { int H = 0, R = 0; float eps = -1.0f; FsRows t; };
   static thread_local Cache c;   // (the table depends on the height, the rows per group and the threshold only)
@@ -628,7 +526,7 @@ static FsRows fwdstream_rows(int H, int R, float row_eps) {
   c.H = H; c.R = R; c.eps = row_eps;
   FsRows& t = c.t;
   t.n = 0;
-  if (!PD_FS_REGROUP || R < 2 || G * R > kFsRowsMax) return t;
+  if (R < 2 || G * R > kFsRowsMax) return t;
   static thread_local unsigned char link[kFsRowsMax], placed[kFsRowsMax], fill[kFsRowsMax];
   int nlinks = 0;
   for (int y = 0; y < H; ++y) link[y] = placed[y] = 0;
@@ -676,7 +574,7 @@ static FsOrder fwdstream_order(const pd_sweep_desc* d, const FsShape& sh, float 
   FsOrder o;
   o.n = 0;
   const int groups = ceil_div(d->H, sh.rows), T = groups * d->B;
-  if (!PD_FS_BALANCE || sh.rounds < 2 || T > kFsOrderMax) return o;
+  if (sh.rounds < 2 || T > kFsOrderMax) return o;
   int weight[kFsOrderMax], sorted[kFsOrderMax];
   for (int g = 0; g < groups; ++g) {
     int w = 0;
@@ -705,7 +603,7 @@ static FsOrder fwdstream_order(const pd_sweep_desc* d, const FsShape& sh, float 
 }
 
 bool fwdstream_applicable(const pd_sweep_desc* d, const SweepArgs& a) {
-  if (!rowshift_applicable(d) || a.has_mask || !switches().fwd_stream) return false;
+  if (!rowshift_applicable(d) || a.has_mask) return false;
   if ((d->flags & PD_RENDER_PROB) && (((long)d->H * d->W) % 2 != 0 || (reinterpret_cast<uintptr_t>(a.dists) & 7))) return false;
   // pixel pairs: even width, 8-byte aligned rows of the per-pixel tensors (their bases come 8-byte aligned from any allocator
   // that hands out float2-aligned memory; checked because the boundary takes raw pointers)
@@ -763,12 +661,3 @@ extern "C" int pd_debug_fwd_row_groups(int H, int rows, float row_eps, unsigned 
   if (cut) *cut = nc;
   return t.n;
 }
-
-#if PD_FS_TRACE
-// diagnostics build only (not declared in include/planedepth_hip.h): copies the stamps of the last launch to the host
-extern "C" int pd_debug_fs_trace(unsigned long long* host_dst, long words) {
-  const long have = (long)pd::kFsTraceWgs * 16 * pd::kFsTraceWords;
-  if (hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(pd::g_fs_trace), sizeof(unsigned long long) * (words < have ? words : have)) != hipSuccess) return 1;
-  return 0;
-}
-#endif

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kRowThreadsMax, HASMASK ? 3 : PD_FWD_OCC) void rows
   // LDS: colour rows float4[2*(W+4)] | sdisp[N] | parked partial sums [nwaves][2][8][64]
   float* sdisp = reinterpret_cast<float*>(lds4 + 2 * (a.W + 4));
   float* parts = sdisp + a.N;
-  const int y = block_row(wg_rowid(a.B, a.H), a.H);
+  const int y = wg_rowid(a.B, a.H);
   const RowSel row = two_row_form(make_row_sel(y, a.H), a.row_eps);
   float ph_sum = 0.0f;
   int partner = y;
@@ -158,13 +158,7 @@ __device__ __forceinline__ void bwd_compute(const PlaneGroup<NROWS, U>& g, const
                                             const PixelCtx& c, int HW, float gix_scale, int want_plane,
                                             int gl_bytes, int gs_bytes, uint32_t& bits, RenderBwd* rb = nullptr) {
   const int W = a.W, N = a.N;
-#if PD_TC_IN_GROUP
   const ColourTaps<NROWS>* tc = g.tc;
-#else
-  ColourTaps<NROWS> tc[U];  // all LDS reads of the group first, then the arithmetic
-#pragma unroll
-  for (int u = 0; u < U; ++u) tc[u] = load_colour_taps<NROWS>(lrgb, W, colour_off(g.ct[u].x0, W));
-#endif
   float gds[U], outl[U], outs[U];
   unsigned xoffs[U];
 #pragma unroll
@@ -240,7 +234,7 @@ __device__ __forceinline__ void bwd_compute(const PlaneGroup<NROWS, U>& g, const
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       hl[u] = hs[u] = 0.0f;
-      if (PD_BWD_HANDOVER && sc.lane == 0) {
+      if (sc.lane == 0) {
         float* rp = bnd.rec + (sc.seg_prev * N + n0 + u) * 2;
         hl[u] = atomicExch(rp, 0.0f);
         if (MIX) hs[u] = atomicExch(rp + 1, 0.0f);
@@ -275,7 +269,7 @@ template <bool MIX, bool HASMASK, int NROWS, bool RENDER = false>
 __device__ __forceinline__ void rowshift_bwd_body(const SweepArgs& a, const BwdOut& o, const RowSel& row,
                                                   float* sdisp, int* kshift, float* red, const Boundary& bnd, float4* lrgb) {
   constexpr int U = PD_BWD_U;
-  const int y = block_row(bwd_rowid(a.B, a.H), a.H), b = wg_image(a.B, a.H);
+  const int y = bwd_rowid(a.B, a.H), b = wg_image(a.B, a.H);
   const int HW = a.H * a.W, W = a.W, N = a.N;
   const int lane = threadIdx.x & (kWave - 1), nwaves = __builtin_amdgcn_readfirstlane(blockDim.x >> 6);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // provably wave-uniform: stays in SGPRs
@@ -324,36 +318,19 @@ __device__ __forceinline__ void rowshift_bwd_body(const SweepArgs& a, const BwdO
     rb.Rtot = MIX ? -c.A * c.mx : c.gdotr;
     uint32_t bits = 0;
     // same software pipeline as the forward (the mask comes from the stash bits, not from memory)
-    PlaneGroup<NROWS, U> g0, g1, g2;
+    PlaneGroup<NROWS, U> g0, g1;
     const int nfull = (n_hi - n_lo) / U;
 #define PD_BISSUE(GR, I) group_issue<MIX, false, NROWS, U, RENDER>(GR, a, row, lbytes, sdisp, b, y, n_lo + (I) * U, sc.xt, HW, Wm1, rcpWm1)
 #define PD_BCOMP(GR, I) bwd_compute<MIX, HASMASK, NROWS, U, RENDER>(GR, a, o, row, lbytes, kshift, red, bnd, b, y, n_lo + (I) * U, sc, c, HW, gix_scale, want_plane, gl_bytes, gs_bytes, bits, &rb)
     int gi = 0;
-    if (PD_BWD_PF && PD_BWD_PF_DEPTH == 2) {
-      if (nfull > 0) PD_BISSUE(g0, 0);
-      for (; gi + 2 <= nfull; gi += 2) {
-        PD_BISSUE(g1, gi + 1);
-        PD_BCOMP(g0, gi);
-        PD_BISSUE(g0, min(gi + 2, nfull - 1));  // unconditional: see the forward
-        PD_BCOMP(g1, gi + 1);
-      }
-      if (gi < nfull) PD_BCOMP(g0, gi);
-    } else if (PD_BWD_PF) {
-      if (nfull > 0) PD_BISSUE(g0, 0);
-      if (nfull > 1) PD_BISSUE(g1, 1);
-      for (; gi + 3 <= nfull; gi += 3) {
-        PD_BISSUE(g2, gi + 2);
-        PD_BCOMP(g0, gi);
-        PD_BISSUE(g0, min(gi + 3, nfull - 1));
-        PD_BCOMP(g1, gi + 1);
-        PD_BISSUE(g1, min(gi + 4, nfull - 1));
-        PD_BCOMP(g2, gi + 2);
-      }
-      if (gi < nfull) PD_BCOMP(g0, gi);
-      if (gi + 1 < nfull) PD_BCOMP(g1, gi + 1);
-    } else {
-      for (; gi < nfull; ++gi) { PD_BISSUE(g0, gi); PD_BCOMP(g0, gi); }
+    if (nfull > 0) PD_BISSUE(g0, 0);
+    for (; gi + 2 <= nfull; gi += 2) {
+      PD_BISSUE(g1, gi + 1);
+      PD_BCOMP(g0, gi);
+      PD_BISSUE(g0, min(gi + 2, nfull - 1));  // unconditional: see the forward
+      PD_BCOMP(g1, gi + 1);
     }
+    if (gi < nfull) PD_BCOMP(g0, gi);
 #undef PD_BISSUE
 #undef PD_BCOMP
     for (int n = n_lo + nfull * U; n < n_hi; ++n) {
@@ -412,7 +389,7 @@ __global__ __launch_bounds__(kRowThreadsMax, PD_BWD_OCC) void rowshift_bwd_kerne
   bnd.rec = red + a.N;
   bnd.irr = reinterpret_cast<unsigned*>(bnd.rec + 2 * nsn);
   bnd.side = o.side + ((long)wg_image(a.B, a.H) * a.H + bwd_rowid(a.B, a.H)) * (4L * nsn);
-  const RowSel row = two_row_form(make_row_sel(block_row(bwd_rowid(a.B, a.H), a.H), a.H), a.row_eps);
+  const RowSel row = two_row_form(make_row_sel(bwd_rowid(a.B, a.H), a.H), a.row_eps);
   if (row.nrows == 2) rowshift_bwd_body<MIX, HASMASK, 2, RENDER>(a, o, row, sdisp, kshift, red, bnd, lds4);
   else                rowshift_bwd_body<MIX, HASMASK, 1, RENDER>(a, o, row, sdisp, kshift, red, bnd, lds4);
 }
@@ -443,9 +420,6 @@ __global__ void div_check_kernel(float Wm1, int count, float lo, float step, int
 // Waves per row-workgroup (each wave walks its share of the row's 64-lane segments).
 static int row_threads(int W) {
   const int nseg = ceil_div(W, kWave);
-  if (const int w = switches().row_waves) {  // tuning hook (PD_ROW_WAVES, read once)
-    if (w >= 1 && w <= kRowThreadsMax / kWave) return (w < nseg ? w : nseg) * kWave;   // the kernels' launch bound
-  }
   // Measured on MI355X (W=640, 10 segments): 4, 5, 8 and 10 waves per workgroup are within 3% of each other, 1-2
   // waves are 1.5-2.5x slower (too few waves in flight).  Take the largest divisor of nseg up to 8 for equal work
   // per wave; awkward (prime) segment counts fall back to 8 waves with a ragged last pass.

@@ -47,15 +47,6 @@ namespace pd {
 #define PD_STREAM_WAVES 8   // waves per row workgroup: 42 KB of LDS per 640-pixel row -> three workgroups = 24 waves per CU
                             // (4 / 12 / 16 waves measured 0.193 / 0.183 / 0.230 ms against 0.176-0.186; rows wider than ~800: 2x)
 #endif
-#ifndef PD_STREAM_ABL
-#define PD_STREAM_ABL 0  // timing experiments only (wrong results): 1 no context reads, 2 no per-plane gradient math,
-#endif                   // 4 every row as one source row, 8 no gradient stores, 16 no coordinate chain
-#ifndef PD_DIAGNOSTICS   // timing-ablation / trace code (results wrong by design) compiles only into a library that says so: pd_build_flags()
-#if PD_STREAM_ABL
-#error "timing-ablation / trace switches need -DPD_DIAGNOSTICS as well (pd_build_flags() then reports the build)"
-#endif
-#endif
-constexpr int kStreamAbl = PD_STREAM_ABL;
 #ifndef PD_STREAM_STORE_AUX
 #define PD_STREAM_STORE_AUX 2   // cache-policy bits of the gradient stores (1 = sc0, 2 = nt, 16 = sc1; 0 = write-back).  nt: the
 #endif                          // 385 MB of gradients stream past the caches instead of leaving ~256 MB of dirty lines behind for
@@ -67,16 +58,14 @@ constexpr int kStreamAbl = PD_STREAM_ABL;
 #ifndef PD_STREAM_LOAD_AUX
 #define PD_STREAM_LOAD_AUX 0    // same for the tap loads
 #endif
-#ifndef PD_STREAM_DEAD
-#define PD_STREAM_DEAD 1  // (plane, segment) items none of whose slots has a target inside the row (shift beyond the segment: the near planes'
-#endif                    // leading segments) issue no memory reads (zero-extent descriptors), read no context, do no arithmetic and store
-                          // the zeros they have to store: 11 of the 245 items of a headline row (round 6)
-#ifndef PD_STREAM_PRIO
-#define PD_STREAM_PRIO 1  // wave priority of a row workgroup's phases (s_setprio): 1 = the staging and the ring's first loads at 3, the item loop
-#endif                    // at 0 — a workgroup that has just arrived on the CU gets through its dependent round trips ahead of the two that are
-                          // streaming (-0.9 % alone, -2.2 % with the max-ilp scheduler, __graft_entry__.FILE_FLAGS); 2 = the first D+1 items at 3
-                          // as well (where -mllvm -amdgpu-set-wave-priority puts it: the same within the noise); 0 = none.  Measured and dropped
-                          // (NOTEBOOK 11.5): a rotating leader per SIMD as in the forward (+13 %), loads above arithmetic or below it (+1-4 %)
+// Dead items: (plane, segment) items none of whose slots has a target inside the row (shift beyond the segment: the near planes'
+// leading segments) issue no memory reads (zero-extent descriptors), read no context, do no arithmetic and store the zeros they
+// have to store: 11 of the 245 items of a headline row (round 6).
+// Wave priority of a row workgroup's phases (s_setprio): the staging and the ring's first loads at 3, the item loop at 0 — a
+// workgroup that has just arrived on the CU gets through its dependent round trips ahead of the two that are streaming (-0.9 %
+// alone, -2.2 % with the max-ilp scheduler, __graft_entry__.FILE_FLAGS).  Measured and dropped (NOTEBOOK 11.5): the first D+1
+// items at 3 as well (where -mllvm -amdgpu-set-wave-priority puts it: the same within the noise), a rotating leader per SIMD as
+// in the forward (+13 %), loads above arithmetic or below it (+1-4 %).
 #ifndef PD_STREAM_OCC
 #define PD_STREAM_OCC 4  // launch bound (1024 threads): the allocator's cap is 128 VGPRs; the kernel uses 76 = 6 waves per SIMD
 #endif
@@ -108,7 +97,7 @@ struct StreamLds {
   int* special;   // [1]  any plane with a negative shift or an irregular one (the epilogue has work)
   float4* tail;   // TAIL: [CW] per SOURCE pixel (lse of the decoder's logits, 1 / sum pi/sigma, disp, d loss / d disp)
   float* dpl;     // TAIL: [N]  the planes' disparities (unsigned, unclamped: the decoder's disp_layered)
-  int* live;      // [N]  PD_STREAM_DEAD: first live segment | (one past the last live segment) << 16
+  int* live;      // [N]  dead items: first live segment | (one past the last live segment) << 16
   int CW;
 };
 
@@ -212,16 +201,14 @@ __device__ __forceinline__ void stream_compute(const StreamGroup<NROWS>& g, cons
   const float xs0f = (float)(seg * kSeg) + lane2f;
   const float xt0f = xs0f - (float)k;   // integers below 2^24: exact
   // context of the two paired targets xt, xt+1: adjacent cells (guard cells two deep on both sides keep them adjacent)
-  // (PD_STREAM_ABL & 32, timing only: cells at a 16-byte lane stride — the context reads without their 2-way bank conflict)
-  const int cell = (kStreamAbl & 32) ? min(max((xs0 >> 1) - k, -2), a.W) + 2 : min(max(xs0 - k, -2), a.W) + 2;
+  const int cell = min(max(xs0 - k, -2), a.W) + 2;
   const float4 cv0 = col_at<PK>(L, xs0 + 2), cv1 = col_at<PK>(L, xs0 + 3), cv2 = col_at<PK>(L, xs0 + 4);
   float cl0[kSlots], cl1[kSlots], cs0[kSlots], cs1[kSlots];
 #pragma unroll
   for (int i = 0; i < kSlots; ++i) {
-    PixelCtx c;
-    if (kStreamAbl & 1) { c = zero_pixel_ctx(); c.t0 = lane2f; c.gr0 = sd; c.A = xs0f; } else c = ctx_at(L, cell + i);
+    const PixelCtx c = ctx_at(L, cell + i);
     const float xsf = xs0f + (float)i;
-    const float ix = (kStreamAbl & 16) ? xsf + 0.25f : stream_ix(xt0f + (float)i, sd, Wm1, rcpWm1);
+    const float ix = stream_ix(xt0f + (float)i, sd, Wm1, rcpWm1);
     const float w1 = ix - xsf, w0 = (xsf + 1.0f) - ix;   // torch's (x1 - ix), (ix - x0) with x0 = xs
     float l, s = 0.0f, dlx, dsx = 0.0f;
     if (NROWS == 1) {
@@ -242,9 +229,7 @@ __device__ __forceinline__ void stream_compute(const StreamGroup<NROWS>& g, cons
     }
     const float4 ca = (i == 0) ? cv0 : cv1, cb = (i == 0) ? cv1 : cv2;
     const float c0 = ca.x * w0 + cb.x * w1, c1 = ca.y * w0 + cb.y * w1, c2 = ca.z * w0 + cb.z * w1;
-    PlaneGrad pg;
-    if (kStreamAbl & 2) { pg.g_l = l + c.t0; pg.g_s = s + c.gr0; pg.gc0 = c0 + c.A; pg.gc1 = c1; pg.gc2 = c2; }
-    else pg = plane_grad<MIX>(c, l, s, c0, c1, c2);
+    const PlaneGrad pg = plane_grad<MIX>(c, l, s, c0, c1, c2);
     const float m0 = (NROWS == 1) ? w0 : w0 * r.wy, m1 = (NROWS == 1) ? w1 : w1 * r.wy;
     cl0[i] = pg.g_l * m0; cl1[i] = pg.g_l * m1;
     cs0[i] = pg.g_s * m0; cs1[i] = pg.g_s * m1;
@@ -273,12 +258,9 @@ __device__ __forceinline__ void stream_compute(const StreamGroup<NROWS>& g, cons
     if (want_plane) gacc += a.sign * (t0.gdl + t1.gdl);   // (the row's sum is scaled by d ix / d disp = sign at the end: sign^2 = 1)
   }
   const unsigned soff = (unsigned)seg * (kSeg * 4);
-  if (!(kStreamAbl & 8) || out_l0 == 123.456f)
   buf_store2(row_rsrc_bytes(plane_ptr(o.g_logits + (long)r.b * a.N * HW + (long)r.y * a.W, n, HW), gl_bytes), lane8, soff, out_l0, out_l1);
-  if (MIX) {
-    if (!(kStreamAbl & 8) || out_s0 == 123.456f)
+  if (MIX)
     buf_store2(row_rsrc_bytes(plane_ptr(o.g_sigma + (long)r.b * a.N * HW + (long)r.y * a.W, n, HW), gs_bytes), lane8, soff, out_s0, out_s1);
-  }
 }
 
 // General form for one paired slot xs of plane n (n may differ per lane): the target xt = xs - k with its EXACT
@@ -374,7 +356,7 @@ __device__ __forceinline__ void stream_stage_ctx(const SweepArgs& a, const BwdOu
   }
 }
 
-// One plane's staged shift (stream_body's form) + its live segment range (PD_STREAM_DEAD).  Returns "special".
+// One plane's staged shift (stream_body's form) + its live segment range (dead items).  Returns "special".
 template <bool TAIL>
 __device__ __forceinline__ int stage_shift(const SweepArgs& a, const StreamLds& L, int i, float plane_i, bool masked, int nseg) {
   const int W = a.W;
@@ -426,7 +408,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   float carry_l = 0.0f, carry_s = 0.0f, gacc = 0.0f;
   int n = i0 / nseg, seg = i0 - n * nseg;            // the item being computed
   int pn = n, pseg = seg;                            // the item being prefetched
-  constexpr bool kDead = PD_STREAM_DEAD && !TAIL;    // (TAIL: a dead item's stores still carry the tail's own terms, which need the taps)
+  constexpr bool kDead = !TAIL;                      // (TAIL: a dead item's stores still carry the tail's own terms, which need the taps)
   int p_live = nseg << 16;                           // live segment range of the plane being prefetched (lo | hi << 16): all, until staged
   auto advance = [&](int& nn, int& ss) {
     ++ss;
@@ -442,7 +424,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   };
 
   // ---- stage the row: per-target-pixel context, blended colour row, per-plane shifts -----------------------------
-  if (PD_STREAM_PRIO) __builtin_amdgcn_s_setprio(3);   // a workgroup that has just arrived gets through its dependent round trips ahead of the streaming ones
+  __builtin_amdgcn_s_setprio(3);   // a workgroup that has just arrived gets through its dependent round trips ahead of the streaming ones
   int special;
   stream_stage_ctx<MIX, NROWS, PK, TAIL>(a, o, r, L, HW);
   if (threadIdx.x == 0) *L.special = 0;
@@ -511,7 +493,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   if (i0 < i1) {
 #pragma unroll
     for (int j = 0; j < D; ++j) prefetch(g[j]);
-    if (PD_STREAM_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     int it = i0;
     for (; it + (D + 1) <= i1; it += D + 1) {
 #pragma unroll
@@ -519,7 +501,6 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
         prefetch(g[(j + D) % (D + 1)]);
         step(g[j]);
       }
-      if (PD_STREAM_PRIO == 2) __builtin_amdgcn_s_setprio(0);
     }
 #pragma unroll
     for (int j = 0; j <= D; ++j) {
@@ -564,7 +545,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
     }
     __syncthreads();
   }
-  if (PD_STREAM_PRIO) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
   if (want_plane) {
     const float gix_scale = (Wm1 / 2) * 2.0f / Wm1 * a.sign;  // d ix / d disp through un-normalise, *2, /(W-1)
     if (a.flags & PD_DISP_ROWS) {  // one disparity per (plane, row): this workgroup owns the whole sum
@@ -577,10 +558,6 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
     }
   }
 }
-
-#ifdef PD_EXPERIMENTS   // row pairs in the backward (round 6): measured slower; the kernel lives in scripts/experiments/
-#include "pd_rowstream_pairs.inc"
-#endif
 
 // (TAIL: the tail's terms take the kernel from 77 to 93 VGPRs, which costs the third resident workgroup; bounded at six waves per
 // SIMD it keeps it for twelve spilled dwords outside the loop: 0.175 against 0.196 ms, next to 0.174 + 0.208 ms for the two kernels)
@@ -600,10 +577,10 @@ __global__ __launch_bounds__(kStreamThreadsMax, TAIL ? 6 : PD_STREAM_OCC) void r
   L.special = reinterpret_cast<int*>(L.hand + 2 * (blockDim.x >> 6));
   L.dpl = reinterpret_cast<float*>(L.special + 4);
   L.live = reinterpret_cast<int*>(L.dpl + a.N);
-  const int y = block_row(bwd_rowid(a.B, a.H), a.H), b = wg_image(a.B, a.H);
+  const int y = bwd_rowid(a.B, a.H), b = wg_image(a.B, a.H);
   const RowSel row = two_row_form(make_row_sel(y, a.H), a.row_eps);
-  if (row.nrows == 2 && !(kStreamAbl & 4)) stream_body<MIX, 2, PK, TAIL>(a, o, b, y, row, L);
-  else                                     stream_body<MIX, 1, PK, TAIL>(a, o, b, y, row, L);
+  if (row.nrows == 2) stream_body<MIX, 2, PK, TAIL>(a, o, b, y, row, L);
+  else                stream_body<MIX, 1, PK, TAIL>(a, o, b, y, row, L);
 }
 
 __global__ void reduce_rows_stream_kernel(const float* __restrict__ partials, float* __restrict__ out, int R, int M) {
@@ -667,42 +644,17 @@ bool rowstream_bwd_tail_applicable(const pd_sweep_desc* d, const SweepArgs& a) {
          (d->sign == 1.0f || d->sign == -1.0f) && rowstream_shape(d, true).lds <= device_lds_bytes();
 }
 
-#ifdef PD_EXPERIMENTS
-#include "pd_rowstream_pairs_host.inc"
-#else
-static bool rowstream_pairs(const pd_sweep_desc*, const SweepArgs&, bool) { return false; }
-#endif
-
 int rowstream_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, hipStream_t stream) {
   const bool tail = o.tail_stash != nullptr;
   const bool mix = (d->flags & PD_MIXTURE) != 0;
+  const StreamShape sh = rowstream_shape(d, tail);
+  const dim3 grid(d->H, d->B), block(sh.nwaves * kWave);
   int rc;
-#ifdef PD_EXPERIMENTS
-  static const bool pairs_on = getenv("PD_BWD_PAIRS") != nullptr;
-#else
-  constexpr bool pairs_on = false;
-#endif
-  if (pairs_on && rowstream_pairs(d, a, tail)) {
-#ifdef PD_EXPERIMENTS
-    const int items = d->N * ceil_div(d->W, kSeg);
-    const int nwaves = items < PD_STREAM_PAIR_WAVES ? items : PD_STREAM_PAIR_WAVES;
-    const dim3 block(nwaves * kWave);
-    const size_t lds = rowstream_pair_lds_bytes(d, nwaves);
-    const StreamUnits& units = rowstream_units(d->H);
-    rc = mix ? rowstream_pair_launch<true>(a, o, units, d->B, block, lds, stream)
-             : rowstream_pair_launch<false>(a, o, units, d->B, block, lds, stream);
-#else
-    rc = PD_ERR_UNSUPPORTED;
-#endif
-  } else {
-    const StreamShape sh = rowstream_shape(d, tail);
-    dim3 grid(d->H, d->B), block(sh.nwaves * kWave);
-    if (tail)     rc = rowstream_launch<true, false, true>(a, o, grid, block, sh.lds, stream);
-    else if (mix) rc = sh.packed ? rowstream_launch<true, true, false>(a, o, grid, block, sh.lds, stream)
-                                 : rowstream_launch<true, false, false>(a, o, grid, block, sh.lds, stream);
-    else          rc = sh.packed ? rowstream_launch<false, true, false>(a, o, grid, block, sh.lds, stream)
-                                 : rowstream_launch<false, false, false>(a, o, grid, block, sh.lds, stream);
-  }
+  if (tail)     rc = rowstream_launch<true, false, true>(a, o, grid, block, sh.lds, stream);
+  else if (mix) rc = sh.packed ? rowstream_launch<true, true, false>(a, o, grid, block, sh.lds, stream)
+                               : rowstream_launch<true, false, false>(a, o, grid, block, sh.lds, stream);
+  else          rc = sh.packed ? rowstream_launch<false, true, false>(a, o, grid, block, sh.lds, stream)
+                               : rowstream_launch<false, false, false>(a, o, grid, block, sh.lds, stream);
   if (rc) return rc;
   rc = check_launch("rowstream_bwd_kernel");
   if (rc || !o.g_plane || (d->flags & (PD_DISP_ROWS | PD_BWD_PLANE_ZEROED))) return rc;

@@ -30,8 +30,8 @@
 // Two views of one source image (the novel frames -1 / +1): pd_uniform_fwd_pair runs both forwards in one launch (PairSlot),
 // pd_uniform_bwd_pair the whole backward in one call (first passes, pair gather, reductions).
 // The whole batch goes through each pass in one launch (parallelism beat keeping one image's scratch in the 256 MB
-// memory-side cache: uniform_chunk); workgroups are dealt to the XCDs in contiguous bands of the image (xcd_banded).
-// Opt-in alternative (PD_UNI_FUSED): both passes in one kernel with an LDS hand-over per plane — exact, slower.
+// memory-side cache: uniform_bwd); workgroups are dealt to the XCDs in contiguous bands of the image (xcd_banded).
+// Measured and dropped: both passes in one kernel with an LDS hand-over per plane — exact, slower (uniform_bwd).
 // Measured and dropped for the target-side kernels: the two horizontal taps of a row as one 8-byte buffer load with the
 // weights permuted onto the pair (4 instead of 8 memory instructions per pixel and plane): forward 0.147 -> 0.157 ms,
 // pass 1 0.189 -> 0.211 ms — unlike the row kernels' shifted streams these pairs are not 8-byte aligned AND not
@@ -228,9 +228,7 @@ constexpr int kUniG = 4;
 
 template <bool MIX, bool RENDER = false>
 __global__ __launch_bounds__(kBlock) void uniform_bwd_pass1_kernel(SweepArgs a, BwdOut o, int b0, float* __restrict__ tmp,
-                                                                   float* __restrict__ partials, const float* __restrict__ tw,
-                                                                   const int* __restrict__ run_flag) {
-  if (run_flag && *run_flag == 0) return;   // the fused kernel served the whole launch
+                                                                   float* __restrict__ partials, const float* __restrict__ tw) {
   __shared__ float red[kUniG * 9];
   const int HW = a.H * a.W, N = a.N;
   const int ntiles = gridDim.x;
@@ -432,10 +430,9 @@ template <bool MIX, bool OVERFLOW>
 __global__ __launch_bounds__(kBlock) void uniform_bwd_pass2_kernel(SweepArgs a, int b0, const float* __restrict__ tmp,
                                                                    const UniPrep* __restrict__ prep,
                                                                    float* __restrict__ g_logits, float* __restrict__ g_sigma,
-                                                                   int* __restrict__ overflow_flag, const int* __restrict__ run_flag,
-                                                                   int accumulate, int list_limit = kUniK) {
+                                                                   int* __restrict__ overflow_flag, int accumulate,
+                                                                   int list_limit = kUniK) {
   // list_limit (OVERFLOW only): the register slots of the kernel this one follows (kUniK, or kPairK after the pair kernel)
-  if (run_flag && *run_flag == 0) return;        // the fused kernel served the whole launch
   const int HW = a.H * a.W, N = a.N, W = a.W, H = a.H;
   const int spix = xcd_banded(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
   const int b = b0 + blockIdx.y;
@@ -890,18 +887,10 @@ __global__ __launch_bounds__(kStageThreads) void uniform_bwd_pass2_pair_kernel(P
   }
 }
 
-#ifdef PD_EXPERIMENTS   // the one-kernel form (LDS hand-over, no scratch): measured slower; lives in scripts/experiments/
-#include "pd_plane_sweep_uniform_fused.inc"
-#endif
-
-
-// partial sums of the kernels that ran: the fused kernel's unless it raised the flag
-__global__ void uniform_reduce_kernel(const float* __restrict__ part_fused, int nblk_fused, const float* __restrict__ part_two,
-                                      int nblk_two, const int* __restrict__ irregular_flag, float* __restrict__ out, int M) {
+// partials [B][nblk][M] of the first pass -> out [B][M]
+__global__ void uniform_reduce_kernel(const float* __restrict__ partials, int nblk, float* __restrict__ out, int M) {
   const int j = blockIdx.x, b = blockIdx.y;
-  const bool two = (*irregular_flag != 0) || part_fused == nullptr;
-  const float* p = (two ? part_two + (long)b * nblk_two * M : part_fused + (long)b * nblk_fused * M) + j;
-  const int nblk = two ? nblk_two : nblk_fused;
+  const float* p = partials + (long)b * nblk * M + j;
   float acc = 0.0f;
   for (int i = threadIdx.x; i < nblk; i += kWave) acc += p[(long)i * M];
   acc = wave_sum(acc);
@@ -913,20 +902,11 @@ __global__ void uniform_reduce_kernel(const float* __restrict__ part_fused, int 
 // ---------------------------------------------------------------------------------------------------------------
 static size_t ualign4(size_t floats) { return (floats + 3) & ~(size_t)3; }
 
-// images per launch of the two backward passes: enough workgroups to fill the chip, a scratch that still fits the
-// 256 MB memory-side cache (2 x N x H x W floats per image)
-static int uniform_chunk(const pd_sweep_desc* d) {
-  if (const int c = switches().uni_chunk) return c < d->B ? c : d->B;   // PD_UNI_CHUNK, read once
-  const size_t per_image = (size_t)2 * d->N * d->H * d->W * sizeof(float);
-  (void)per_image;   // measured at 8x49x192x640: 1 / 2 / 4 / 8 images per launch -> 2.16 / 1.83 / 1.42 / 0.99 ms: parallelism
-  return d->B;        // beats cache residency, so the whole batch goes in one launch per pass
-}
-
-// workspace: 2 x [B][nblk][4*9] partial sums (two-pass / fused) | UniPrep[B] | scratch [chunk][2][N][H][W]
+// workspace: [B][nblk][4*9] partial sums | UniPrep[B] | scratch [B][2][N][H][W]
 size_t uniform_bwd_workspace_floats(const pd_sweep_desc* d) {
-  const size_t nblk = (size_t)ceil_div(d->H * d->W, kBlock);   // (>= the fused kernel's tile count: 256 <= 13 * 60)
-  return 2 * ualign4((size_t)d->B * nblk * kUniG * 9) + ualign4((size_t)d->B * (sizeof(UniPrep) / sizeof(float))) +
-         (size_t)uniform_chunk(d) * 2 * d->N * d->H * d->W + 8;
+  const size_t nblk = (size_t)ceil_div(d->H * d->W, kBlock);
+  return ualign4((size_t)d->B * nblk * kUniG * 9) + ualign4((size_t)d->B * (sizeof(UniPrep) / sizeof(float))) +
+         (size_t)d->B * 2 * d->N * d->H * d->W + 8;
 }
 
 template <bool PAIR>
@@ -951,17 +931,15 @@ int uniform_fwd_pair(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec,
 }
 
 // where the backward keeps its pieces inside a workspace
-struct UniformWs { float* part_two; float* part_fused; UniPrep* prep; float* tmp; int* overflow; int* irregular; };
+struct UniformWs { float* part_two; UniPrep* prep; float* tmp; int* overflow; };
 static UniformWs uniform_ws(const pd_sweep_desc* d, float* workspace) {
   const int nblk = ceil_div(d->H * d->W, kBlock);
   const uintptr_t base = (reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15;
   UniformWs w;
   w.part_two = reinterpret_cast<float*>(base);
-  w.part_fused = w.part_two + ualign4((size_t)d->B * nblk * kUniG * 9);
-  w.prep = reinterpret_cast<UniPrep*>(w.part_fused + ualign4((size_t)d->B * nblk * kUniG * 9));
+  w.prep = reinterpret_cast<UniPrep*>(w.part_two + ualign4((size_t)d->B * nblk * kUniG * 9));
   w.tmp = reinterpret_cast<float*>(w.prep) + ualign4((size_t)d->B * (sizeof(UniPrep) / sizeof(float)));
-  w.overflow = reinterpret_cast<int*>(&w.prep[0].pad[0]);    // both written 0 by uniform_prep_kernel
-  w.irregular = reinterpret_cast<int*>(&w.prep[0].pad[1]);
+  w.overflow = reinterpret_cast<int*>(&w.prep[0].pad[0]);    // written 0 by uniform_prep_kernel
   return w;
 }
 
@@ -971,7 +949,6 @@ int uniform_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, flo
   const bool mix = (d->flags & PD_MIXTURE) != 0;
   const UniformWs w = uniform_ws(d, workspace);
   float* part_two = w.part_two;
-  float* part_fused = w.part_fused;
   UniPrep* prep = w.prep;
   float* tmp = w.tmp;
   const float* tw = a.padding_mask;
@@ -979,70 +956,42 @@ int uniform_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, flo
   ak.padding_mask = nullptr;
   uniform_prep_kernel<<<ceil_div(d->B, 64), 64, 0, stream>>>(a.plane, prep, d->B);
   int rc = check_launch("uniform_prep_kernel");
+  if (rc) return rc;
   int* overflow = w.overflow;
-  int* irregular = w.irregular;
-  (void)part_fused;
-  // Measured at 8x49x192x640 (pose_net-like rotations): two-pass 0.27 + 0.38 = 0.65 ms, fused 0.75 ms — sixteen waves
-  // meeting at a barrier 49 times cost more than the 770 MB the scratch tensor moves.  The fused kernel stays opt-in.
+  // Measured at 8x49x192x640 (pose_net-like rotations): two-pass 0.27 + 0.38 = 0.65 ms, both passes in one kernel with an
+  // LDS hand-over per plane 0.75 ms — sixteen waves meeting at a barrier 49 times cost more than the 770 MB the scratch
+  // tensor moves.  The whole batch goes in one launch per pass: 1 / 2 / 4 / 8 images per launch measured 2.16 / 1.83 /
+  // 1.42 / 0.99 ms — parallelism beats keeping the scratch in the memory-side cache.
   const int accumulate = (d->flags & PD_BWD_ACCUMULATE) ? 1 : 0;
   const bool render = (d->flags & PD_RENDER_PROB) != 0;
   const bool defer = (d->flags & PD_BWD_DEFER_GATHER) != 0;   // pass 2 is pd_uniform_gather_pair's
-#ifdef PD_EXPERIMENTS
-  const bool fused = getenv("PD_UNI_FUSED") != nullptr && !accumulate && !render && !defer;   // experiments build only
-#else
-  const bool fused = false;
-#endif
-#ifdef PD_EXPERIMENTS
-  const int tiles_x = ceil_div(d->W, kFuseC), ntiles = tiles_x * ceil_div(d->H, kFuseR);
-#else
-  const int ntiles = 0;
-#endif
-#ifdef PD_EXPERIMENTS
-  if (!rc && fused) {   // regular case: per-plane gradients handed over through LDS
-    dim3 grid(ntiles, d->B);
-    if (mix) uniform_bwd_fused_kernel<true><<<grid, kFuseThreads, 0, stream>>>(ak, o, prep, part_fused, tw, tiles_x, irregular);
-    else     uniform_bwd_fused_kernel<false><<<grid, kFuseThreads, 0, stream>>>(ak, o, prep, part_fused, tw, tiles_x, irregular);
-    rc = check_launch("uniform_bwd_fused_kernel");
-  }
-#endif
-  const int* run_flag = fused ? irregular : nullptr;   // the two-pass kernels return at once unless the fused one gave up
-  const int chunk = uniform_chunk(d);
-  if (defer && chunk < d->B) {
-    set_error("PD_BWD_DEFER_GATHER needs the whole batch's scratch (PD_UNI_CHUNK is set)");
-    return PD_ERR_UNSUPPORTED;
-  }
-  for (int b0 = 0; b0 < d->B && !rc; b0 += chunk) {
-    const int nb = (d->B - b0) < chunk ? (d->B - b0) : chunk;
-    dim3 grid(nblk, nb);
-    const int stiles_x = ceil_div(d->W, kStageW);
-    dim3 sgrid(stiles_x * ceil_div(d->H, kStageH), nb);
-    // pass 2 with the scratch staged through LDS unless the fused kernel is selected (its run_flag protocol belongs to
-    // the direct-gather kernel) or PD_IMPL_UNIFORM_DIRECT asks for the direct gather (cross-check)
-    const bool staged = !fused && d->impl != PD_IMPL_UNIFORM_DIRECT;
-    if (mix) {
-      if (render) uniform_bwd_pass1_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, o, b0, tmp, part_two, tw, run_flag);
-      else        uniform_bwd_pass1_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, o, b0, tmp, part_two, tw, run_flag);
-      if (defer) { /* the caller gathers: pd_uniform_gather_pair */ }
-      else {
-      if (staged) uniform_bwd_pass2_staged_kernel<true><<<sgrid, kStageThreads, 0, stream>>>(ak, b0, tmp, prep, o.g_logits, o.g_sigma, overflow, stiles_x, accumulate);
-      else uniform_bwd_pass2_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, b0, tmp, prep, o.g_logits, o.g_sigma, overflow, run_flag, accumulate);
-      uniform_bwd_pass2_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, b0, tmp, prep, o.g_logits, o.g_sigma, overflow, run_flag, accumulate);
-      }
-    } else {
-      if (render) uniform_bwd_pass1_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, o, b0, tmp, part_two, tw, run_flag);
-      else        uniform_bwd_pass1_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, o, b0, tmp, part_two, tw, run_flag);
-      if (defer) { /* the caller gathers: pd_uniform_gather_pair */ }
-      else {
-      if (staged) uniform_bwd_pass2_staged_kernel<false><<<sgrid, kStageThreads, 0, stream>>>(ak, b0, tmp, prep, o.g_logits, nullptr, overflow, stiles_x, accumulate);
-      else uniform_bwd_pass2_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, b0, tmp, prep, o.g_logits, nullptr, overflow, run_flag, accumulate);
-      uniform_bwd_pass2_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, b0, tmp, prep, o.g_logits, nullptr, overflow, run_flag, accumulate);
-      }
+  const dim3 grid(nblk, d->B);
+  const int stiles_x = ceil_div(d->W, kStageW);
+  const dim3 sgrid(stiles_x * ceil_div(d->H, kStageH), d->B);
+  // pass 2 with the scratch staged through LDS unless PD_IMPL_UNIFORM_DIRECT asks for the direct gather (cross-check)
+  const bool staged = d->impl != PD_IMPL_UNIFORM_DIRECT;
+  if (mix) {
+    if (render) uniform_bwd_pass1_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, tmp, part_two, tw);
+    else        uniform_bwd_pass1_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, tmp, part_two, tw);
+    if (defer) { /* the caller gathers: pd_uniform_gather_pair */ }
+    else {
+    if (staged) uniform_bwd_pass2_staged_kernel<true><<<sgrid, kStageThreads, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, o.g_sigma, overflow, stiles_x, accumulate);
+    else uniform_bwd_pass2_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, o.g_sigma, overflow, accumulate);
+    uniform_bwd_pass2_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, o.g_sigma, overflow, accumulate);
     }
-    rc = check_launch("uniform_bwd_pass kernels");
+  } else {
+    if (render) uniform_bwd_pass1_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, tmp, part_two, tw);
+    else        uniform_bwd_pass1_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, tmp, part_two, tw);
+    if (defer) { /* the caller gathers: pd_uniform_gather_pair */ }
+    else {
+    if (staged) uniform_bwd_pass2_staged_kernel<false><<<sgrid, kStageThreads, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, nullptr, overflow, stiles_x, accumulate);
+    else uniform_bwd_pass2_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, nullptr, overflow, accumulate);
+    uniform_bwd_pass2_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, nullptr, overflow, accumulate);
+    }
   }
+  rc = check_launch("uniform_bwd_pass kernels");
   if (rc || !o.g_plane) return rc;
-  uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(fused ? part_fused : nullptr, ntiles, part_two, nblk,
-                                                                     irregular, o.g_plane, kUniG * 9);
+  uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(part_two, nblk, o.g_plane, kUniG * 9);
   return check_launch("uniform_reduce_kernel");
 }
 
@@ -1069,8 +1018,8 @@ int uniform_gather_pair(const pd_sweep_desc* d, const float* plane_a, const floa
     a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W; a.flags = d->flags;
     a.plane = v ? plane_b : plane_a; a.inv_K3 = v ? inv_K3_b : inv_K3_a;
     const UniformWs& w = v ? wb : wa;
-    if (mix) uniform_bwd_pass2_kernel<true, true><<<grid, kBlock, 0, stream>>>(a, 0, w.tmp, w.prep, g_logits, g_sigma, w.overflow, nullptr, 1, kPairK);
-    else     uniform_bwd_pass2_kernel<false, true><<<grid, kBlock, 0, stream>>>(a, 0, w.tmp, w.prep, g_logits, nullptr, w.overflow, nullptr, 1, kPairK);
+    if (mix) uniform_bwd_pass2_kernel<true, true><<<grid, kBlock, 0, stream>>>(a, 0, w.tmp, w.prep, g_logits, g_sigma, w.overflow, 1, kPairK);
+    else     uniform_bwd_pass2_kernel<false, true><<<grid, kBlock, 0, stream>>>(a, 0, w.tmp, w.prep, g_logits, nullptr, w.overflow, 1, kPairK);
   }
   return check_launch("uniform_bwd_pass2_pair_kernel");
 }
@@ -1095,10 +1044,10 @@ int uniform_bwd_pair(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o
     SweepArgs ak = s;
     ak.padding_mask = nullptr;
     const dim3 grid(nblk, d->B);
-    if (mix) { if (render) uniform_bwd_pass1_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask, nullptr);
-               else        uniform_bwd_pass1_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask, nullptr); }
-    else     { if (render) uniform_bwd_pass1_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask, nullptr);
-               else        uniform_bwd_pass1_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask, nullptr); }
+    if (mix) { if (render) uniform_bwd_pass1_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask);
+               else        uniform_bwd_pass1_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask); }
+    else     { if (render) uniform_bwd_pass1_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask);
+               else        uniform_bwd_pass1_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask); }
     rc = check_launch("uniform_bwd_pass1_kernel");
   }
   if (rc) return rc;
@@ -1106,8 +1055,8 @@ int uniform_bwd_pair(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o
     rc = uniform_gather_pair(d, a.plane, a.inv_K3, workspace_a, b.plane, b.inv_K3, workspace_b, g_logits, g_sigma, stream);
     if (rc) return rc;
   }
-  if (oa.g_plane) uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(nullptr, 0, wa.part_two, nblk, wa.irregular, oa.g_plane, kUniG * 9);
-  if (ob.g_plane) uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(nullptr, 0, wb.part_two, nblk, wb.irregular, ob.g_plane, kUniG * 9);
+  if (oa.g_plane) uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(wa.part_two, nblk, oa.g_plane, kUniG * 9);
+  if (ob.g_plane) uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(wb.part_two, nblk, ob.g_plane, kUniG * 9);
   return check_launch("uniform_reduce_kernel");
 }
 

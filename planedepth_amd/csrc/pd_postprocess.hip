@@ -518,9 +518,6 @@ __global__ __launch_bounds__(kSegWaves* kWave) void warp_sum_seg_kernel(WarpArgs
 #ifndef PD_PP_CHAIN_G
 #define PD_PP_CHAIN_G 4
 #endif
-#ifndef PD_PP_CHAIN_SPLIT
-#define PD_PP_CHAIN_SPLIT 1   // 0: one wave per segment (A/B)
-#endif
 struct ChainArgs {
   WarpArgs w[2];          // first warp of chain 0 (image, plain) / chain 1 (mirrored image, PD_PP_FLIP_SRC)
   const float* disp2[2];  // the second warp's disparities [B,N] ([B,N,H] with rows2) and sign
@@ -821,7 +818,7 @@ static bool seg_applicable(const WarpArgs& a, int B, const float* out, int nmax)
 
 // the row kernels need 32-bit byte offsets inside a row and grid dimensions within the launch limits
 static bool rows_applicable(const WarpArgs& a, int B) {
-  return !switches().pp_rows_off && !a.dense && a.H <= 65535 && B <= 65535 && a.W <= (1 << 24);
+  return !a.dense && a.H <= 65535 && B <= 65535 && a.W <= (1 << 24);
 }
 
 static int warp_args(WarpArgs& a, int B, int N, int H, int W, float sign, int flags, const float* planes,
@@ -936,7 +933,7 @@ extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const floa
   int rc;
   // Row chains where the softmax of a row fits the CU's LDS: per-plane disparities, pixel pairs, N <= 64
   const size_t chain_lds = (size_t)N * (W + 4) * sizeof(float);
-  if (!(flags & PD_PP_DISP_DENSE) && !switches().pp_seg_off && !switches().pp_chain_off && (W % 2 == 0) && W <= 8 * kSegPix && N <= 64 && H <= 65535 &&
+  if (!(flags & PD_PP_DISP_DENSE) && !switches().pp_seg_off && (W % 2 == 0) && W <= 8 * kSegPix && N <= 64 && H <= 65535 &&
       chain_lds <= device_lds_bytes() && (long)2 * B * H < (1L << 31) && ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(disp_pp)) & 7) == 0) {
     ChainArgs c;
     const int rowsf = flags & PD_PP_DISP_ROWS;
@@ -953,7 +950,7 @@ extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const floa
     const size_t side_lds = chain_lds + (size_t)3 * nseg * kSegPix * sizeof(float2);
     const bool alias = side_lds > device_lds_bytes();   // the parts' statistics / partial sums inside the row buffer (needs 9 maps of
     const size_t split_lds = alias ? chain_lds : side_lds;   // nseg x 128 float2 there: N >= 18 at W = 640)
-    if (PD_PP_CHAIN_SPLIT && 3 * nseg <= 16 && (!alias || (size_t)9 * nseg * kSegPix * sizeof(float2) <= chain_lds)) {
+    if (3 * nseg <= 16 && (!alias || (size_t)9 * nseg * kSegPix * sizeof(float2) <= chain_lds)) {
       const dim3 block3(3 * nseg * kWave);
 #define PD_PP_SPLIT_(NPART, R2, AL)                                                                                                 \
       do {                                                                                                                        \

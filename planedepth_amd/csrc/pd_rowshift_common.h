@@ -1,5 +1,5 @@
 // Memory-access layer and row staging shared by the row-organised sweep kernels (pd_plane_sweep_rowshift.hip: one pixel
-// per lane; pd_plane_sweep_rowquad.hip: four pixels per lane): dispatch order, buffer resources per (plane, row), tap
+// per lane; the segment-stream forward and the row-stream backward): dispatch order, buffer resources per (plane, row), tap
 // loads, colour rows in LDS, per-plane shifts.
 #pragma once
 #include <stdlib.h>
@@ -10,16 +10,10 @@ namespace pd {
 
 constexpr int kMaxRowThreads = 1024;
 
-// Tuning knobs (scripts/gpu_variants.sh builds variants with -D...): plane-group size, one-group-ahead prefetch and
-// the occupancy the register allocator must leave room for (waves per SIMD), per kernel.
-#ifndef PD_VARIANT
-#define PD_VARIANT 0
-#endif
+// Tuning knobs (scripts/build_variants.sh builds variants with -D...): plane-group size and the occupancy the register
+// allocator must leave room for (waves per SIMD), per kernel.
 #ifndef PD_FWD_U
 #define PD_FWD_U 4
-#endif
-#ifndef PD_FWD_PF
-#define PD_FWD_PF 1
 #endif
 #ifndef PD_FWD_OCC
 #define PD_FWD_OCC 3  // (the single-row bodies alone fit 128 VGPRs = 4 waves per SIMD; the pair body needs ~147)
@@ -27,39 +21,15 @@ constexpr int kMaxRowThreads = 1024;
 #ifndef PD_BWD_U
 #define PD_BWD_U 2
 #endif
-#ifndef PD_PF_DEPTH
-#define PD_PF_DEPTH 2  // groups in the software pipeline (2: one group ahead, colour taps prefetched too; 3: two ahead)
-#endif
 #ifndef PD_STORE_AUX
 #define PD_STORE_AUX 0  // cache-policy bits of the gradient stores (experiments: 1 = sc0, 2 = nt, 16 = sc1)
 #endif
 #ifndef PD_LOAD_AUX
 #define PD_LOAD_AUX 0   // same for the tap loads
 #endif
-#ifndef PD_BWD_REVERSE
-#define PD_BWD_REVERSE 1  // the backward walks the rows in the opposite order of the forward: what the forward read last is
-#endif                    // what the backward reads first, and the other way round for the next step's forward — with the
-                          // gradient stores streaming past the caches (PD_STREAM_STORE_AUX = nt) the 256 MB memory-side cache
-                          // still holds those rows: step +2.4-2.8 % (forward 0.109 -> 0.105 ms, backward 0.178 -> 0.174), and
-                          // the same inside the DDP training step.  (Round 1, write-back stores: no gain — the dirty gradient
-                          // lines cycled the cache.  Forward bottom-up / backward top-down instead: +1 %, worse in the DDP step.)
-#ifndef PD_BWD_HANDOVER
-#define PD_BWD_HANDOVER 1  // lane 0 takes its left neighbour's hand-over out of LDS when it is already there
-#endif
-#ifndef PD_BWD_PF
-#define PD_BWD_PF 1
-#endif
-#ifndef PD_TC_PREFETCH
-#define PD_TC_PREFETCH 1  // colour taps (LDS) ride along with the prefetched plane group; 0: read when the group is reduced
-#endif
-#define PD_TC_IN_GROUP (PD_PF_DEPTH == 2 && PD_TC_PREFETCH)
-#ifndef PD_BWD_PF_DEPTH
-#define PD_BWD_PF_DEPTH PD_PF_DEPTH  // the backward's own pipeline depth (experiments)
-#endif
 #ifndef PD_BWD_OCC
 #define PD_BWD_OCC 3
 #endif
-constexpr int kVariant = PD_VARIANT;
 constexpr int kRowThreadsMax = 512;  // row workgroups use <= 8 waves (row_threads)
 
 // Row handled by workgroup r of an image.  The dispatcher deals consecutive workgroups to the 8 XCDs round-robin; the
@@ -73,24 +43,19 @@ constexpr int kRowThreadsMax = 512;  // row workgroups use <= 8 waves (row_threa
 //     neighbour's main row and mostly hits in that XCD's L2 (PMC at B = 8: backward HBM traffic 995 -> 909 MB).  Padding
 //     B to a multiple of 8 to get this for every batch size was measured and rejected: the padding workgroups all land
 //     on the same XCDs and leave them idle (B = 4: 4.1 k -> 2.4 k images/s).
-// Variant 8 = the image-major order.
 __device__ __forceinline__ int wg_image(int B, int H) {
-  if (kVariant & 8) return blockIdx.y;
   return (int)((blockIdx.y * gridDim.x + blockIdx.x) % (unsigned)B);
 }
 __device__ __forceinline__ int wg_rowid(int B, int H) {
-  if (kVariant & 8) return blockIdx.x;
   return (int)((blockIdx.y * gridDim.x + blockIdx.x) / (unsigned)B);
 }
-// PD_BWD_REVERSE: the backward walks the rows in the opposite order of the forward, so that what the forward touched last
-// is still in the memory-side cache when autograd starts the backward right after it (see the switch above for the numbers).
+// The backward walks the rows in the opposite order of the forward: what the forward read last is what the backward reads
+// first, and the other way round for the next step's forward — with the gradient stores streaming past the caches
+// (PD_STREAM_STORE_AUX = nt) the 256 MB memory-side cache still holds those rows: step +2.4-2.8 % (forward 0.109 -> 0.105 ms,
+// backward 0.178 -> 0.174), and the same inside the DDP training step.  (Round 1, write-back stores: no gain — the dirty
+// gradient lines cycled the cache.  Forward bottom-up / backward top-down instead: +1 %, worse in the DDP step.)
 __device__ __forceinline__ int bwd_rowid(int B, int H) {
-  const int r = wg_rowid(B, H);
-  return PD_BWD_REVERSE ? H - 1 - r : r;
-}
-__device__ __forceinline__ int block_row(int r, int H) {
-  if ((kVariant & 1) && (H % 8 == 0)) return (r & 7) * (H >> 3) + (r >> 3);
-  return r;
+  return H - 1 - wg_rowid(B, H);
 }
 
 // The one-row bodies drop the multiplications by the vertical weight: they run only for rows whose single live source

@@ -59,9 +59,7 @@ template <int NROWS, int U>
 struct PlaneGroup {
   ColTap ct[U];
   Taps<NROWS> tl[U], ts[U];
-#if PD_TC_IN_GROUP
   ColourTaps<NROWS> tc[U];  // LDS colour taps ride along with the global loads (their latency overlaps too)
-#endif
   float mval[U];
   float dist[U];  // PD_RENDER_PROB: the decoder's inter-plane distance at the TARGET pixel (trainer.py:587)
 };
@@ -76,29 +74,18 @@ __device__ __forceinline__ void group_issue(PlaneGroup<NROWS, U>& g, const Sweep
   for (int u = 0; u < U; ++u) {
     const int n = n0 + u;
     const float* pl = plane_ptr(a.logits + (long)b * a.N * HW, n, HW);  // workgroup-uniform
-    if (kAblate & 8) {  // diagnostics: no coordinate chain (integer shift, constant weights)
-      g.ct[u].x0 = x + (int)sdisp[n]; g.ct[u].w0 = 0.25f; g.ct[u].w1 = 0.75f;
-    } else {
-      g.ct[u] = make_col_tap((float)x + sdisp[n], Wm1, rcpWm1);
-    }
-#if PD_TC_IN_GROUP
-    if (!(kAblate & 2)) g.tc[u] = colour_taps_at<CL, NROWS>(lrgb, a.W, g.ct[u].x0);
-#endif
+    g.ct[u] = make_col_tap((float)x + sdisp[n], Wm1, rcpWm1);
+    g.tc[u] = colour_taps_at<CL, NROWS>(lrgb, a.W, g.ct[u].x0);
     if (RENDER)  // unshifted, coalesced: read where the pixel is, not where it samples
       g.dist[u] = (n < a.N - 1 && x < a.W) ? a.dists[((long)b * (a.N - 1) + n) * HW + (long)y * a.W + x] : 0.0f;
     g.mval[u] = 1.0f;
-    if (HASMASK && !(kAblate & 16))
+    if (HASMASK)
       g.mval[u] = buf_load(row_rsrc_uniform(plane_ptr(a.padding_mask + (long)b * a.N * HW + (long)y * a.W, n, HW), a.W), (unsigned)x << 2);
-    if (kAblate & 1) {  // diagnostics: no logit / sigma loads
-      g.tl[u].a0 = g.tl[u].a1 = g.tl[u].b0 = g.tl[u].b1 = g.ct[u].w0;
-      g.ts[u] = g.tl[u];
-    } else {
-      const TapPos tp = tap_pos(g.ct[u]);
-      g.tl[u] = load_taps<NROWS>(row_rsrc(pl + (long)row.yA * a.W, a.W), row_rsrc(pl + (long)row.yB * a.W, a.W), tp);
-      if (MIX) {
-        const float* ps = plane_ptr(a.sigma + (long)b * a.N * HW, n, HW);
-        g.ts[u] = load_taps<NROWS>(row_rsrc(ps + (long)row.yA * a.W, a.W), row_rsrc(ps + (long)row.yB * a.W, a.W), tp);
-      }
+    const TapPos tp = tap_pos(g.ct[u]);
+    g.tl[u] = load_taps<NROWS>(row_rsrc(pl + (long)row.yA * a.W, a.W), row_rsrc(pl + (long)row.yB * a.W, a.W), tp);
+    if (MIX) {
+      const float* ps = plane_ptr(a.sigma + (long)b * a.N * HW, n, HW);
+      g.ts[u] = load_taps<NROWS>(row_rsrc(ps + (long)row.yA * a.W, a.W), row_rsrc(ps + (long)row.yB * a.W, a.W), tp);
     }
   }
 }
@@ -108,14 +95,7 @@ __device__ __forceinline__ void fwd_compute(const PlaneGroup<NROWS, U>& g, const
                                             const char* __restrict__ lrgb, int b, int n0, int pix, int HW, float t0,
                                             float t1, float t2, float ea, bool automask, FwdAcc& acc, uint32_t& bits,
                                             float* __restrict__ stash, RenderState* rs = nullptr) {
-#if PD_TC_IN_GROUP
   const ColourTaps<NROWS>* tc = g.tc;
-#else
-  ColourTaps<NROWS> tc[U];  // all LDS reads of the group first, then the arithmetic
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (!(kAblate & 2)) tc[u] = colour_taps_at<CL, NROWS>(lrgb, a.W, g.ct[u].x0);
-#endif
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int n = n0 + u;
@@ -141,10 +121,8 @@ __device__ __forceinline__ void fwd_compute(const PlaneGroup<NROWS, U>& g, const
     const float l = tap_value<NROWS>(g.tl[u], we);
     const float s = MIX ? tap_value<NROWS>(g.ts[u], we) : 0.0f;
     float c0, c1, c2;
-    if (kAblate & 2) { c0 = w.a0; c1 = w.a1; c2 = l; }  // diagnostics: no colour taps
-    else colour_values<NROWS>(tc[u], w, c0, c1, c2);
-    if (kAblate & 4) { acc.Z += l; acc.S += s; acc.C0 += c0; acc.C1 += c1; acc.C2 += c2; acc.m = 0.0f; }  // no softmax/mixture math
-    else if (RENDER)  // alpha compositing front to back (trainer.py:584-591): the planes arrive in order
+    colour_values<NROWS>(tc[u], w, c0, c1, c2);
+    if (RENDER)  // alpha compositing front to back (trainer.py:584-591): the planes arrive in order
       mixture_accumulate<MIX>(acc, render_prob(*rs, render_alpha(l, g.dist[u], n == a.N - 1)), s, c0, c1, c2, t0, t1, t2,
                               ea, automask);
     else fwd_accumulate<MIX>(acc, l, s, c0, c1, c2, t0, t1, t2, ea, automask);
@@ -301,41 +279,24 @@ __device__ __forceinline__ float rowshift_fwd_rows(const SweepArgs& a, const Row
     FwdAcc acc;
     RenderState rs;
     uint32_t bits = 0;
-    // Groups of U planes through a software pipeline: while group i is reduced the loads of group i+1 (PD_PF_DEPTH 2;
-    // measured best) or of groups i+1 and i+2 (PD_PF_DEPTH 3; no faster, more registers) are in flight.
-    PlaneGroup<NROWS, U> g0, g1, g2;
+    // Groups of U planes through a software pipeline: while group i is reduced the loads of group i+1 are in flight
+    // (measured best; two groups ahead was no faster and took more registers).
+    PlaneGroup<NROWS, U> g0, g1;
     const int nfull = (n_hi - n_lo) / U;  // full groups
 #define PD_FISSUE(GR, I) group_issue<MIX, HASMASK, NROWS, U, RENDER, CL>(GR, a, row, lbytes, sdisp, b, y, n_lo + (I) * U, x, HW, Wm1, rcpWm1)
 #define PD_FCOMP(GR, I) fwd_compute<MIX, HASMASK, NROWS, U, RENDER, CL>(GR, a, row, lbytes, b, n_lo + (I) * U, pix, HW, t0, t1, t2, ea, automask, acc, bits, stash, &rs)
     int gi = 0;
-    if (PD_FWD_PF && PD_PF_DEPTH == 2) {
-      if (nfull > 0) PD_FISSUE(g0, 0);
-      for (; gi + 2 <= nfull; gi += 2) {
-        PD_FISSUE(g1, gi + 1);
-        PD_FCOMP(g0, gi);
-        // Unconditional on purpose: under an `if` the waitcnt pass has to assume the loads were NOT issued, counts too
-        // few operations in flight and makes every second group wait for the loads issued right before it (found in
-        // the ISA: vmcnt(7)..(0) instead of (15)..(8)).  On the last round this re-loads the final group; nobody reads it.
-        PD_FISSUE(g0, min(gi + 2, nfull - 1));
-        PD_FCOMP(g1, gi + 1);
-      }
-      if (gi < nfull) PD_FCOMP(g0, gi);
-    } else if (PD_FWD_PF) {
-      if (nfull > 0) PD_FISSUE(g0, 0);
-      if (nfull > 1) PD_FISSUE(g1, 1);
-      for (; gi + 3 <= nfull; gi += 3) {
-        PD_FISSUE(g2, gi + 2);
-        PD_FCOMP(g0, gi);
-        PD_FISSUE(g0, min(gi + 3, nfull - 1));
-        PD_FCOMP(g1, gi + 1);
-        PD_FISSUE(g1, min(gi + 4, nfull - 1));
-        PD_FCOMP(g2, gi + 2);
-      }
-      if (gi < nfull) PD_FCOMP(g0, gi);
-      if (gi + 1 < nfull) PD_FCOMP(g1, gi + 1);
-    } else {
-      for (; gi < nfull; ++gi) { PD_FISSUE(g0, gi); PD_FCOMP(g0, gi); }
+    if (nfull > 0) PD_FISSUE(g0, 0);
+    for (; gi + 2 <= nfull; gi += 2) {
+      PD_FISSUE(g1, gi + 1);
+      PD_FCOMP(g0, gi);
+      // Unconditional on purpose: under an `if` the waitcnt pass has to assume the loads were NOT issued, counts too
+      // few operations in flight and makes every second group wait for the loads issued right before it (found in
+      // the ISA: vmcnt(7)..(0) instead of (15)..(8)).  On the last round this re-loads the final group; nobody reads it.
+      PD_FISSUE(g0, min(gi + 2, nfull - 1));
+      PD_FCOMP(g1, gi + 1);
     }
+    if (gi < nfull) PD_FCOMP(g0, gi);
 #undef PD_FISSUE
 #undef PD_FCOMP
     for (int n = n_lo + nfull * U; n < n_hi; ++n) {  // remainder planes (only at the end of the plane axis)
@@ -421,7 +382,6 @@ __device__ __forceinline__ float rowpair_fwd_rows(const SweepArgs& a, int yL, in
                                                   const char* __restrict__ lbytes, const float* __restrict__ sdisp,
                                                   float* parts, float* __restrict__ rgb_rec,
                                                   float* __restrict__ ph_map, float* __restrict__ stash, int ppw = 2) {
-  static_assert(PD_TC_IN_GROUP, "the pair bodies use the two-group pipeline with colour taps in the group");
   constexpr int U = PD_FWD_U > 1 ? PD_FWD_U / 2 : 1;  // planes per group; each carries both rows
   constexpr int G = U;
   const int HW = a.H * a.W, N = a.N;

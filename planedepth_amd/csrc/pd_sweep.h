@@ -7,17 +7,6 @@
 
 namespace pd {
 
-// Diagnostics only: -DPD_ABLATE=<bits> builds a library that skips parts of the row-shift kernels (scripts/gpu_ablate.sh).
-#ifndef PD_ABLATE
-#define PD_ABLATE 0
-#endif
-#ifndef PD_DIAGNOSTICS   // timing-ablation / trace code (results wrong by design) compiles only into a library that says so: pd_build_flags()
-#if PD_ABLATE
-#error "timing-ablation / trace switches need -DPD_DIAGNOSTICS as well (pd_build_flags() then reports the build)"
-#endif
-#endif
-constexpr int kAblate = PD_ABLATE;
-
 constexpr int kStashBase = 4;  // lse, S, Mx, flags  (then ceil(N/32) mask words in disp mode)
 constexpr float kFastRowWeight = 1.52587890625e-05f;  // 2^-16: the threshold of PD_IMPL_FAST_ROWS (pd_rowshift_common.h: two_row_form)
 constexpr float kSigmaMin = 0.01f, kSigmaMax = 1.0f, kLogEps = 1e-7f, kZMin = 1e-7f;
@@ -283,19 +272,7 @@ bool rowstream_bwd_tail_applicable(const pd_sweep_desc* d, const SweepArgs& a);
 int rowstream_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, hipStream_t stream);
 size_t rowstream_bwd_workspace_floats(const pd_sweep_desc* d);
 
-#ifdef PD_EXPERIMENTS
-// Four-pixels-per-lane row kernels (pd_plane_sweep_rowquad.hip): same contract as the row-shift ones, wide memory accesses.
-bool rowquad_applicable(const pd_sweep_desc* d, bool dense_mask);
-int rowquad_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, float* ph_map, float* stash,
-                hipStream_t stream);
-int rowquad_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, hipStream_t stream);
-size_t rowquad_bwd_workspace_floats(const pd_sweep_desc* d);
 
-// Scatter-free general backward (pd_plane_sweep_tile.hip): homography mode, source tiles owned by workgroups.
-bool tile_bwd_applicable(const pd_sweep_desc* d);
-size_t tile_bwd_workspace_floats(const pd_sweep_desc* d);
-int tile_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, float* workspace, hipStream_t stream);
-#endif  // PD_EXPERIMENTS
 // Plane-uniform homography (pd_plane_sweep_uniform.hip, PD_HOMO_UNIFORM)
 int uniform_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, float* ph_map, float* stash, hipStream_t stream);
 int uniform_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, float* workspace, hipStream_t stream);

@@ -34,7 +34,6 @@ from .postprocess import (  # noqa: F401
 from .geometry import (  # noqa: F401
     _Backproject, backproject_depth, _Project3D, project_3d, _HomographyGrid, homography_grid,
     _GridSample, grid_sample)
-from ._state import _env_int  # noqa: F401
 
 
 class _OpsModule(types.ModuleType):

@@ -9,7 +9,6 @@ import os
 
 from . import _capi as C
 from . import _state as S
-from ._state import _env_int
 from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, _plane_grad_buffer
 
 
@@ -47,11 +46,8 @@ def _sweep_forward(src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_ma
     k = lib.pd_sweep_stash_floats(ctypes.byref(d)) // (H * W)
     rgb_rec = torch.empty(B, 3, H, W, device=logits.device, dtype=torch.float32)
     ph_map = torch.empty(B, 1, H, W, device=logits.device, dtype=torch.float32)
-    if S.ZERO_POOL:
-        ph_mean = _zero_scalar(logits.device)   # a pre-zeroed slot: the entry point then launches no memset (PD_PH_MEAN_ZEROED)
-        d.flags |= C.PD_PH_MEAN_ZEROED
-    else:
-        ph_mean = torch.empty(1, device=logits.device, dtype=torch.float32)
+    ph_mean = _zero_scalar(logits.device)   # a pre-zeroed slot: the entry point then launches no memset (PD_PH_MEAN_ZEROED)
+    d.flags |= C.PD_PH_MEAN_ZEROED
     stash = torch.empty(B, k, H, W, device=logits.device, dtype=torch.float32)
     with C.on_device(logits.device), _timed("fwd"):
         rc = lib.pd_plane_sweep_fwd(ctypes.byref(d), C.ptr(src), C.ptr(tgt), C.ptr(logits), C.ptr(sigma),
@@ -79,8 +75,7 @@ def _sweep_forward_pair(src, logits, sigma, side_a, side_b):
     src, logits, sigma = _contig(src), _contig(logits), _contig(sigma)
     d = _desc(B, N, H, W, mode, flags, sign)
     k = lib.pd_sweep_stash_floats(ctypes.byref(d)) // (H * W)
-    if S.ZERO_POOL:
-        d.flags |= C.PD_PH_MEAN_ZEROED
+    d.flags |= C.PD_PH_MEAN_ZEROED
     views, results = [], []
     for tgt, plane, plane_aux, inv_K3, padding_mask, dists, _, _, _ in (side_a, side_b):
         C.require_gpu_tensor("tgt", tgt, (B, 3, H, W))
@@ -96,7 +91,7 @@ def _sweep_forward_pair(src, logits, sigma, side_a, side_b):
         tgt, plane, plane_aux, inv_K3, padding_mask, dists = map(_contig, (tgt, plane, plane_aux, inv_K3, padding_mask, dists))
         rgb_rec = torch.empty(B, 3, H, W, device=logits.device, dtype=torch.float32)
         ph_map = torch.empty(B, 1, H, W, device=logits.device, dtype=torch.float32)
-        ph_mean = _zero_scalar(logits.device) if S.ZERO_POOL else torch.empty(1, device=logits.device, dtype=torch.float32)
+        ph_mean = _zero_scalar(logits.device)
         stash = torch.empty(B, k, H, W, device=logits.device, dtype=torch.float32)
         views.append(C.sweep_view(tgt=tgt, plane=plane, plane_aux=plane_aux, inv_K3=inv_K3, dists=dists, rgb_rec=rgb_rec,
                                   ph_map=ph_map, ph_mean=ph_mean, stash=stash))
@@ -391,8 +386,7 @@ class _MultiPlaneSweep(torch.autograd.Function):
 
         def pairable(v):   # plane-uniform views with the same kernel configuration gather together (pd_uniform_gather_pair)
             mode, flags, sign = ctx.cfgs[v[0]]
-            # (PD_UNI_CHUNK, the library's chunked plane-uniform passes, does not serve the deferred gather: sequential views then)
-            return (S.PAIR_GATHER and not _env_int("PD_UNI_CHUNK") and mode == C.PD_WARP_HOMOGRAPHY and
+            return (S.PAIR_GATHER and mode == C.PD_WARP_HOMOGRAPHY and
                     bool(flags & C.PD_HOMO_UNIFORM) and (need_logits or need_sigma))
         k = 0
         while k < len(views):

@@ -26,7 +26,7 @@ def elementwise(a, b, floor_frac=1e-3):
 
 for tag in TRAINER_MONO:
     z, meta = load_trainer_fixture(tag)
-    for impl in (None, C.PD_IMPL_TILE):
+    for impl in (None, C.PD_IMPL_GENERAL):
         got = run_product_trainer(z, meta, impl=impl)
         print(tag, "impl", impl, {k: "%.1e" % rel_err(v if k != "g_disp_layered" else v.sum(-1),
                                                       z[k] if k != "g_disp_layered" else z[k].sum(-1))

@@ -3,9 +3,9 @@
 side by side and runs the same forward -> backward sequence (the caches are then in the state the training step leaves
 them in), interleaved round by round; HIP events on the launch stream around each C-ABI call.
 
-    python scripts/diag_kernel_ab.py [--impl 0|2] [--rounds 5] [--iters 40] [--batch 8 ...] product occ4 abl16 product@7 ...
+    python scripts/diag_kernel_ab.py [--impl 0|2] [--rounds 5] [--iters 40] [--batch 8 ...] product occ4 d2 product@4 ...
 
-`name@impl` runs that library under another pd_sweep_impl than --impl (e.g. product@7 = PD_IMPL_ROW_SINGLES next to product);
+`name@impl` runs that library under another pd_sweep_impl than --impl (e.g. product@4 = PD_IMPL_ROWS1 next to product);
 --check compares every arm's outputs with the first arm's bit for bit (max |difference| per tensor).
 """
 import argparse

@@ -1,5 +1,5 @@
 # Round 6: A/B of library variants / impls on the headline kernels in one process (scripts/diag_kernel_ab.py).
-#   ARMS="product product@7 var1 ..." (name@impl: that library under another pd_sweep_impl; variants built by scripts/build_variants.sh)
+#   ARMS="product product@4 var1 ..." (name@impl: that library under another pd_sweep_impl; variants built by scripts/build_variants.sh)
 #   SHAPES="headline b12 hr n63"   CHECK=1 (bitwise comparison of every arm with the first)   TEST_K="pytest -k expression" (parity subset)
 mkdir -p gpurun_out/r6
 O=gpurun_out/r6/${TAG:-ab}.txt; : > $O

@@ -241,7 +241,7 @@ def _stream_tol(W):
     (70, 5, 5, "l", True, dict(disp_min=0.3, disp_max=40.0)),
     (2, 3, 2, "r", True, dict(disp_min=0.2, disp_max=1.5)),
     (257, 5, 5, "l", True, dict(disp_min=0.5, disp_max=80.0)),
-    # the shapes the row-quad experiments were checked on: whole and ragged segments, both signs, integer and
+    # the shapes the (since removed) four-pixels-per-lane row kernels were checked on: whole and ragged segments, both signs, integer and
     # almost-integer shifts, shifts beyond the row
     (640, 12, 9, "r", True, dict(disp_min=2.0, disp_max=300.0)),
     (70, 11, 10, "r", True, dict(special_disp=[0.0, 1.0, 2.0, 1.9999999, 3.0000002, 7.5, 68.9999, 69.0, 75.0, 1e6], disp_min=0.5, disp_max=9.0)),
@@ -377,7 +377,7 @@ def test_segment_stream_forward_equals_the_plane_group_forward(B, N, H, W, sign,
 def test_fixed_reference_softmax_falls_back_on_extreme_logits(kind):
     """The segment-stream forward's softmax runs against a FIXED per-pixel reference (the first plane's scaled logit) and
     re-does a wave's planes with the rescaling accumulator when a term went beyond 2^90 (pd_plane_sweep_fwdstream.hip:
-    PD_FS_FIXREF).  Logit sets that trip it — the first plane 300 below the rest; one plane 300 above — and a NaN logit
+    kFixRefLimit).  Logit sets that trip it — the first plane 300 below the rest; one plane 300 above — and a NaN logit
     (which must propagate like the reference's softmax, not trip anything) against the oracle and the plane-group forward."""
     from gpu_cases import run_product
     from planedepth_amd import _capi as C
@@ -2889,10 +2889,8 @@ def test_plane_uniform_homography_kernels_equal_the_general_ones(B, N, H, W, mix
     from planedepth_amd import ops
     from planedepth_amd.synthetic import intrinsics
     # backward variants: pass 2 with the scratch staged through LDS (default), the direct-gather pass 2
-    # (PD_IMPL_UNIFORM_DIRECT); tests/experiments runs the same body with the one-kernel form (PD_UNI_FUSED)
+    # (PD_IMPL_UNIFORM_DIRECT)
     from planedepth_amd import _capi as C
-    if bwd != "fused":
-        monkeypatch.delenv("PD_UNI_FUSED", raising=False)
     monkeypatch.setattr(ops, "SWEEP_IMPL", C.PD_IMPL_UNIFORM_DIRECT if bwd == "direct" else C.PD_IMPL_AUTO)
     g = torch.Generator().manual_seed(900 + W + N)
     dev = "cuda"
