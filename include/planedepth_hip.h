@@ -9,7 +9,8 @@
  *
  * Conventions
  *   - all tensors are fp32, contiguous NCHW device pointers owned by the caller
- *     (outputs are caller-allocated; nothing is allocated, freed or synchronised here);
+ *     (outputs are caller-allocated; nothing is allocated, freed or synchronised here) — except, under PD_LOGITS_BF16,
+ *     the sweep's logits / sigma / g_logits / g_sigma, which then hold bf16 bit patterns (see the flag);
  *   - `stream` is a hipStream_t (0 = the null stream); launches are asynchronous;
  *   - every function returns PD_OK (0) or a PD_ERR_* code; pd_last_error() returns a
  *     thread-local human-readable message for the last non-zero return on this thread;
@@ -87,7 +88,16 @@ enum pd_sweep_flags {
                          pd_sweep_bwd_plane_adds(d) == 1 (the row-stream backward) every row workgroup then ADDS its share with
                          atomics and the entry point launches no reduction kernel of its own (4-5 us + a launch gap per call next
                          to a 0.18 ms kernel; the sum's order, hence its last bits, varies from run to run); elsewhere the kernels
-                         overwrite `g_plane` as always — the promise is harmless there */
+                         overwrite `g_plane` as always — the promise is harmless there */,
+  PD_LOGITS_BF16 = 2048 /* pd_plane_sweep_fwd / _bwd: `logits`, `sigma`, `g_logits` and `g_sigma` hold bf16 (torch.bfloat16) bit
+                         patterns, 4-byte aligned; everything else stays fp32 (src, tgt, plane, padding mask, dists, rgb_rec,
+                         ph_map, ph_mean, stash, workspace, g_plane).  The arithmetic is the fp32 kernels': a bf16 element widens
+                         exactly on load, and every gradient element is rounded to bf16 ONCE (round to nearest even) from the
+                         fp32 value that holds all of its contributions — no bf16 read-modify-write, no bf16 atomics — so the
+                         gradients equal the fp32 route's on the widened inputs rounded once.  Served where
+                         pd_sweep_native_bf16(d) == 1 (the segment-stream forward and the row-stream backward); elsewhere, with
+                         a per-pixel padding mask, with PD_BWD_ACCUMULATE / PD_BWD_DEFER_GATHER and in pd_plane_sweep_bwd_tail
+                         and the pair entry points the call returns PD_ERR_UNSUPPORTED naming the flag */
 };
 
 enum pd_padding_mode { PD_PAD_ZEROS = 0, PD_PAD_BORDER = 1 };
@@ -156,6 +166,10 @@ int pd_sweep_bwd_plane_adds(const pd_sweep_desc* d);
 int pd_sweep_bwd_accumulates(const pd_sweep_desc* d);
 /* 1 if this descriptor is served by the row-shift kernels (PD_WARP_DISP, scalar or per-row disparities), else 0. */
 int pd_sweep_uses_rowshift(const pd_sweep_desc* d);
+/* 1 if PD_LOGITS_BF16 is served for this descriptor (the flag itself need not be set in d->flags), else 0: PD_WARP_DISP with
+ * per-plane disparities or PD_DISP_ROWS (with or without PD_MASK_ROWS), mixture or L1, with or without automask, impl AUTO /
+ * FAST_ROWS / EXACT_ROWS, no PD_RENDER_PROB, even W, and a row whose LDS fits.  Needs no GPU. */
+int pd_sweep_native_bf16(const pd_sweep_desc* d);
 
 /* Floats per image the forward pass stashes for the backward pass (softmax statistics + mask bits). */
 size_t pd_sweep_stash_floats(const pd_sweep_desc* d);

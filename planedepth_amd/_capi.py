@@ -17,6 +17,7 @@ PD_BWD_ACCUMULATE = 128
 PD_BWD_DEFER_GATHER = 256
 PD_PH_MEAN_ZEROED = 512
 PD_BWD_PLANE_ZEROED = 1024
+PD_LOGITS_BF16 = 2048   # logits / sigma / g_logits / g_sigma hold bf16 (pd_sweep_native_bf16)
 PD_PAD_ZEROS, PD_PAD_BORDER = 0, 1
 PD_TAIL_MIXTURE, PD_TAIL_DISP_DENSE = 1, 2
 PD_PP_DISP_DENSE, PD_PP_FLIP_SRC, PD_PP_DISP_ROWS = 1, 2, 4
@@ -59,6 +60,7 @@ SIGNATURES = {
     "pd_last_error": (ctypes.c_char_p, []),
     "pd_source_hash": (ctypes.c_char_p, []),
     "pd_sweep_uses_rowshift": (_I, [_D]),
+    "pd_sweep_native_bf16": (_I, [_D]),
     "pd_sweep_auto_row_eps": (_F, []),
     "pd_sweep_bwd_accumulates": (_I, [_D]),
     "pd_sweep_bwd_plane_adds": (_I, [_D]),

@@ -385,6 +385,18 @@ static int validate(const pd_sweep_desc* d, const float* src, const float* logit
              d->H, d->W);
   PD_REQUIRE(d->B <= 65535, "B=%d exceeds the grid.y limit", d->B);
   PD_REQUIRE(d->mode == PD_WARP_DISP || d->mode == PD_WARP_HOMOGRAPHY, "unknown warp mode %d", d->mode);
+  if (d->flags & PD_LOGITS_BF16) {   // (before the pointer checks: a probe with NULL tensors launches nothing either way)
+    const char* why = !pd_sweep_native_bf16(d) ? "not served for this descriptor (pd_sweep_native_bf16)"
+                      : (padding_mask && !(d->flags & PD_MASK_ROWS)) ? "no per-pixel padding mask"
+                      : (d->flags & (PD_BWD_ACCUMULATE | PD_BWD_DEFER_GATHER)) ? "no PD_BWD_ACCUMULATE / PD_BWD_DEFER_GATHER"
+                      : nullptr;
+    if (why) {
+      set_error("PD_LOGITS_BF16: %s", why);
+      return PD_ERR_UNSUPPORTED;
+    }
+    PD_REQUIRE(!((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(sigma)) & 3),
+               "PD_LOGITS_BF16: logits / sigma must be 4-byte aligned");
+  }
   PD_REQUIRE(src && logits && plane, "src/logits/plane must not be NULL");
   PD_REQUIRE(!(d->flags & PD_MIXTURE) || sigma, "PD_MIXTURE needs sigma");
   if (d->mode == PD_WARP_HOMOGRAPHY) {
@@ -461,6 +473,17 @@ extern "C" int pd_sweep_uses_rowshift(const pd_sweep_desc* d) {
   return (d && wants_rowshift(d) && rowshift_applicable(d)) ? 1 : 0;
 }
 
+extern "C" int pd_sweep_native_bf16(const pd_sweep_desc* d) {
+  if (!d || d->mode != PD_WARP_DISP || (d->flags & (PD_RENDER_PROB | PD_DISP_DENSE | PD_HOMO_UNIFORM))) return 0;
+  if (!(d->impl == PD_IMPL_AUTO || d->impl == PD_IMPL_FAST_ROWS || d->impl == PD_IMPL_EXACT_ROWS)) return 0;
+  if (d->B <= 0 || d->N <= 0 || d->H <= 1 || d->W <= 1 || d->W % 2 != 0 || !rowshift_applicable(d)) return 0;
+  pd_sweep_desc q = *d;
+  q.flags |= PD_LOGITS_BF16;   // (the row-stream backward's LDS grows under the flag)
+  SweepArgs probe{};
+  probe.has_mask = 0;
+  return (fwdstream_applicable(&q, probe) && rowstream_bwd_applicable(&q, probe)) ? 1 : 0;
+}
+
 extern "C" int pd_sweep_bwd_accumulates(const pd_sweep_desc* d) {
   if (!d) return 0;
   if (wants_rowshift(d) && rowshift_applicable(d)) return 0;   // owner-computes ring stores: no read-modify-write form
@@ -519,6 +542,7 @@ extern "C" int pd_plane_sweep_fwd(const pd_sweep_desc* d, const float* src, cons
     // default for the headline shape: one wave per 128-pixel segment streams over the planes (pd_plane_sweep_fwdstream.hip);
     // PD_IMPL_ROWS1 keeps the plane-group row-shift forward (cross-check, A/B)
     if (d->impl != PD_IMPL_ROWS1 && fwdstream_applicable(d, a)) return fwdstream_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
+    PD_REQUIRE(!(d->flags & PD_LOGITS_BF16), "PD_LOGITS_BF16: the segment-stream forward does not apply");   // (validate() refused it)
     return rowshift_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
   }
   if (d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM))
@@ -548,6 +572,14 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   const bool mix = (d->flags & PD_MIXTURE) != 0;
   const bool accumulate = (d->flags & PD_BWD_ACCUMULATE) != 0;
   PD_REQUIRE(!accumulate || pd_sweep_bwd_accumulates(d), "PD_BWD_ACCUMULATE is not served for this descriptor (pd_sweep_bwd_accumulates)");
+  if (d->flags & PD_LOGITS_BF16) {
+    if (tail) {
+      set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_bwd_tail");
+      return PD_ERR_UNSUPPORTED;
+    }
+    PD_REQUIRE(!((reinterpret_cast<uintptr_t>(g_logits) | reinterpret_cast<uintptr_t>(g_sigma)) & 3),
+               "PD_LOGITS_BF16: g_logits / g_sigma must be 4-byte aligned");
+  }
   SweepArgs ak = make_args(d, src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists);
   BwdOut o;
   o.g_logits = g_logits; o.g_sigma = mix ? g_sigma : nullptr; o.g_plane = g_plane; o.partials = workspace;
@@ -569,6 +601,7 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
       return rowstream_bwd(d, ak, o, stream);
     }
     if (d->impl != PD_IMPL_ROWS1 && rowstream_bwd_applicable(d, ak)) return rowstream_bwd(d, ak, o, stream);
+    PD_REQUIRE(!(d->flags & PD_LOGITS_BF16), "PD_LOGITS_BF16: the row-stream backward does not apply");   // (validate() refused it)
     return rowshift_bwd(d, ak, o, stream);
   }
   if (tail) {
@@ -650,6 +683,10 @@ extern "C" int pd_plane_sweep_bwd_tail(const pd_sweep_desc* d, const float* src,
                                        const float* raw_sigma, const float* tail_stash, const float* disp,
                                        const float* g_disp, const float* g_depth, float* g_raw_logits,
                                        float* g_raw_sigma, float* g_plane, float* workspace, pd_stream_t stream) {
+  if (d && (d->flags & PD_LOGITS_BF16)) {
+    set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_bwd_tail");
+    return PD_ERR_UNSUPPORTED;
+  }
   PD_REQUIRE(raw_sigma && tail_stash && disp, "raw_sigma / tail_stash / disp must not be NULL");
   const TailIn t = {raw_sigma, tail_stash, disp, g_disp, g_depth};
   return sweep_bwd_impl(d, src, tgt, logits, sigma, plane, nullptr, nullptr, nullptr, nullptr, rgb_rec, stash, g_rgb_rec,
@@ -660,6 +697,10 @@ extern "C" int pd_uniform_gather_pair(const pd_sweep_desc* d, const float* plane
                                       const float* plane_b, const float* inv_K3_b, float* workspace_b, float* g_logits,
                                       float* g_sigma, pd_stream_t stream) {
   PD_REQUIRE(d != nullptr, "desc is NULL");
+  if (d->flags & PD_LOGITS_BF16) {
+    set_error("PD_LOGITS_BF16: not served by pd_uniform_gather_pair");
+    return PD_ERR_UNSUPPORTED;
+  }
   PD_REQUIRE(d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM) && (d->flags & PD_BWD_DEFER_GATHER),
              "pd_uniform_gather_pair takes the descriptor of two PD_HOMO_UNIFORM | PD_BWD_DEFER_GATHER backward calls");
   PD_REQUIRE(d->B > 0 && d->B <= 65535 && d->N > 0 && d->H > 1 && d->W > 1, "bad shape");
@@ -672,6 +713,10 @@ extern "C" int pd_uniform_gather_pair(const pd_sweep_desc* d, const float* plane
 static int validate_pair(const pd_sweep_desc* d, const float* src, const float* logits, const float* sigma,
                          const pd_sweep_view* va, const pd_sweep_view* vb) {
   PD_REQUIRE(d && va && vb, "desc / view is NULL");
+  if (d->flags & PD_LOGITS_BF16) {
+    set_error("PD_LOGITS_BF16: not served by the pair entry points");
+    return PD_ERR_UNSUPPORTED;
+  }
   PD_REQUIRE(d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM), "the pair entry points serve PD_HOMO_UNIFORM views");
   for (const pd_sweep_view* v : {va, vb}) {
     const int rc = validate(d, src, logits, sigma, v->plane, v->plane_aux, v->inv_K3, v->padding_mask);
@@ -738,6 +783,10 @@ extern "C" int pd_plane_sweep_layers(const pd_sweep_desc* d, const float* src, c
   if (rc) return rc;
   PD_REQUIRE(!(d->flags & PD_RENDER_PROB) || (dists && d->N >= 2), "PD_RENDER_PROB needs dists [B,N-1,H,W] and N >= 2");
   PD_REQUIRE(!(d->flags & PD_HOMO_UNIFORM), "pd_plane_sweep_layers takes one homography per plane (expand the matrix)");
+  if (d->flags & PD_LOGITS_BF16) {
+    set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_layers");
+    return PD_ERR_UNSUPPORTED;
+  }
   SweepArgs a = make_args(d, src, nullptr, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists);
   LayersOut o{rgb_rec_layered, logit_rec, probability_rec, sigma_rec, pi_rec};
   dim3 grid(ceil_div(d->H * d->W, kBlock), d->B);

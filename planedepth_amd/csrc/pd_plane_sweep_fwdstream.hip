@@ -64,16 +64,46 @@ constexpr int kFsGuard = 4;            // zero cells on each side of the colour 
 constexpr int kFsThreadsMax = 1024;    // 16 waves: rows up to 2048 pixels
 
 typedef float v3f __attribute__((ext_vector_type(3)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ v3f fs_load3(Rsrc r, unsigned byte_off) {
   return __builtin_bit_cast(v3f, __builtin_amdgcn_raw_buffer_load_b96(r, (int)byte_off, 0, 0));
 }
 
-template <int NROWS>
+template <class T, int NROWS>
 struct FsTaps {   // the taps of one plane for the lane's two pixels: L[c .. c+2] per live source row
   float l[NROWS][3], s[NROWS][3];
   float dist[2];  // PD_RENDER_PROB: the decoder's inter-plane distances at the two TARGET pixels (trainer.py:587)
 };
+// bf16 storage: the raw 8 bytes of ONE load per tensor and row, four elements from the 4-byte-aligned column c or c - 1
+// (the parity of c = xt + k is the parity of k: wave-uniform); the three taps are picked and widened when the plane is reduced
+// (fs_taps), so the ring holds 2 VGPRs per tensor and row instead of 3.
+template <int NROWS>
+struct FsTaps<Bf16, NROWS> {
+  unsigned l[NROWS][2], s[NROWS][2];
+  float dist[2];
+};
+// Byte offset of the lane's tap load for source column c = xt0 + k (even xt0): fp32 at c, bf16 at the even column c - (k & 1).
+template <class T> __device__ __forceinline__ unsigned fs_tap_off(int c, int k) {
+  return sizeof(T) == 4 ? (unsigned)c << 2 : (unsigned)(c - (k & 1)) << 1;
+}
+template <int NROWS>
+__device__ __forceinline__ void fs_taps(const FsTaps<float, NROWS>& g, int, float (&l)[NROWS][3], float (&s)[NROWS][3]) {
+#pragma unroll
+  for (int r = 0; r < NROWS; ++r)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { l[r][i] = g.l[r][i]; s[r][i] = g.s[r][i]; }
+}
+__device__ __forceinline__ void bf16_taps3(const unsigned (&w)[2], bool odd, float (&t)[3]) {   // elements (0,1,2) or (1,2,3)
+  t[0] = odd ? bf16_hi(w[0]) : bf16_lo(w[0]);
+  t[1] = odd ? bf16_lo(w[1]) : bf16_hi(w[0]);
+  t[2] = odd ? bf16_hi(w[1]) : bf16_lo(w[1]);
+}
+template <int NROWS>
+__device__ __forceinline__ void fs_taps(const FsTaps<Bf16, NROWS>& g, int k, float (&l)[NROWS][3], float (&s)[NROWS][3]) {
+#pragma unroll
+  for (int r = 0; r < NROWS; ++r) { bf16_taps3(g.l[r], k & 1, l[r]); bf16_taps3(g.s[r], k & 1, s[r]); }
+}
 
 struct FsRow {    // workgroup-uniform
   int b, y, yA, yB;
@@ -81,7 +111,22 @@ struct FsRow {    // workgroup-uniform
 };
 
 template <bool MIX, int NROWS>
-__device__ __forceinline__ void fs_issue(FsTaps<NROWS>& g, const SweepArgs& a, const FsRow& r, int n, unsigned off, int HW) {
+__device__ __forceinline__ void fs_issue(FsTaps<Bf16, NROWS>& g, const SweepArgs& a, const FsRow& r, int n, unsigned off, int HW) {
+  const Bf16* pl = plane_ptr_t(elems<Bf16>(a.logits) + (long)r.b * a.N * HW, n, HW);
+  auto ld = [&](const Bf16* row, unsigned (&w)[2]) {
+    const v2u v = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(row_rsrc_t(row, a.W), (int)off, 0, 0));
+    w[0] = v.x; w[1] = v.y;
+  };
+  ld(pl + (long)r.yA * a.W, g.l[0]);
+  if (NROWS == 2) ld(pl + (long)r.yB * a.W, g.l[NROWS - 1]);
+  if (MIX) {
+    const Bf16* ps = plane_ptr_t(elems<Bf16>(a.sigma) + (long)r.b * a.N * HW, n, HW);
+    ld(ps + (long)r.yA * a.W, g.s[0]);
+    if (NROWS == 2) ld(ps + (long)r.yB * a.W, g.s[NROWS - 1]);
+  }
+}
+template <bool MIX, int NROWS>
+__device__ __forceinline__ void fs_issue(FsTaps<float, NROWS>& g, const SweepArgs& a, const FsRow& r, int n, unsigned off, int HW) {
   const float* pl = plane_ptr(a.logits + (long)r.b * a.N * HW, n, HW);
   const v3f la = fs_load3(row_rsrc(pl + (long)r.yA * a.W, a.W), off);
   g.l[0][0] = la.x; g.l[0][1] = la.y; g.l[0][2] = la.z;
@@ -111,15 +156,18 @@ __device__ __forceinline__ void fs_accumulate(FwdAcc& acc, RenderState& rs, floa
   else fwd_accumulate<MIX>(acc, l, s, c0, c1, c2, t0, t1, t2, ea, automask);
 }
 
-template <bool MIX, int NROWS, bool RENDER>
+template <class T, bool MIX, int NROWS, bool RENDER>
 __device__ __forceinline__ void fs_general_plane(const SweepArgs& a, const FsRow& r, const float4* __restrict__ col, int n,
                                                  float sd, float xt0f, int HW, float Wm1, float rcpWm1, const float* t,
                                                  const float* ea, bool automask, FwdAcc* acc, RenderState* rs,
                                                  const float* dist) {
-  const float* pl = plane_ptr(a.logits + (long)r.b * a.N * HW, n, HW);
-  const float* ps = MIX ? plane_ptr(a.sigma + (long)r.b * a.N * HW, n, HW) : pl;
-  const Rsrc lA = row_rsrc(pl + (long)r.yA * a.W, a.W), lB = row_rsrc(pl + (long)r.yB * a.W, a.W);
-  const Rsrc sA = row_rsrc(ps + (long)r.yA * a.W, a.W), sB = row_rsrc(ps + (long)r.yB * a.W, a.W);
+  // (bf16: 16-bit loads, the same range-checked columns)
+  const T* pl = plane_ptr_t(elems<T>(a.logits) + (long)r.b * a.N * HW, n, HW);
+  const T* ps = MIX ? plane_ptr_t(elems<T>(a.sigma) + (long)r.b * a.N * HW, n, HW) : pl;
+  const Rsrc lA = row_rsrc_t(pl + (long)r.yA * a.W, a.W), lB = row_rsrc_t(pl + (long)r.yB * a.W, a.W);
+  const Rsrc sA = row_rsrc_t(ps + (long)r.yA * a.W, a.W), sB = row_rsrc_t(ps + (long)r.yB * a.W, a.W);
+  T* const et = nullptr;
+  auto ld_el = [&](Rsrc rs, unsigned byte_off) { return buf_load_elem(rs, (int)(byte_off >> 2), et); };
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const ColTap ct = make_col_tap(xt0f + (float)i + sd, Wm1, rcpWm1);
@@ -129,13 +177,13 @@ __device__ __forceinline__ void fs_general_plane(const SweepArgs& a, const FsRow
     const unsigned o0 = (unsigned)max(ct.x0, 0) << 2, o1 = (unsigned)max(ct.x0 + 1, 0) << 2;
     const float w0 = (ct.x0 >= 0) ? ct.w0 : 0.0f, w1 = (ct.x0 + 1 >= 0) ? ct.w1 : 0.0f;
     const float wa0 = (NROWS == 1) ? w0 : w0 * r.wA, wa1 = (NROWS == 1) ? w1 : w1 * r.wA;
-    float l = buf_load(lA, o0) * wa0 + buf_load(lA, o1) * wa1;
+    float l = ld_el(lA, o0) * wa0 + ld_el(lA, o1) * wa1;
     float s = 0.0f;
-    if (MIX) s = buf_load(sA, o0) * wa0 + buf_load(sA, o1) * wa1;
+    if (MIX) s = ld_el(sA, o0) * wa0 + ld_el(sA, o1) * wa1;
     if (NROWS == 2) {
       const float wb0 = w0 * r.wB, wb1 = w1 * r.wB;
-      l += buf_load(lB, o0) * wb0 + buf_load(lB, o1) * wb1;
-      if (MIX) s += buf_load(sB, o0) * wb0 + buf_load(sB, o1) * wb1;
+      l += ld_el(lB, o0) * wb0 + ld_el(lB, o1) * wb1;
+      if (MIX) s += ld_el(sB, o0) * wb0 + ld_el(sB, o1) * wb1;
     }
     const int cell = min(max(ct.x0, -kFsGuard), a.W + 2) + kFsGuard;
     const float4 ca = col[cell], cb = col[cell + 1];
@@ -181,7 +229,7 @@ __device__ __forceinline__ void fs_stage_row(const SweepArgs& a, const RowSel& r
 }
 
 // One wave's segment `seg` of the staged target row (b, y), all planes.  No barrier inside.
-template <bool MIX, bool AUTO, int NROWS, bool RENDER>
+template <class T, bool MIX, bool AUTO, int NROWS, bool RENDER>
 __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel& row, int b, int y, int seg,
                                                 float4* __restrict__ col, int2* __restrict__ shift,
                                                 float* __restrict__ rgb_rec, float* __restrict__ ph_map,
@@ -220,39 +268,48 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
   FwdAcc acc[2];
   RenderState rs[2];
   float dmax[2] = {-INFINITY, -INFINITY};   // fixed-reference softmax: largest exponent used so far
-  FsTaps<NROWS> g[D + 1];
+  FsTaps<T, NROWS> g[D + 1];
   int pn = 0;
   // A plane's staged shift is read from LDS ONE iteration before its tap loads are issued and kept in scalar registers until
   // the plane is reduced (one LDS read per iteration, off the critical path, instead of two round trips at the head of every
   // iteration).
   int sh_sd[D + 1], sh_kk[D + 1];          // wave-uniform (SGPRs): the shifts of the planes whose taps are in flight
   int2 sh_next = shift[0];       // LDS read in flight: the shift of the next plane to be prefetched
-  auto prefetch = [&](FsTaps<NROWS>& grp, int slot) {
+  auto prefetch = [&](FsTaps<T, NROWS>& grp, int slot) {
     const int n = min(pn, N - 1);   // past the end: re-load the last plane (unused) — unconditional issue keeps the wait counts right
     sh_sd[slot] = __builtin_amdgcn_readfirstlane(sh_next.x);
     sh_kk[slot] = __builtin_amdgcn_readfirstlane(sh_next.y);
     sh_next = shift[min(pn + 1, N - 1)];
     const int k = sh_kk[slot] >> 1;
-    fs_issue<MIX, NROWS>(grp, a, r, n, (unsigned)(xt0 + k) << 2, HW);
+    fs_issue<MIX, NROWS>(grp, a, r, n, fs_tap_off<T>(xt0 + k, k), HW);
     if (RENDER) {   // unshifted, coalesced: read where the pixels are, not where they sample (the last plane has none: alpha = 1)
       const float2 d2 = *reinterpret_cast<const float2*>(a.dists + ((long)r.b * (N - 1) + min(n, N - 2)) * HW + pix);
       grp.dist[0] = d2.x; grp.dist[1] = d2.y;
     }
     ++pn;
   };
-  auto step = [&](const FsTaps<NROWS>& grp, int n, int slot, int next_slot) {
+  // 8-byte form: regular plane, and no lane's load starts at a byte offset in [-size, -1] (12-byte fp32 form: column -3, -2
+  // or -1; 8-byte bf16 form from an even column: -4 or -2): a load that starts left of the row reads as zeros as a whole
+  // although its last columns may be inside, and the dword at byte offset -4 passes the 32-bit range check (offset + 4 wraps
+  // to 0).  Loads that start further left are dropped cleanly, those at >= 0 are exact.  (bf16: W is even, so no dword
+  // straddles the row's end: the per-dword check drops exactly the columns >= W.)
+  auto general_form = [&](int kk, int c0) {
+    if (sizeof(T) == 4) return (kk & 1) || (c0 < 0 && c0 + 2 * (kWave - 1) >= -3);
+    const int e0 = c0 - ((kk >> 1) & 1);
+    return (kk & 1) || (e0 < 0 && e0 + 2 * (kWave - 1) >= -4);
+  };
+  auto step = [&](const FsTaps<T, NROWS>& gq, int n, int slot, int next_slot) {
     const float sd = __int_as_float(sh_sd[slot]);
     const int kk = sh_kk[slot];
     const int k = kk >> 1;
     const int c0 = seg * kFsSeg + k;   // source column of the segment's first left tap (wave-uniform); lane i loads c0 + 2i ..
-    // 12-byte form: regular plane, and no lane's load starts at column -3, -2 or -1: a load that starts left of the row reads
-    // as zeros as a whole although its last columns may be inside, and the dword at byte offset -4 passes the 32-bit range
-    // check (offset + 4 wraps to 0).  Loads that start at column <= -4 are dropped cleanly, those at >= 0 are exact.
-    const bool general = (kk & 1) || (c0 < 0 && c0 + 2 * (kWave - 1) >= -3);
-    if (general) {
-      fs_general_plane<MIX, NROWS, RENDER>(a, r, col, n, sd, xt0f, HW, Wm1, rcpWm1, t, ea, automask, acc, rs, grp.dist);
+    if (general_form(kk, c0)) {
+      fs_general_plane<T, MIX, NROWS, RENDER>(a, r, col, n, sd, xt0f, HW, Wm1, rcpWm1, t, ea, automask, acc, rs, gq.dist);
       return;
     }
+    struct { float l[NROWS][3], s[NROWS][3]; float dist[2]; } grp;
+    fs_taps(gq, k, grp.l, grp.s);
+    grp.dist[0] = gq.dist[0]; grp.dist[1] = gq.dist[1];
     const int cell = min(max(xt0 + k, -kFsGuard), W + 1) + kFsGuard;
     const float4 cv0 = col[cell], cv1 = col[cell + 1], cv2 = col[cell + 2];
     const float kf = (float)k;
@@ -288,18 +345,20 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
     const int2 sh0 = shift[0];   // otherwise the general path's rescaling accumulator sets it when it reduces that plane)
     const float sd = __int_as_float(__builtin_amdgcn_readfirstlane(sh0.x));
     const int kk = __builtin_amdgcn_readfirstlane(sh0.y), k = kk >> 1, c0 = seg * kFsSeg + k;
-    if (!((kk & 1) || (c0 < 0 && c0 + 2 * (kWave - 1) >= -3))) {
+    if (!general_form(kk, c0)) {
       const float kf = (float)k;
+      float g0l[NROWS][3], g0s[NROWS][3];
+      fs_taps(g[0], k, g0l, g0s);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const float xtf = xt0f + (float)i, xsf = xtf + kf;
         const float ix = stream_ix(xtf, sd, Wm1, rcpWm1);
         const float w1 = ix - xsf, w0 = (xsf + 1.0f) - ix;
         float l;
-        if (NROWS == 1) l = g[0].l[0][i] * w0 + g[0].l[0][i + 1] * w1;
+        if (NROWS == 1) l = g0l[0][i] * w0 + g0l[0][i + 1] * w1;
         else {
           const float a0 = w0 * r.wA, a1 = w1 * r.wA, b0 = w0 * r.wB, b1 = w1 * r.wB;
-          l = g[0].l[0][i] * a0 + g[0].l[0][i + 1] * a1 + g[0].l[NROWS - 1][i] * b0 + g[0].l[NROWS - 1][i + 1] * b1;
+          l = g0l[0][i] * a0 + g0l[0][i + 1] * a1 + g0l[NROWS - 1][i] * b0 + g0l[NROWS - 1][i + 1] * b1;
         }
         acc[i].m = l * kLog2e;
       }
@@ -331,7 +390,7 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
     if (__builtin_amdgcn_ballot_w64(beyond) != 0) {   // rare: this wave again, every plane through the rescaling accumulator
       acc[0] = FwdAcc(); acc[1] = FwdAcc();
       for (int q = 0; q < N; ++q)
-        fs_general_plane<MIX, NROWS, RENDER>(a, r, col, q, __int_as_float(__builtin_amdgcn_readfirstlane(shift[q].x)), xt0f, HW, Wm1,
+        fs_general_plane<T, MIX, NROWS, RENDER>(a, r, col, q, __int_as_float(__builtin_amdgcn_readfirstlane(shift[q].x)), xt0f, HW, Wm1,
                                              rcpWm1, t, ea, automask, acc, rs, g[0].dist);
     }
   }
@@ -358,7 +417,7 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
 // staging, and polls until the whole team has.  LDS operations of a wave retire in order, so the bump follows the wave's
 // staging stores; the fences keep the compiler from moving LDS accesses across.
 // INVARIANT: every wave of a team runs the round loop of fwdstream_kernel the same number of times and reaches this barrier
-// in every round — the loop's only exits (`pos >= T`) are workgroup-uniform.  A per-wave early exit or `continue` before the
+// in every round — the loop's only exits (`pos >= nitems`) are workgroup-uniform.  A per-wave early exit or `continue` before the
 // barrier would leave the team's other waves polling for ever, with no diagnostic.
 __device__ __forceinline__ void fs_team_barrier(int* cnt, int target) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -387,7 +446,7 @@ static_assert(sizeof(SweepArgs) + 3 * sizeof(float*) + 4 * sizeof(int) + sizeof(
 // teams keep computing), and only the team meets (fs_team_barrier).  Measured on the per-wave timeline
 // (profiles/r05_fwd_ladder.md): with one 15-wave workgroup per CU and a workgroup barrier per item, the staging, the
 // dispatch turn-around and the 40 % spread between the first and the last wave of a workgroup idle the CU between items.
-template <bool MIX, bool AUTO, bool RENDER>
+template <class T, bool MIX, bool AUTO, bool RENDER>
 __global__ __launch_bounds__(kFsThreadsMax) void fwdstream_kernel(SweepArgs a, float* __restrict__ rgb_rec,
                                                                             float* __restrict__ ph_map,
                                                                             float* __restrict__ stash, int rows, int cblocks,
@@ -409,7 +468,7 @@ __global__ __launch_bounds__(kFsThreadsMax) void fwdstream_kernel(SweepArgs a, f
   // row groups first, the rounds snaking so that a block's items add up alike) or, without a table, item r * nbk + k.
   const int blk = blockIdx.y * gridDim.x + blockIdx.x;
   const int cb = blk % cblocks, k = blk / cblocks;
-  const int T = groups * a.B;
+  const int nitems = groups * a.B;
   const int tix = threadIdx.x - slot * segs * kWave, nthr = segs * kWave;
   if (!RENDER && rounds > 1) {
     if (threadIdx.x < rows) team[threadIdx.x] = 0;
@@ -420,7 +479,7 @@ __global__ __launch_bounds__(kFsThreadsMax) void fwdstream_kernel(SweepArgs a, f
                                              // and the loop around it costs them 40-60 spilled registers)
   for (int r = 0; r < nrounds; ++r) {
     const int pos = r * nbk + k;
-    if (pos >= T) break;                                         // (workgroup-uniform)
+    if (pos >= nitems) break;                                         // (workgroup-uniform)
     const int item = order.n ? (int)order.it[pos] : pos;
     const int b = item % a.B, grp = item / a.B;
     const int seg = cb * segs + (wave - slot * segs);            // which segment of the row
@@ -436,8 +495,8 @@ __global__ __launch_bounds__(kFsThreadsMax) void fwdstream_kernel(SweepArgs a, f
     if (!RENDER && rounds > 1) fs_team_barrier(team + slot, segs * (r + 1));
     else __syncthreads();
     if (!active) {}
-    else if (row.nrows == 2) ph_sum += fwdstream_body<MIX, AUTO, 2, RENDER>(a, row, b, y, seg, col, shift, rgb_rec, ph_map, stash);
-    else                     ph_sum += fwdstream_body<MIX, AUTO, 1, RENDER>(a, row, b, y, seg, col, shift, rgb_rec, ph_map, stash);
+    else if (row.nrows == 2) ph_sum += fwdstream_body<T, MIX, AUTO, 2, RENDER>(a, row, b, y, seg, col, shift, rgb_rec, ph_map, stash);
+    else                     ph_sum += fwdstream_body<T, MIX, AUTO, 1, RENDER>(a, row, b, y, seg, col, shift, rgb_rec, ph_map, stash);
   }
   if (a.ph_mean) {  // fused `.mean()` of trainer.py:742: wave totals -> LDS -> ONE atomic per workgroup
     const float v = wave_sum_hi(ph_sum);
@@ -613,21 +672,30 @@ bool fwdstream_applicable(const pd_sweep_desc* d, const SweepArgs& a) {
 
 int fwdstream_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, float* ph_map, float* stash, hipStream_t stream) {
   if ((reinterpret_cast<uintptr_t>(a.tgt) | reinterpret_cast<uintptr_t>(a.src) | reinterpret_cast<uintptr_t>(rgb_rec) |
-       reinterpret_cast<uintptr_t>(ph_map) | reinterpret_cast<uintptr_t>(stash)) & 7)
+       reinterpret_cast<uintptr_t>(ph_map) | reinterpret_cast<uintptr_t>(stash)) & 7) {
+    if (d->flags & PD_LOGITS_BF16) {   // (the one-pixel-per-lane forward reads fp32 only)
+      set_error("PD_LOGITS_BF16: tgt / src / rgb_rec / ph_map / stash must be 8-byte aligned");
+      return PD_ERR_UNSUPPORTED;
+    }
     return rowshift_fwd(d, a, rgb_rec, ph_map, stash, stream);   // unaligned tensors: the one-pixel-per-lane forward
+  }
   const FsShape sh = fwdstream_shape(d);
   const dim3 grid(sh.nbk * sh.cblocks, 1), block(sh.segs * sh.rows * kWave);
   const FsRows rowtab = fwdstream_rows(d->H, sh.rows, a.row_eps);
   const FsOrder order = fwdstream_order(d, sh, a.row_eps, rowtab);
   const size_t shmem = sh.lds;
   const bool mix = (d->flags & PD_MIXTURE) != 0, am = (d->flags & PD_AUTOMASK) != 0, render = (d->flags & PD_RENDER_PROB) != 0;
-#define PD_FS_LAUNCH(M, A, R)                                                                                              \
+#define PD_FS_LAUNCH_T(T, M, A, R)                                                                                         \
   do {                                                                                                                    \
     static LdsGrant granted;                                                                                              \
-    if (int rc = grant_dynamic_lds((const void*)fwdstream_kernel<M, A, R>, shmem, &granted, "fwdstream_kernel")) return rc; \
-    fwdstream_kernel<M, A, R><<<grid, block, shmem, stream>>>(a, rgb_rec, ph_map, stash, sh.rows, sh.cblocks, sh.rounds, sh.nbk, order, rowtab); \
+    if (int rc = grant_dynamic_lds((const void*)fwdstream_kernel<T, M, A, R>, shmem, &granted, "fwdstream_kernel")) return rc; \
+    fwdstream_kernel<T, M, A, R><<<grid, block, shmem, stream>>>(a, rgb_rec, ph_map, stash, sh.rows, sh.cblocks, sh.rounds, sh.nbk, order, rowtab); \
   } while (0)
-  if (render) {
+#define PD_FS_LAUNCH(M, A, R) PD_FS_LAUNCH_T(float, M, A, R)
+  if (d->flags & PD_LOGITS_BF16) {   // (pd_sweep_native_bf16: never with PD_RENDER_PROB)
+    if (mix) { if (am) PD_FS_LAUNCH_T(Bf16, true, true, false); else PD_FS_LAUNCH_T(Bf16, true, false, false); }
+    else PD_FS_LAUNCH_T(Bf16, false, false, false);
+  } else if (render) {
     if (mix) { if (am) PD_FS_LAUNCH(true, true, true); else PD_FS_LAUNCH(true, false, true); }
     else PD_FS_LAUNCH(false, false, true);
   } else {
@@ -635,6 +703,7 @@ int fwdstream_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, fl
     else PD_FS_LAUNCH(false, false, false);
   }
 #undef PD_FS_LAUNCH
+#undef PD_FS_LAUNCH_T
   return check_launch("fwdstream_kernel");
 }
 

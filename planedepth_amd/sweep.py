@@ -20,11 +20,12 @@ def _sweep_forward(src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_ma
     S.LAST_SWEEP_FLAGS = flags
     lib = C.load()
     B, N, H, W = logits.shape
-    C.require_gpu_tensor("logits", logits)
+    edt = torch.bfloat16 if flags & C.PD_LOGITS_BF16 else torch.float32   # storage of logits / sigma and their gradients
+    C.require_gpu_tensor("logits", logits, dtype=edt)
     C.require_gpu_tensor("src", src, (B, 3, H, W))
     C.require_gpu_tensor("tgt", tgt, (B, 3, H, W))
     if flags & C.PD_MIXTURE:
-        C.require_gpu_tensor("sigma", sigma, (B, N, H, W))
+        C.require_gpu_tensor("sigma", sigma, (B, N, H, W), dtype=edt)
     if mode == C.PD_WARP_DISP:
         C.require_gpu_tensor("disp", plane, (B, N, H, W) if flags & C.PD_DISP_DENSE else
                              ((B, N, H) if flags & C.PD_DISP_ROWS else (B, N)))
@@ -163,6 +164,11 @@ def _sweep_backward(saved, cfg, grads, need, into=None, accumulate=False, defer=
         g_logits = g_sigma = None
     elif into is not None:
         g_logits, g_sigma = into
+        edt = torch.bfloat16 if flags & C.PD_LOGITS_BF16 else torch.float32   # the buffers hold what the flag says
+        if g_logits is not None:
+            C.require_gpu_tensor("g_logits", g_logits, dtype=edt)
+        if g_sigma is not None:
+            C.require_gpu_tensor("g_sigma", g_sigma, dtype=edt)
     else:
         g_logits = torch.empty_like(logits) if need_logits else None
         g_sigma = torch.empty_like(sigma) if (need_sigma and mix) else None
@@ -438,10 +444,47 @@ class _MultiPlaneSweep(torch.autograd.Function):
         return tuple(out)
 
 
+def as_f32(t):
+    """``t`` as fp32 for the fp32 route (``t`` itself when it is fp32 already or None).  The copy is cached on ``t`` (per
+    version and grad mode): every view of one step that falls back sweeps the SAME fp32 tensor, so plane_sweep_multi
+    accepts them and their gradients add in fp32 before the cast's backward rounds the sum to ``t``'s dtype once.
+
+    Memory: the copy (twice the size of a bf16 ``t``) lives as long as ``t`` does.  For a LEAF ``t`` that requires grad the
+    copy's graph refers back to ``t``, a cycle through autograd's C++ nodes that Python's collector cannot break: ``del
+    t._pd_f32`` when such a tensor is done with (the trainer's tensors are decoder outputs, not leaves)."""
+    if t is None or t.dtype == torch.float32:
+        return t
+    key = (t._version, torch.is_grad_enabled())
+    c = getattr(t, "_pd_f32", None)
+    if c is not None and c[0] == key:
+        return c[1]
+    f = t.float()
+    t._pd_f32 = (key, f)
+    return f
+
+
+def _storage_route(logits, sigma, mix, desc):
+    """Where the call tuple is built: (logits, sigma, extra flags).  fp32 inputs pass as they are; bf16 logits (and bf16
+    sigma with the mixture) go to the kernels as bf16 with PD_LOGITS_BF16 where pd_sweep_native_bf16(desc) says the
+    descriptor is served (desc None: never); everything else — mixed dtypes, fp16, a descriptor outside the native set —
+    runs the fp32 route on as_f32 copies (their backward rounds each fp32 gradient once)."""
+    sig = sigma if mix else None
+    if logits.dtype == torch.float32 and (sig is None or sig.dtype == torch.float32):
+        return logits, sigma, 0
+    if (desc is not None and logits.dtype == torch.bfloat16 and (sig is None or sig.dtype == torch.bfloat16)
+            and C.load().pd_sweep_native_bf16(ctypes.byref(desc))):
+        return logits, sigma, C.PD_LOGITS_BF16
+    return as_f32(logits), as_f32(sig) if mix else sigma, 0
+
+
 def plane_sweep_multi(deferred):
     """``deferred``: one argument tuple per target view as returned by ``plane_sweep_disp(..., defer=True)`` /
     ``plane_sweep_homography(..., defer=True)`` — all over the same (src, logits, sigma).  Returns a list of
     ``(rgb_rec, ph_map, ph_mean)`` per view; see _MultiPlaneSweep."""
+    if any(d[10] & C.PD_LOGITS_BF16 for d in deferred):
+        # one node sums the views' gradients in place (PD_BWD_ACCUMULATE): fp32 only — every view sweeps ONE fp32 copy
+        deferred = [(d[0], d[1], as_f32(d[2]), as_f32(d[3])) + tuple(d[4:10]) + (d[10] & ~C.PD_LOGITS_BF16,) + tuple(d[11:])
+                    for d in deferred]
     src, _, logits = deferred[0][0], deferred[0][1], deferred[0][2]
     sigma = next((d[3] for d in deferred if d[3] is not None), None)
     flat = []
@@ -526,6 +569,9 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
         if C.load().pd_sweep_uses_rowshift(ctypes.byref(probe)):
             shift, mask = _rows
             flags = _flags(use_mixture_loss, automask, rows=True, render=render_probability) | C.PD_MASK_ROWS
+            logits, sigma, bf = _storage_route(logits, sigma, use_mixture_loss,
+                                               _desc(B, N, H, W, C.PD_WARP_DISP, flags, _SIGN.get(target_side, 0.0)))
+            flags |= bf
             call = (src, tgt, logits, sigma if use_mixture_loss else None, shift, None, None, mask,
                     dists if render_probability else None, C.PD_WARP_DISP, flags, _SIGN.get(target_side, 0.0))
             if defer:
@@ -560,12 +606,17 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
             padding_mask = padding_mask[..., 0]
             flags |= C.PD_MASK_ROWS
     sign = _SIGN.get(target_side, 0.0)  # any other key leaves the grid untouched (trainer.py:546-549)
+    # bf16 logits / sigma: native where the descriptor is served (a per-pixel mask never is); else fp32 copies
+    native_ok = padding_mask is None or bool(flags & C.PD_MASK_ROWS)
+    logits, sigma, bf = _storage_route(logits, sigma, use_mixture_loss,
+                                       _desc(B, N, H, W, C.PD_WARP_DISP, flags, sign) if native_ok else None)
+    flags |= bf
     call = (src, tgt, logits, sigma if use_mixture_loss else None, plane, None, None, padding_mask,
             dists if render_probability else None, C.PD_WARP_DISP, flags, sign)
     # a fused decoder tail that asked for it (decoder_tail(..., fuse_sweep_backward=True)) gets its backward applied by this
     # sweep's backward kernel — where the library serves that form for this descriptor
     link = getattr(logits, "_pd_tail_link", None)
-    if (link is not None and per_plane and use_mixture_loss and padding_mask is None and not render_probability
+    if (link is not None and not bf and per_plane and use_mixture_loss and padding_mask is None and not render_probability
             and sigma is not None and getattr(sigma, "_pd_tail_link", None) is link
             and C.load().pd_sweep_bwd_tail_fuses(ctypes.byref(_desc(B, N, H, W, C.PD_WARP_DISP, flags, sign)))):
         link.consumers += 1
@@ -697,6 +748,7 @@ def plane_sweep_homography(src, tgt, logits, sigma, distance, norm, T, K, inv_K,
                                   return_mean, defer, render_probability, dists)
     ex = lambda M: M[:, None].expand(-1, N, -1, -1).reshape(B * N, 4, 4)  # noqa: E731
     inv_K3 = inv_K[:, :3, :3]
+    logits, sigma, _ = _storage_route(logits, sigma, use_mixture_loss, None)   # (per-plane / plane-uniform matrices: fp32 only)
     flags = _flags(use_mixture_loss, automask, render=render_probability)
     tw = None
     if plane_uniform:
@@ -749,6 +801,7 @@ def plane_sweep_layers(src, logits, sigma, *, disp_layered=None, padding_mask=No
     lib = C.load()
     B, N, H, W = logits.shape
     with torch.no_grad():
+        logits, sigma, _ = _storage_route(logits, sigma, use_mixture_loss, None)   # (the layers kernel reads fp32 only)
         if homography is None:
             if tuple(disp_layered.shape) != (B, N, H, W):
                 disp_layered = disp_layered.expand(B, N, H, W)

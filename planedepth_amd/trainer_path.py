@@ -100,11 +100,14 @@ def pred_novel_images(self, inputs, outputs):
     except AttributeError:
         pass
     calls, handles = [], []
+    logits = outputs["logits"]
+    if len(self.target_sides) > 1:   # bf16 (autocast) logits / sigma: ONE fp32 copy for every view, whose gradients then add
+        logits = ops.as_f32(logits)  # in fp32 and are rounded once (ops.as_f32); a single view may run the native bf16 kernels
     for target_side in self.target_sides:
         tgt = inputs[(cname, target_side)]
-        sigma = outputs["sigma"] if mix else None
+        sigma = (ops.as_f32(outputs["sigma"]) if len(self.target_sides) > 1 else outputs["sigma"]) if mix else None
         if opt.warp_type == "disp_warp":
-            call = ops.plane_sweep_disp(src, tgt, outputs["logits"], sigma, outputs["disp_layered"],
+            call = ops.plane_sweep_disp(src, tgt, logits, sigma, outputs["disp_layered"],
                                         padding_mask, target_side=target_side,
                                         use_mixture_loss=mix, automask=automask,
                                         render_probability=render, dists=dists,
@@ -132,7 +135,7 @@ def pred_novel_images(self, inputs, outputs):
                         and bool((outputs["norm"][..., 0] == 0).all())):
                     raise ValueError("outputs[('Rt', %r)] is not a pure x-translation, or a plane normal has an x "
                                      "component although opt.yz_levels == 0" % (target_side,))
-            call = ops.plane_sweep_homography(src, tgt, outputs["logits"], sigma,
+            call = ops.plane_sweep_homography(src, tgt, logits, sigma,
                                               outputs["distance"], outputs["norm"], T, inputs["K"],
                                               inputs["inv_K"], use_mixture_loss=mix,
                                               automask=automask, render_probability=render,
