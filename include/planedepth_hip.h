@@ -539,6 +539,39 @@ int pd_grid_sample_bwd(int M, int C, int Hi, int Wi, int Ho, int Wo, int padding
                        const float* grid, const float* g_out, float* g_input, float* g_grid, pd_stream_t stream);
 
 /*
+ * Depth evaluation (pd_depth_eval.hip): the Eigen metrics with median scaling of evaluate_depth_HR.py:148-166, 217-279
+ * (compute_errors :30-49, batch_post_process_disparity :51-59) and Trainer.compute_depth_losses (trainer.py:775-810 with
+ * layers.py:356-374).  The full contract is the header comment of pd_depth_eval.hip and planedepth_amd/metrics.py.
+ *   pred      A: disparity [M,h,w] ([2M,h,w] with PD_EVAL_POST_PROCESS: image i's mirrored pass is image i+M);
+ *             PD_EVAL_TRAINER: depth [M,1,h,w] at the GT's resolution
+ *   grid      PD_EVAL_TRAINER only: channel 0 of inputs["grid"], [M,h,grid_w] (the per-row divisor grid[..,gw-1] - grid[..,0])
+ *   gt, meta  GT of every image packed into one fp32 buffer; meta int64 [M][8] on the device = (offset of the image in `gt`
+ *             in floats, gt_h, gt_w, crop y0, y1, x0, x1, 0); the crop is the whole image for non-Eigen splits
+ *   max_tiles ceil(max_i gt_h*gt_w / PD_EVAL_TILE): the launch grid is [M][max_tiles] tiles
+ *   disp_num  float32(0.1*0.58*width) (A); scale_factor: A 1 or 5.4 before the medians, PD_EVAL_TRAINER the factor used
+ *             instead of the medians (5.4)
+ * Outputs over S segments (S = M; 1 with PD_EVAL_TRAINER, which pools the batch): metrics [S,7] fp32 (abs_rel, sq_rel, rmse,
+ * rmse_log, a1, a2, a3), ratio [S], medians [S,2] (of gt, of depth; NaN without PD_EVAL_MEDIAN), counts [S,4] int32
+ * (n, #a1, #a2, #a3).  workspace: pd_depth_eval_workspace_bytes bytes (no zero-fill needed).  Deterministic: integer
+ * atomics only, fixed-order floating-point sums.
+ * pd_depth_eval_resize: the resized (and, PD_EVAL_POST_PROCESS, post-processed) disparity of step A2 alone, written into a
+ * buffer packed like `gt` (max_hw = max_i gt_h*gt_w).
+ */
+enum pd_eval_flags {
+  PD_EVAL_POST_PROCESS = 1, /* evaluate_depth_HR.py:163-165: average with the mirrored pass before resizing        */
+  PD_EVAL_EIGEN = 2,        /* eigen_raw / eigen_improved: 1e-3 < gt < 80 inside the Eigen crop (:237-249); else gt > 0 */
+  PD_EVAL_MEDIAN = 4,       /* median scaling (A: numpy's median; PD_EVAL_TRAINER: opt.no_stereo, torch's lower median)  */
+  PD_EVAL_TRAINER = 8       /* Trainer.compute_depth_losses: depth input, per-row grid divisor, pooled batch            */
+};
+enum { PD_EVAL_TILE = 16384 };
+size_t pd_depth_eval_workspace_bytes(int M, int max_tiles, int flags);
+int pd_depth_eval(int M, int h, int w, int flags, int max_tiles, float disp_num, float scale_factor, const float* pred,
+                  const float* grid, int grid_w, const float* gt, const int64_t* meta, void* workspace, float* metrics,
+                  float* ratio, float* medians, int32_t* counts, pd_stream_t stream);
+int pd_depth_eval_resize(int M, int h, int w, int flags, int max_hw, const float* pred, const int64_t* meta, float* out,
+                         pd_stream_t stream);
+
+/*
  * Diagnostics (used by tests/ and scripts/, not by the product path).
  *   pd_selftest_division        counts, over `count` samples lo + i*step, where the row kernels' fast division by W-1
  *                               (refined reciprocal) differs from the IEEE quotient; *d_mismatches (device int) += count.

@@ -24,6 +24,8 @@ PD_PP_DISP_DENSE, PD_PP_FLIP_SRC, PD_PP_DISP_ROWS = 1, 2, 4
 PD_HMAT_PLANES, PD_HMAT_UNIFORM, PD_HMAT_STEREO_ROWS = 0, 1, 2
 PD_IMPL_AUTO, PD_IMPL_GENERAL, PD_IMPL_FAST_ROWS, PD_IMPL_TILE, PD_IMPL_ROWS1, PD_IMPL_UNIFORM_DIRECT = 0, 1, 2, 3, 4, 5
 PD_IMPL_EXACT_ROWS = 6
+PD_EVAL_POST_PROCESS, PD_EVAL_EIGEN, PD_EVAL_MEDIAN, PD_EVAL_TRAINER = 1, 2, 4, 8
+PD_EVAL_TILE = 16384   # GT pixels per tile of pd_depth_eval (enum in the header)
 
 
 class SweepDesc(ctypes.Structure):
@@ -117,6 +119,9 @@ SIGNATURES = {
     "pd_homography_grid_bwd": (_I, [_I] * 3 + [_P] * 5),
     "pd_grid_sample_fwd": (_I, [_I] * 7 + [_P] * 4),
     "pd_grid_sample_bwd": (_I, [_I] * 7 + [_P] * 6),
+    "pd_depth_eval_workspace_bytes": (ctypes.c_size_t, [_I] * 3),
+    "pd_depth_eval": (_I, [_I] * 5 + [_F, _F, _P, _P, _I] + [_P] * 8),
+    "pd_depth_eval_resize": (_I, [_I] * 5 + [_P] * 4),
 }
 
 _lib = None

@@ -1,8 +1,8 @@
 """Autograd-aware operators over the C ABI (``include/planedepth_hip.h``) — the one namespace the rest of the package, the tests
 and ``bench.py`` use.  The operators live in ``sweep`` (the fused plane sweep: autograd nodes, routing, homography algebra),
 ``tails`` (decoder / PladeNet tails), ``losses`` (SSIM, mixture NLL, masked photometric, smoothness), ``postprocess``
-(self-distillation warps, batch doubling, crop grid), ``geometry`` (backproject / project / homography grids, grid_sample) and
-``_buffers`` (descriptors, pre-zeroed pools); the switches tests flip between calls (``ops.SWEEP_IMPL = ...``) are attributes
+(self-distillation warps, batch doubling, crop grid), ``metrics`` (depth evaluation), ``geometry`` (backproject / project /
+homography grids, grid_sample) and ``_buffers`` (descriptors, pre-zeroed pools); the switches tests flip between calls (``ops.SWEEP_IMPL = ...``) are attributes
 of ``_state`` that this module forwards both ways.
 
 Every function launches hand-written HIP kernels through ctypes on torch's current stream.  PyTorch is used for device
@@ -31,6 +31,8 @@ from .losses import (  # noqa: F401
 from .postprocess import (  # noqa: F401
     _pp_disp, warp_softmax, warp_sum, pp_combine, post_process_disp, post_process_disp_stepwise, cat_flip,
     crop_grid)
+from .metrics import (  # noqa: F401
+    DepthEval, PackedGT, pack_gt, eval_depth_errors, resize_disp, trainer_depth_metrics, summarize)
 from .geometry import (  # noqa: F401
     _Backproject, backproject_depth, _Project3D, project_3d, _HomographyGrid, homography_grid,
     _GridSample, grid_sample)

@@ -324,6 +324,25 @@ def add_flip_right_inputs(self, inputs):
     return new_inputs
 
 
+def compute_depth_losses(self, inputs, outputs):
+    """Depth metrics for monitoring during training (reference trainer.py:775-810 with layers.py:356-374), pooled over the
+    batch as the reference does, on the device and without a host sync: ``{"de/abs_rel": 0-dim tensor, ...}``.
+
+    ``self`` only needs ``opt.no_stereo`` (median scaling by torch's lower medians; otherwise the fixed factor 5.4).
+    ``inputs[("depth_gt", "l")]`` must have the prediction's H x W, as in the reference (metrics.py, contract B)."""
+    from . import metrics
+    r = metrics.trainer_depth_metrics(outputs["depth"], inputs["grid"], inputs[("depth_gt", "l")],
+                                      no_stereo=bool(getattr(self.opt, "no_stereo", False)))
+    names = getattr(self, "depth_metric_names", metrics.TRAINER_METRIC_NAMES)
+    return {name: r.metrics[0, i] for i, name in enumerate(names)}
+
+
+def patch_trainer_metrics(trainer_cls):
+    """Opt-in: bind :func:`compute_depth_losses` to a reference ``Trainer`` class (``patch_trainer`` leaves it alone)."""
+    trainer_cls.compute_depth_losses = compute_depth_losses
+    return trainer_cls
+
+
 def patch_trainer(trainer_cls):
     """Bind the fused hot path onto a reference-style Trainer class (drop-in)."""
     trainer_cls.pred_novel_images = pred_novel_images
