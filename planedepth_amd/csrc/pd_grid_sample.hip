@@ -13,6 +13,11 @@ __device__ __forceinline__ float clip_coord(float v, float hi, float& dmul) {
   return v;
 }
 
+// zeros mode: a NaN, infinite or huge coordinate samples nothing (F.grid_sample: no tap is inside the image).  The tap
+// weights of such a coordinate are NaN (inf - inf), and NaN * 0 would reach the output and both gradients, so it is
+// replaced by a finite coordinate outside every image.  (Also covers inf * 0 from a one-pixel-wide input.)
+__device__ __forceinline__ float outside_if_wild(float v) { return fabsf(v) <= 1e9f ? v : -2.0f; }
+
 __global__ __launch_bounds__(kBlock) void grid_sample_fwd_kernel(int C, int Hi, int Wi, int HWo, int border,
                                                                  const float* __restrict__ in,
                                                                  const float* __restrict__ grid,
@@ -26,6 +31,9 @@ __global__ __launch_bounds__(kBlock) void grid_sample_fwd_kernel(int C, int Hi, 
     float dm;
     ix = clip_coord(ix, (float)(Wi - 1), dm);
     iy = clip_coord(iy, (float)(Hi - 1), dm);
+  } else {
+    ix = outside_if_wild(ix);
+    iy = outside_if_wild(iy);
   }
   const Tap t = make_tap(ix, iy, Wi, Hi);
   for (int c = 0; c < C; ++c)
@@ -49,6 +57,9 @@ __global__ __launch_bounds__(kBlock) void grid_sample_bwd_kernel(int C, int Hi, 
     iy = clip_coord(iy, (float)(Hi - 1), dmy);
     mx *= dmx;
     my *= dmy;
+  } else {
+    ix = outside_if_wild(ix);
+    iy = outside_if_wild(iy);
   }
   const Tap t = make_tap(ix, iy, Wi, Hi);
   // neighbouring output pixels usually sample neighbouring input pixels: lanes whose left column is the previous lane's

@@ -18,31 +18,51 @@ __device__ __forceinline__ int reflect(int i, int n) {  // ReflectionPad2d(1): -
 }
 
 struct SsimStats {
-  float mu_x, mu_y, sxx, syy, sxy;  // window means of x, y, x^2, y^2, xy
+  float mu_x, mu_y, vx, vy, cxy;  // window means of x and y, variances and covariance
 };
+
+// The second moments are taken about the means (a second pass over the nine values in registers), not as
+// E[x^2] - mu^2: that difference loses log2(E[x^2] / sigma) bits, and on a low-contrast window of two nearly equal images
+// the loss is the size of the SSIM value itself, which then lands on the wrong side of the clamp at 0 that gates the
+// gradient.  Explicit FMAs, the same for the three sums: x == y gives vx == vy == cxy bit for bit.
+__device__ __forceinline__ SsimStats stats9(const float (&a)[9], const float (&b)[9]) {
+  float sx = 0.0f, sy = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) { sx += a[i]; sy += b[i]; }
+  const float k = 1.0f / 9.0f;
+  const float mx = sx * k, my = sy * k;
+  float vx = 0.0f, vy = 0.0f, cxy = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    const float da = a[i] - mx, db = b[i] - my;
+    vx = fmaf(da, da, vx); vy = fmaf(db, db, vy); cxy = fmaf(da, db, cxy);
+  }
+  return {mx, my, vx * k, vy * k, cxy * k};
+}
 
 __device__ __forceinline__ SsimStats window_stats(const float* __restrict__ x, const float* __restrict__ y, int px,
                                                   int py, int H, int W) {
-  float sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
+  float a[9], b[9];
 #pragma unroll
   for (int dy = -1; dy <= 1; ++dy) {
     const int yy = reflect(py + dy, H);
 #pragma unroll
     for (int dx = -1; dx <= 1; ++dx) {
       const int xx = reflect(px + dx, W);
-      const float a = x[yy * W + xx], b = y[yy * W + xx];
-      sx += a; sy += b; sxx += a * a; syy += b * b; sxy += a * b;
+      a[(dy + 1) * 3 + dx + 1] = x[yy * W + xx];
+      b[(dy + 1) * 3 + dx + 1] = y[yy * W + xx];
     }
   }
-  const float k = 1.0f / 9.0f;
-  return {sx * k, sy * k, sxx * k, syy * k, sxy * k};
+  return stats9(a, b);
 }
 
+// No FMA contraction in the two functions below: with x == y the numerator and the denominator are then the same
+// rounded products, so identical images give exactly 0 and an exactly zero gradient (contracted, mu_x^2 + mu_y^2 rounds
+// once and 2 mu_x mu_y twice).
 __device__ __forceinline__ float ssim_value(const SsimStats& s) {
-  const float sigma_x = s.sxx - s.mu_x * s.mu_x, sigma_y = s.syy - s.mu_y * s.mu_y;
-  const float sigma_xy = s.sxy - s.mu_x * s.mu_y;
-  const float n = (2.0f * s.mu_x * s.mu_y + kC1) * (2.0f * sigma_xy + kC2);
-  const float d = (s.mu_x * s.mu_x + s.mu_y * s.mu_y + kC1) * (sigma_x + sigma_y + kC2);
+#pragma clang fp contract(off)
+  const float n = (2.0f * s.mu_x * s.mu_y + kC1) * (2.0f * s.cxy + kC2);
+  const float d = (s.mu_x * s.mu_x + s.mu_y * s.mu_y + kC1) * (s.vx + s.vy + kC2);
   return fminf(fmaxf((1.0f - n / d) * 0.5f, 0.0f), 1.0f);
 }
 
@@ -52,8 +72,9 @@ struct SsimCoef {
 };
 
 __device__ __forceinline__ SsimCoef ssim_coef(const SsimStats& s, float g) {
+#pragma clang fp contract(off)
   const float mx = s.mu_x, my = s.mu_y;
-  const float sigma_x = s.sxx - mx * mx, sigma_y = s.syy - my * my, sigma_xy = s.sxy - mx * my;
+  const float sigma_x = s.vx, sigma_y = s.vy, sigma_xy = s.cxy;
   const float n1 = 2.0f * mx * my + kC1, n2 = 2.0f * sigma_xy + kC2;
   const float d1 = mx * mx + my * my + kC1, d2 = sigma_x + sigma_y + kC2;
   const float n = n1 * n2, d = d1 * d2;
@@ -61,9 +82,9 @@ __device__ __forceinline__ SsimCoef ssim_coef(const SsimStats& s, float g) {
   SsimCoef k = {0, 0, 0, 0, 0};
   if (!(v >= 0.0f && v <= 1.0f)) return k;  // clamp(.,0,1) blocks the gradient outside [0,1] (inclusive inside)
   const float gn = -0.5f * g / d;           // d out / d n
-  const float gd = 0.5f * g * n / (d * d);  // d out / d d
+  const float gd = -gn * (n / d);           // d out / d d = 0.5 g n / d^2; in this form n == d gives gd == -gn exactly
   const float g_n1 = gn * n2, g_n2 = gn * n1, g_d1 = gd * d2, g_d2 = gd * d1;
-  // through sigma_x = E[x^2] - mu_x^2 etc.
+  // through sigma_x = E[x^2] - mu_x^2 etc. (the derivatives do not depend on how the moments were summed)
   const float g_sxx = g_d2, g_syy = g_d2, g_sxy = 2.0f * g_n2;
   const float g_mx = g_n1 * 2.0f * my + g_d1 * 2.0f * mx - g_d2 * 2.0f * mx - g_sxy * my;
   const float g_my = g_n1 * 2.0f * mx + g_d1 * 2.0f * my - g_d2 * 2.0f * my - g_sxy * mx;
@@ -109,16 +130,15 @@ __device__ __forceinline__ void ssim_grad_tile(SsimTile& t, int H, int W, const 
     const int py = ty0 - 1 + r, px = tx0 - 1 + cc;
     SsimCoef k = {0, 0, 0, 0, 0};
     if (py >= 0 && py < H && px >= 0 && px < W) {
-      float sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
+      float a[9], b[9];
 #pragma unroll
       for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {   // same summation order as window_stats (row-major over the window)
-          const float a = t.x[r + dy][cc + dx], b = t.y[r + dy][cc + dx];
-          sx += a; sy += b; sxx += a * a; syy += b * b; sxy += a * b;
+        for (int dx = 0; dx < 3; ++dx) {   // same order as window_stats (row-major over the window)
+          a[dy * 3 + dx] = t.x[r + dy][cc + dx];
+          b[dy * 3 + dx] = t.y[r + dy][cc + dx];
         }
-      const float k9 = 1.0f / 9.0f;
-      const SsimStats st = {sx * k9, sy * k9, sxx * k9, syy * k9, sxy * k9};
+      const SsimStats st = stats9(a, b);
       k = ssim_coef(st, scale * g[py * W + px]);
     }
     t.ax[r][cc] = k.ax; t.bx[r][cc] = k.bx; t.c[r][cc] = k.c;
@@ -148,8 +168,15 @@ __device__ __forceinline__ void ssim_grad_tile(SsimTile& t, int H, int W, const 
       for (int dx = -1; dx <= 1; ++dx) cx += (reflect(px + dx, W) == qx);
       const float mult = (float)(cx * cy);
       const int r = ly + 1 + oy, cc = lx + 1 + ox;
-      gx += mult * (t.ax[r][cc] + t.bx[r][cc] * xq + t.c[r][cc] * yq);
-      if (WANT_Y) gy += mult * (t.ay[r][cc] + t.by[r][cc] * yq + t.c[r][cc] * xq);
+      {
+#pragma clang fp contract(off)   // bx == -c and x == y (identical images) cancel exactly only as two rounded products
+        const float tx = t.ax[r][cc] + t.bx[r][cc] * xq + t.c[r][cc] * yq;
+        gx += mult * tx;
+        if (WANT_Y) {
+          const float ty = t.ay[r][cc] + t.by[r][cc] * yq + t.c[r][cc] * xq;
+          gy += mult * ty;
+        }
+      }
     }
   }
 }
@@ -229,6 +256,7 @@ using namespace pd;
 
 extern "C" int pd_ssim_fwd(int B, int C, int H, int W, const float* x, const float* y, float* out, pd_stream_t stream) {
   PD_REQUIRE(B > 0 && C > 0 && H >= 2 && W >= 2, "bad shape");
+  PD_REQUIRE((long)B * C <= 65535, "too many image planes for one launch (B * C <= 65535)");   // grid.y = B * C
   PD_REQUIRE(x && y && out, "NULL pointer");
   ssim_fwd_kernel<<<dim3(ceil_div(H * W, kBlock), B * C), kBlock, 0, (hipStream_t)stream>>>(H, W, x, y, out);
   return check_launch("ssim_fwd_kernel");
@@ -248,6 +276,7 @@ extern "C" int pd_ssim_bwd(int B, int C, int H, int W, const float* x, const flo
 extern "C" int pd_reproj_loss_fwd(int B, int H, int W, int use_ssim, const float* pred, const float* target,
                                   float* loss, pd_stream_t stream) {
   PD_REQUIRE(B > 0 && H >= 2 && W >= 2, "bad shape");
+  PD_REQUIRE(B <= 65535, "batch too large for one launch (B <= 65535)");   // grid.y = B
   PD_REQUIRE(pred && target && loss, "NULL pointer");
   reproj_fwd_kernel<<<dim3(ceil_div(H * W, kBlock), B), kBlock, 0, (hipStream_t)stream>>>(H, W, use_ssim, pred, target,
                                                                                            loss);

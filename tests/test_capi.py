@@ -62,6 +62,16 @@ def test_argument_validation_needs_no_gpu():
     assert b"warp mode" in lib.pd_last_error()
     assert lib.pd_ssim_fwd(0, 3, 8, 8, None, None, None, None) == 1
     assert lib.pd_grid_sample_fwd(1, 1, 4, 4, 4, 4, 9, None, None, None, None) == 1
+    # the forward SSIM / reprojection launches put B * C (B) in the second grid dimension: refused on the host, and told
+    # apart from the NULL-pointer refusal by the limit the message names
+    assert lib.pd_ssim_fwd(21846, 3, 8, 8, None, None, None, None) == 1
+    assert b"65535" in lib.pd_last_error() and b"NULL" not in lib.pd_last_error()
+    assert lib.pd_ssim_fwd(21845, 3, 8, 8, None, None, None, None) == 1
+    assert b"NULL" in lib.pd_last_error()
+    assert lib.pd_reproj_loss_fwd(65536, 8, 8, 1, None, None, None, None) == 1
+    assert b"65535" in lib.pd_last_error() and b"NULL" not in lib.pd_last_error()
+    assert lib.pd_reproj_loss_fwd(65535, 8, 8, 1, None, None, None, None) == 1
+    assert b"NULL" in lib.pd_last_error()
     # the next-row entry points validate before they launch, too
     assert lib.pd_decoder_tail_fwd(1, 4, 8, 8, C.PD_TAIL_MIXTURE, *([None] * 10)) == 1
     assert b"NULL" in lib.pd_last_error()
