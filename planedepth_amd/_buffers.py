@@ -1,5 +1,7 @@
 """Plumbing shared by the operator modules: descriptors, event timing around launches, pre-zeroed pools, the (optionally
 poisoned) allocator front."""
+import ctypes
+import functools
 import os
 
 import torch
@@ -96,14 +98,20 @@ def _zero_block(device, shape):
     return st[0][i:i + n].view(shape)
 
 
-def _plane_grad_buffer(plane, mode, flags):
-    """(g_plane buffer, extra descriptor flags) for a backward call that wants the plane-parameter gradient: one disparity
-    per plane gets a pre-zeroed [B, N] block and PD_BWD_PLANE_ZEROED (the row-stream backward then adds its rows' shares
-    there and launches no reduction kernel; the other kernels overwrite it as ever)."""
+@functools.lru_cache(maxsize=None)
+def _plane_adds(B, N, H, W, mode, flags, sign, impl):
+    """pd_sweep_bwd_plane_adds for a descriptor, asked once per descriptor (no library call per step)."""
+    return bool(C.load().pd_sweep_bwd_plane_adds(ctypes.byref(C.SweepDesc(B, N, H, W, mode, flags, float(sign), impl))))
+
+
+def _plane_grad_buffer(plane, B, N, H, W, mode, flags, sign):
+    """(g_plane buffer, extra descriptor flags) for a backward call that wants the plane-parameter gradient.  Where the library
+    adds it into a zeroed block (pd_sweep_bwd_plane_adds: the row-stream backward, one disparity per plane — it then launches
+    no reduction kernel) that is a pre-zeroed [B, N] block and PD_BWD_PLANE_ZEROED; elsewhere a fresh buffer the kernels
+    overwrite."""
     # (float atomics: the sum's last bits depend on the order of the adds — under torch.use_deterministic_algorithms(True) the
     # deterministic partial sums + reduction launch are used instead)
-    if (S.PLANE_ADDS and not torch.are_deterministic_algorithms_enabled() and mode == C.PD_WARP_DISP
-            and not flags & (C.PD_DISP_DENSE | C.PD_DISP_ROWS)):
+    if (S.PLANE_ADDS and not torch.are_deterministic_algorithms_enabled()
+            and _plane_adds(B, N, H, W, mode, flags, sign, S.SWEEP_IMPL)):
         return _zero_block(plane.device, tuple(plane.shape)), C.PD_BWD_PLANE_ZEROED
     return torch.empty_like(plane), 0
-

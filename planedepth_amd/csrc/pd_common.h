@@ -17,6 +17,9 @@ constexpr int kBlock = 256;  // 4 waves: one per SIMD of a CU
 // ---- host side -------------------------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// partials [B][nblk][M] -> out [B][M], summed in a fixed order (deterministic): the second stage of every block-reduced
+// gradient (pd_common.hip: reduce_partials_kernel)
+int reduce_partials(const float* partials, float* out, int nblk, int M, int B, hipStream_t stream);
 
 // Process-environment tuning / A-B switches.  They are read ONCE, when the library is first used (pd_version() or the
 // first launch), never on the launch path: an entry point's behaviour cannot change between two calls of a process, and

@@ -186,16 +186,6 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const floa
   }
 }
 
-// partials [B][R][N] -> out [B][N]; one wave per (n, b)
-__global__ void tail_reduce_kernel(const float* __restrict__ partials, float* __restrict__ out, int R, int N) {
-  const int n = blockIdx.x, b = blockIdx.y;
-  const float* p = partials + (long)b * R * N + n;
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < R; i += kWave) acc += p[(long)i * N];
-  acc = wave_sum(acc);
-  if (threadIdx.x == 0) out[(long)b * N + n] = acc;
-}
-
 static int tail_validate(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
                          const float* dl) {
   PD_REQUIRE(B > 0 && B <= 65535 && N > 0 && H > 0 && W > 0, "bad shape");
@@ -291,8 +281,7 @@ extern "C" int pd_decoder_tail_bwd(int B, int N, int H, int W, int flags, const 
                    g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
   if (int rc = check_launch("tail_bwd_kernel")) return rc;
   if (reduce) {
-    tail_reduce_kernel<<<dim3(N, B), kWave, 0, (hipStream_t)stream>>>(workspace, g_disp_layered, (int)grid.x, N);
-    return check_launch("tail_reduce_kernel");
+    return reduce_partials(workspace, g_disp_layered, (int)grid.x, N, B, (hipStream_t)stream);
   }
   return 0;
 }

@@ -182,16 +182,6 @@ __global__ __launch_bounds__(kBlock) void homography_grid_bwd_kernel(int H, int 
   if (threadIdx.x < 9) partials[((long)m * gridDim.x + blockIdx.x) * 9 + threadIdx.x] = red[threadIdx.x];
 }
 
-// partials [Bo][nblk][M] -> out [Bo][M] in a fixed order: one wave per output element, lanes stride over the blocks
-__global__ void reduce_small_kernel(const float* __restrict__ partials, float* __restrict__ out, int nblk, int M) {
-  const int j = blockIdx.x, b = blockIdx.y;
-  const float* p = partials + (long)b * nblk * M + j;
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < nblk; i += kWave) acc += p[(long)i * M];
-  acc = wave_sum(acc);
-  if (threadIdx.x == 0) out[(long)b * M + j] = acc;
-}
-
 }  // namespace pd
 
 using namespace pd;
@@ -231,8 +221,7 @@ extern "C" int pd_project3d_bwd(int B, int H, int W, float eps, const float* cam
                                                                           g_P ? workspace : nullptr);
   int rc = check_launch("project3d_bwd_kernel");
   if (rc || !g_P) return rc;
-  reduce_small_kernel<<<dim3(12, B), kWave, 0, (hipStream_t)stream>>>(workspace, g_P, nblk, 12);
-  return check_launch("reduce_small_kernel");
+  return reduce_partials(workspace, g_P, nblk, 12, B, (hipStream_t)stream);
 }
 
 extern "C" int pd_homography_grid(int M, int H, int W, const float* H_t2s, const float* Rn, const float* inv_K3,
@@ -252,6 +241,5 @@ extern "C" int pd_homography_grid_bwd(int M, int H, int W, const float* H_t2s, c
   homography_grid_bwd_kernel<<<dim3(nblk, M), kBlock, 0, (hipStream_t)stream>>>(H, W, H_t2s, g_grid, workspace);
   int rc = check_launch("homography_grid_bwd_kernel");
   if (rc) return rc;
-  reduce_small_kernel<<<dim3(9, M), kWave, 0, (hipStream_t)stream>>>(workspace, g_H, nblk, 9);
-  return check_launch("reduce_small_kernel");
+  return reduce_partials(workspace, g_H, nblk, 9, M, (hipStream_t)stream);
 }

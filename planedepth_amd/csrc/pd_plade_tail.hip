@@ -233,16 +233,6 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
   }
 }
 
-// partials [B][R][N] -> out [B][N]; one wave per (n, b); fixed order
-__global__ void plade_reduce_kernel(const float* __restrict__ partials, float* __restrict__ out, int R, int N) {
-  const int n = blockIdx.x, b = blockIdx.y;
-  const float* p = partials + (long)b * R * N + n;
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < R; i += kWave) acc += p[(long)i * N];
-  acc = wave_sum(acc);
-  if (threadIdx.x == 0) out[(long)b * N + n] = acc;
-}
-
 static int plade_validate(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
                           const float* dl, const float* ray) {
   PD_REQUIRE(B > 0 && B <= 65535 && N >= 2 && H > 0 && W > 0, "bad shape (alpha compositing needs N >= 2 planes)");
@@ -321,8 +311,7 @@ extern "C" int pd_plade_tail_bwd(int B, int N, int H, int W, int flags, const fl
                     g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
   if (int rc = check_launch("plade_bwd_kernel")) return rc;
   if (reduce) {
-    plade_reduce_kernel<<<dim3(N, B), kWave, 0, (hipStream_t)stream>>>(workspace, g_disp_layered, (int)grid.x, N);
-    return check_launch("plade_reduce_kernel");
+    return reduce_partials(workspace, g_disp_layered, (int)grid.x, N, B, (hipStream_t)stream);
   }
   return 0;
 }

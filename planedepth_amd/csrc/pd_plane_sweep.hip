@@ -7,11 +7,11 @@
 // planes with an online softmax, so HBM sees logits+sigma once per pass and nothing else of size N*HW.
 //
 // Kernels in this file (general path; the row-shift specialisation of the backward lives in
-// pd_plane_sweep_rowshift.hip):
+// pd_plane_sweep_rowshift.hip), and the host side of every family: sweep_route, the C ABI's entry points and queries:
 //   sweep_fwd_kernel      one pass over N: rgb_rec, ph_map, stash (lse, S, Mx, automask flag, mask bits)
 //   sweep_bwd_kernel      one pass over N: re-sample, per-plane gradients, atomic scatter to g_logits/g_sigma,
 //                         block-reduced plane-parameter gradient partials
-//   reduce_partials_kernel  deterministic second stage for the plane-parameter gradient
+//   (the deterministic second stage of the plane-parameter gradient is pd_common.hip's reduce_partials, as for every family)
 //   sweep_layers_kernel   optional materialisation of the per-plane tensors the reference stores in `outputs`
 #include <stdlib.h>
 
@@ -256,21 +256,6 @@ __global__ __launch_bounds__(kBlock) void sweep_bwd_kernel(SweepArgs a, BwdOut o
   }
 }
 
-// partials [B][nblk][M] -> out [B][M], summed in a fixed order (deterministic)
-__global__ void reduce_partials_kernel(const float* __restrict__ partials, float* __restrict__ out, int nblk, int M) {
-  const int j = blockIdx.x, b = blockIdx.y;  // one wave per output element; lanes stride over the blocks
-  const float* p = partials + (long)b * nblk * M + j;
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < nblk; i += kWave) acc += p[(long)i * M];
-  acc = wave_sum(acc);
-  if (threadIdx.x == 0) out[(long)b * M + j] = acc;
-}
-
-int reduce_partials(const float* partials, float* out, int nblk, int M, int B, hipStream_t stream) {
-  reduce_partials_kernel<<<dim3(M, B), kWave, 0, stream>>>(partials, out, nblk, M);
-  return check_launch("reduce_partials_kernel");
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Per-plane tensors of trainer.py:582-602 (forward values only)
 // ---------------------------------------------------------------------------------------------------------------
@@ -464,32 +449,86 @@ static SweepArgs make_args(const pd_sweep_desc* d, const float* src, const float
 
 extern "C" float pd_sweep_auto_row_eps(void) { return auto_row_eps(); }
 
-static bool wants_rowshift(const pd_sweep_desc* d) {
-  return d->impl == PD_IMPL_AUTO || d->impl == PD_IMPL_FAST_ROWS || d->impl == PD_IMPL_ROWS1 || d->impl == PD_IMPL_UNIFORM_DIRECT ||
-         d->impl == PD_IMPL_EXACT_ROWS;
+// ---- the route: which kernel family serves a call (pd_sweep.h) ---------------------------------------------------------
+// Today's order of preference, per direction.  Row kernels (disp mode, one disparity per plane or row) where `impl` allows
+// them and the shape fits: the stream kernels unless PD_IMPL_ROWS1 asks for the plane-group / target-ordered pair or a
+// per-pixel mask, PD_RENDER_PROB (backward), an odd width, an unaligned tensor (forward) or the LDS rule them out.  Else
+// homography mode: plane-uniform, or per plane the two-pass gather when somebody wants g_logits / g_sigma.  Else the
+// general kernels.
+SweepRoute pd::sweep_route(const pd_sweep_desc* d, const CallFacts& f) {
+  SweepRoute r{};
+  const int impl = d->impl;
+  const bool bf16 = (d->flags & PD_LOGITS_BF16) != 0;
+  const bool uniform = d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM);
+  // what validate() lets through.  A query may hand over less (W = 0): the stream forward's shape arithmetic divides by the
+  // row's segment count, so it is only asked about shapes an entry point could see
+  const bool shape_ok = d->B > 0 && d->N > 0 && d->H > 1 && d->W > 1;
+  const bool wants_rows = impl == PD_IMPL_AUTO || impl == PD_IMPL_FAST_ROWS || impl == PD_IMPL_ROWS1 ||
+                          impl == PD_IMPL_UNIFORM_DIRECT || impl == PD_IMPL_EXACT_ROWS;
+  // PD_IMPL_ROWS1 keeps the plane-group row-shift forward and the target-ordered row-shift backward (cross-check, A/B)
+  const bool stream_ok = impl != PD_IMPL_ROWS1;
+  r.rowshift_fits = rowshift_applicable(d);
+  r.gather_fits = gather_bwd_applicable(d);
+  r.rows = wants_rows && r.rowshift_fits;
+  r.accumulates = !r.rows;   // the row kernels' owner-computes ring stores have no read-modify-write form; the plane-uniform
+                             // and gather stores do, and the atomic scatter accumulates by nature
+  r.tail_fuses = r.rows && stream_ok && rowstream_bwd_tail_applicable(d, f.per_pixel_mask);
+  r.fwd_err = r.bwd_err = PD_ERR_UNSUPPORTED;
+
+  if (r.rows) {
+    // default for the headline shape: one wave per 128-pixel segment streams over the planes (pd_plane_sweep_fwdstream.hip);
+    // unaligned tensors take the one-pixel-per-lane forward, which reads fp32 only
+    const bool stream = stream_ok && shape_ok && fwdstream_applicable(d, f.per_pixel_mask, f.dists_aligned);
+    r.fwd = (stream && f.pixels_aligned) ? FwdFamily::SegmentStream : FwdFamily::RowShift;
+    if (bf16 && r.fwd == FwdFamily::RowShift) {
+      r.fwd = FwdFamily::Unsupported;
+      r.fwd_err = stream ? PD_ERR_UNSUPPORTED : PD_ERR_ARG;   // (not `stream`: validate() refused it)
+      r.fwd_why = stream ? "PD_LOGITS_BF16: tgt / src / rgb_rec / ph_map / stash must be 8-byte aligned"
+                         : "PD_LOGITS_BF16: the segment-stream forward does not apply";
+    }
+    // default: lanes own aligned source slots, waves stream along plane rows (pd_plane_sweep_rowstream.hip); else the
+    // target-ordered row-shift backward, which needs less LDS
+    r.bwd = f.tail ? (r.tail_fuses ? BwdFamily::RowStreamTail : BwdFamily::Unsupported)
+            : (stream_ok && rowstream_bwd_applicable(d, f.per_pixel_mask)) ? BwdFamily::RowStream : BwdFamily::RowShift;
+    if (bf16 && r.bwd == BwdFamily::RowShift) {   // (validate() refused it)
+      r.bwd = BwdFamily::Unsupported; r.bwd_err = PD_ERR_ARG;
+      r.bwd_why = "PD_LOGITS_BF16: the row-stream backward does not apply";
+    }
+  } else {
+    r.fwd = uniform ? FwdFamily::Uniform : FwdFamily::General;
+    // one homography per plane: two passes, no atomics (pd_plane_sweep_gather.hip) where somebody wants g_logits / g_sigma
+    r.bwd = (f.tail || (!uniform && impl == PD_IMPL_TILE)) ? BwdFamily::Unsupported : uniform ? BwdFamily::Uniform
+            : (r.gather_fits && f.wants_grads) ? BwdFamily::Gather : BwdFamily::Scatter;
+  }
+  if (r.bwd == BwdFamily::Unsupported && !r.bwd_why)
+    r.bwd_why = f.tail ? "pd_plane_sweep_bwd_tail: not served for this descriptor (pd_sweep_bwd_tail_fuses)"
+                       : "PD_IMPL_TILE (the owned-tile backward) was removed: it was slower than the default kernels";
+  const bool streams = r.bwd == BwdFamily::RowStream || r.bwd == BwdFamily::RowStreamTail;
+  r.plane_adds = streams && !(d->flags & (PD_DISP_ROWS | PD_DISP_DENSE));
+  // both kernels that read bf16 run (hence: row kernels, not PD_IMPL_ROWS1); PD_IMPL_UNIFORM_DIRECT is a homography cross-check
+  r.serves_bf16 = bf16 && !(d->flags & PD_HOMO_UNIFORM) && impl != PD_IMPL_UNIFORM_DIRECT &&
+                  r.fwd == FwdFamily::SegmentStream && r.bwd == BwdFamily::RowStream;
+  return r;
 }
 
-extern "C" int pd_sweep_uses_rowshift(const pd_sweep_desc* d) {
-  return (d && wants_rowshift(d) && rowshift_applicable(d)) ? 1 : 0;
-}
+// The capability queries: the route of a call with no per-pixel mask, aligned tensors and gradients wanted.
+static SweepRoute query_route(const pd_sweep_desc* d) { return sweep_route(d, assumed_facts()); }
+
+extern "C" int pd_sweep_uses_rowshift(const pd_sweep_desc* d) { return (d && query_route(d).rows) ? 1 : 0; }
 
 extern "C" int pd_sweep_native_bf16(const pd_sweep_desc* d) {
-  if (!d || d->mode != PD_WARP_DISP || (d->flags & (PD_RENDER_PROB | PD_DISP_DENSE | PD_HOMO_UNIFORM))) return 0;
-  if (!(d->impl == PD_IMPL_AUTO || d->impl == PD_IMPL_FAST_ROWS || d->impl == PD_IMPL_EXACT_ROWS)) return 0;
-  if (d->B <= 0 || d->N <= 0 || d->H <= 1 || d->W <= 1 || d->W % 2 != 0 || !rowshift_applicable(d)) return 0;
+  if (!d) return 0;
   pd_sweep_desc q = *d;
   q.flags |= PD_LOGITS_BF16;   // (the row-stream backward's LDS grows under the flag)
-  SweepArgs probe{};
-  probe.has_mask = 0;
-  return (fwdstream_applicable(&q, probe) && rowstream_bwd_applicable(&q, probe)) ? 1 : 0;
+  return query_route(&q).serves_bf16 ? 1 : 0;
 }
 
-extern "C" int pd_sweep_bwd_accumulates(const pd_sweep_desc* d) {
-  if (!d) return 0;
-  if (wants_rowshift(d) && rowshift_applicable(d)) return 0;   // owner-computes ring stores: no read-modify-write form
-  if (d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM)) return 1;
-  return 1;                                                    // the atomic scatter accumulates by nature
-}
+extern "C" int pd_sweep_bwd_accumulates(const pd_sweep_desc* d) { return (d && query_route(d).accumulates) ? 1 : 0; }
+
+// (the caller passes no per-pixel mask when it relies on this: pd_plane_sweep_bwd falls back to overwriting otherwise)
+extern "C" int pd_sweep_bwd_plane_adds(const pd_sweep_desc* d) { return (d && query_route(d).plane_adds) ? 1 : 0; }
+
+extern "C" int pd_sweep_bwd_tail_fuses(const pd_sweep_desc* d) { return (d && query_route(d).tail_fuses) ? 1 : 0; }
 
 extern "C" size_t pd_sweep_stash_floats(const pd_sweep_desc* d) {
   if (!d) return 0;
@@ -500,13 +539,17 @@ extern "C" size_t pd_sweep_stash_floats(const pd_sweep_desc* d) {
 // workgroups of the general backward: four waves of 63 pixels + 1 ghost lane each
 static int bwd_blocks(int HW) { return ceil_div(HW, (kBlock / kWave) * (kWave - 1)); }
 
+// The MAXIMUM over every family whose own limits admit the descriptor, not the routed family's figure: the caller sizes one
+// buffer before the call's facts are known (a per-pixel mask or nobody wanting g_logits / g_sigma moves a call to another
+// family), and callers that cross-check families through `impl` have always got the row kernels' figure in disp mode.
 extern "C" size_t pd_sweep_bwd_workspace_floats(const pd_sweep_desc* d) {
   if (!d) return 0;
+  const SweepRoute r = query_route(d);
   const size_t K = (d->mode == PD_WARP_DISP) ? 1 : 9;
   const size_t general = (size_t)d->B * bwd_blocks(d->H * d->W) * d->N * K;
-  const size_t rows = rowshift_applicable(d) ? rowshift_bwd_workspace_floats(d) : 0;
+  const size_t rows = r.rowshift_fits ? rowshift_bwd_workspace_floats(d) : 0;
   const size_t uni = (d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM)) ? uniform_bwd_workspace_floats(d) : 0;
-  const size_t gat = gather_bwd_applicable(d) ? gather_bwd_workspace_floats(d) : 0;
+  const size_t gat = r.gather_fits ? gather_bwd_workspace_floats(d) : 0;
   size_t m = general > rows ? general : rows;
   m = m > gat ? m : gat;
   return m > uni ? m : uni;
@@ -538,15 +581,19 @@ extern "C" int pd_plane_sweep_fwd(const pd_sweep_desc* d, const float* src, cons
     if (!(d->flags & PD_PH_MEAN_ZEROED) &&
         hipMemsetAsync(ph_mean, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) return check_launch("hipMemsetAsync");
   }
-  if (wants_rowshift(d) && rowshift_applicable(d)) {
-    // default for the headline shape: one wave per 128-pixel segment streams over the planes (pd_plane_sweep_fwdstream.hip);
-    // PD_IMPL_ROWS1 keeps the plane-group row-shift forward (cross-check, A/B)
-    if (d->impl != PD_IMPL_ROWS1 && fwdstream_applicable(d, a)) return fwdstream_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
-    PD_REQUIRE(!(d->flags & PD_LOGITS_BF16), "PD_LOGITS_BF16: the segment-stream forward does not apply");   // (validate() refused it)
-    return rowshift_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
+  CallFacts f = assumed_facts();
+  f.per_pixel_mask = a.has_mask != 0;
+  f.pixels_aligned = !((reinterpret_cast<uintptr_t>(tgt) | reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(rgb_rec) |
+                        reinterpret_cast<uintptr_t>(ph_map) | reinterpret_cast<uintptr_t>(stash)) & 7);
+  f.dists_aligned = !(reinterpret_cast<uintptr_t>(dists) & 7);
+  const SweepRoute r = sweep_route(d, f);
+  switch (r.fwd) {
+    case FwdFamily::SegmentStream: return fwdstream_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
+    case FwdFamily::RowShift: return rowshift_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
+    case FwdFamily::Uniform: return uniform_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
+    case FwdFamily::Unsupported: set_error("%s", r.fwd_why); return r.fwd_err;
+    case FwdFamily::General: break;
   }
-  if (d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM))
-    return uniform_fwd(d, a, rgb_rec, ph_map, stash, (hipStream_t)stream);
   dim3 grid(ceil_div(d->H * d->W, kBlock), d->B);
   PD_DISPATCH(sweep_fwd_kernel, d->mode, (d->flags & PD_MIXTURE) != 0, grid, dim3(kBlock), 0, (hipStream_t)stream, a,
               rgb_rec, ph_map, stash);
@@ -571,7 +618,13 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   hipStream_t stream = (hipStream_t)stream_;
   const bool mix = (d->flags & PD_MIXTURE) != 0;
   const bool accumulate = (d->flags & PD_BWD_ACCUMULATE) != 0;
-  PD_REQUIRE(!accumulate || pd_sweep_bwd_accumulates(d), "PD_BWD_ACCUMULATE is not served for this descriptor (pd_sweep_bwd_accumulates)");
+  SweepArgs ak = make_args(d, src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists);
+  CallFacts f = assumed_facts();
+  f.per_pixel_mask = ak.has_mask != 0;
+  f.wants_grads = g_logits || g_sigma;
+  f.tail = tail != nullptr;
+  const SweepRoute r = sweep_route(d, f);
+  PD_REQUIRE(!accumulate || r.accumulates, "PD_BWD_ACCUMULATE is not served for this descriptor (pd_sweep_bwd_accumulates)");
   if (d->flags & PD_LOGITS_BF16) {
     if (tail) {
       set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_bwd_tail");
@@ -580,43 +633,28 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
     PD_REQUIRE(!((reinterpret_cast<uintptr_t>(g_logits) | reinterpret_cast<uintptr_t>(g_sigma)) & 3),
                "PD_LOGITS_BF16: g_logits / g_sigma must be 4-byte aligned");
   }
-  SweepArgs ak = make_args(d, src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists);
   BwdOut o;
   o.g_logits = g_logits; o.g_sigma = mix ? g_sigma : nullptr; o.g_plane = g_plane; o.partials = workspace;
   o.side = nullptr; o.scratch = nullptr;
   o.g_dists = (d->flags & PD_RENDER_PROB) ? g_dists : nullptr;
   o.rgb_rec = rgb_rec; o.stash = stash; o.g_rgb_rec = g_rgb_rec; o.g_ph_map = g_ph_map; o.g_ph_mean = g_ph_mean;
-  if (wants_rowshift(d) && rowshift_applicable(d)) {
-    PD_REQUIRE(workspace, "the row-shift backward needs workspace (pd_sweep_bwd_workspace_floats)");
-    // default: lanes own aligned source slots, waves stream along plane rows (pd_plane_sweep_rowstream.hip);
-    // PD_IMPL_ROWS1 keeps the target-ordered row-shift backward (cross-check, A/B)
-    if (tail) {   // pd_plane_sweep_bwd_tail: the row-stream backward with the decoder tail's backward riding along
-      if (d->impl == PD_IMPL_ROWS1 || !rowstream_bwd_tail_applicable(d, ak)) {
-        set_error("pd_plane_sweep_bwd_tail: not served for this descriptor (pd_sweep_bwd_tail_fuses)");
-        return PD_ERR_UNSUPPORTED;
-      }
+  if (r.rows) PD_REQUIRE(workspace, "the row-shift backward needs workspace (pd_sweep_bwd_workspace_floats)");
+  switch (r.bwd) {
+    case BwdFamily::Unsupported: set_error("%s", r.bwd_why); return r.bwd_err;
+    case BwdFamily::RowStreamTail:   // pd_plane_sweep_bwd_tail: the row-stream backward with the decoder tail's backward riding along
       PD_REQUIRE(g_logits && g_sigma, "pd_plane_sweep_bwd_tail writes both g_raw_logits and g_raw_sigma");
       o.tail_raw_sigma = tail->raw_sigma; o.tail_stash = tail->stash; o.tail_disp = tail->disp;
       o.tail_g_disp = tail->g_disp; o.tail_g_depth = tail->g_depth;
       return rowstream_bwd(d, ak, o, stream);
-    }
-    if (d->impl != PD_IMPL_ROWS1 && rowstream_bwd_applicable(d, ak)) return rowstream_bwd(d, ak, o, stream);
-    PD_REQUIRE(!(d->flags & PD_LOGITS_BF16), "PD_LOGITS_BF16: the row-stream backward does not apply");   // (validate() refused it)
-    return rowshift_bwd(d, ak, o, stream);
+    case BwdFamily::RowStream: return rowstream_bwd(d, ak, o, stream);
+    case BwdFamily::RowShift: return rowshift_bwd(d, ak, o, stream);
+    case BwdFamily::Uniform:
+      PD_REQUIRE(workspace, "the plane-uniform backward needs workspace (pd_sweep_bwd_workspace_floats)");
+      return uniform_bwd(d, ak, o, workspace, stream);
+    case BwdFamily::Gather:
+    case BwdFamily::Scatter: break;
   }
-  if (tail) {
-    set_error("pd_plane_sweep_bwd_tail: not served for this descriptor (pd_sweep_bwd_tail_fuses)");
-    return PD_ERR_UNSUPPORTED;
-  }
-  if (d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM)) {
-    PD_REQUIRE(workspace, "the plane-uniform backward needs workspace (pd_sweep_bwd_workspace_floats)");
-    return uniform_bwd(d, ak, o, workspace, stream);
-  }
-  if (d->impl == PD_IMPL_TILE) {
-    set_error("PD_IMPL_TILE (the owned-tile backward) was removed: it was slower than the default kernels");
-    return PD_ERR_UNSUPPORTED;
-  }
-  if (gather_bwd_applicable(d) && (g_logits || g_sigma)) {   // one homography per plane: two passes, no atomics (pd_plane_sweep_gather.hip)
+  if (r.bwd == BwdFamily::Gather) {
     PD_REQUIRE(workspace, "the gather backward needs workspace (pd_sweep_bwd_workspace_floats)");
     const GatherPlan gp = gather_bwd_plan(d, workspace);
     o.partials = gp.partials; o.scratch = gp.scratch;
@@ -630,9 +668,7 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
     if (rc) return rc;
     rc = gather_bwd_finish(d, ak, o, gp, stream);
     if (rc || !g_plane) return rc;
-    const int M = d->N * 9;
-    reduce_partials_kernel<<<dim3(M, d->B), kWave, 0, stream>>>(gp.partials, g_plane, gp.nblk, M);
-    return check_launch("reduce_partials_kernel");
+    return reduce_partials(gp.partials, g_plane, gp.nblk, d->N * 9, d->B, stream);
   }
   const size_t plane_bytes = (size_t)d->B * d->N * d->H * d->W * sizeof(float);
   const int HW = d->H * d->W;
@@ -645,11 +681,7 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   PD_DISPATCH(sweep_bwd_kernel, d->mode, mix, grid, dim3(kBlock), shmem, stream, ak, o);
   rc = check_launch("sweep_bwd_kernel");
   if (rc) return rc;
-  if (g_plane && !dense) {
-    const int M = d->N * K;
-    reduce_partials_kernel<<<dim3(M, d->B), kWave, 0, stream>>>(workspace, g_plane, grid.x, M);
-    rc = check_launch("reduce_partials_kernel");
-  }
+  if (g_plane && !dense) rc = reduce_partials(workspace, g_plane, grid.x, d->N * K, d->B, stream);
   return rc;
 }
 
@@ -661,20 +693,6 @@ extern "C" int pd_plane_sweep_bwd(const pd_sweep_desc* d, const float* src, cons
                                   float* g_dists, float* workspace, pd_stream_t stream) {
   return sweep_bwd_impl(d, src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists, rgb_rec, stash, g_rgb_rec,
                         g_ph_map, g_ph_mean, g_logits, g_sigma, g_plane, g_dists, workspace, stream, nullptr);
-}
-
-extern "C" int pd_sweep_bwd_plane_adds(const pd_sweep_desc* d) {
-  if (!d || !(wants_rowshift(d) && rowshift_applicable(d)) || d->impl == PD_IMPL_ROWS1 || (d->flags & (PD_DISP_ROWS | PD_DISP_DENSE))) return 0;
-  SweepArgs probe;
-  probe.has_mask = 0;   // (the caller passes no per-pixel mask when it relies on this: pd_plane_sweep_bwd falls back to overwriting otherwise)
-  return rowstream_bwd_applicable(d, probe) ? 1 : 0;
-}
-
-extern "C" int pd_sweep_bwd_tail_fuses(const pd_sweep_desc* d) {
-  if (!d || !(wants_rowshift(d) && rowshift_applicable(d)) || d->impl == PD_IMPL_ROWS1) return 0;
-  SweepArgs probe;
-  probe.has_mask = 0;
-  return rowstream_bwd_tail_applicable(d, probe) ? 1 : 0;
 }
 
 extern "C" int pd_plane_sweep_bwd_tail(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits,
@@ -717,7 +735,7 @@ static int validate_pair(const pd_sweep_desc* d, const float* src, const float* 
     set_error("PD_LOGITS_BF16: not served by the pair entry points");
     return PD_ERR_UNSUPPORTED;
   }
-  PD_REQUIRE(d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM), "the pair entry points serve PD_HOMO_UNIFORM views");
+  PD_REQUIRE(query_route(d).fwd == FwdFamily::Uniform, "the pair entry points serve PD_HOMO_UNIFORM views");
   for (const pd_sweep_view* v : {va, vb}) {
     const int rc = validate(d, src, logits, sigma, v->plane, v->plane_aux, v->inv_K3, v->padding_mask);
     if (rc) return rc;

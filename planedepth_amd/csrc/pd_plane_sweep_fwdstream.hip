@@ -661,24 +661,16 @@ static FsOrder fwdstream_order(const pd_sweep_desc* d, const FsShape& sh, float 
   return o;
 }
 
-bool fwdstream_applicable(const pd_sweep_desc* d, const SweepArgs& a) {
-  if (!rowshift_applicable(d) || a.has_mask) return false;
-  if ((d->flags & PD_RENDER_PROB) && (((long)d->H * d->W) % 2 != 0 || (reinterpret_cast<uintptr_t>(a.dists) & 7))) return false;
-  // pixel pairs: even width, 8-byte aligned rows of the per-pixel tensors (their bases come 8-byte aligned from any allocator
-  // that hands out float2-aligned memory; checked because the boundary takes raw pointers)
+bool fwdstream_applicable(const pd_sweep_desc* d, bool per_pixel_mask, bool dists_aligned) {
+  if (!rowshift_applicable(d) || per_pixel_mask) return false;
+  if ((d->flags & PD_RENDER_PROB) && (((long)d->H * d->W) % 2 != 0 || !dists_aligned)) return false;
+  // pixel pairs: even width; the 8-byte alignment of the per-pixel tensors is a fact of the call (sweep_route: their bases come
+  // 8-byte aligned from any allocator that hands out float2-aligned memory; checked because the boundary takes raw pointers)
   if (d->W % 2 != 0) return false;
   return fwdstream_shape(d).lds <= device_lds_bytes();
 }
 
 int fwdstream_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, float* ph_map, float* stash, hipStream_t stream) {
-  if ((reinterpret_cast<uintptr_t>(a.tgt) | reinterpret_cast<uintptr_t>(a.src) | reinterpret_cast<uintptr_t>(rgb_rec) |
-       reinterpret_cast<uintptr_t>(ph_map) | reinterpret_cast<uintptr_t>(stash)) & 7) {
-    if (d->flags & PD_LOGITS_BF16) {   // (the one-pixel-per-lane forward reads fp32 only)
-      set_error("PD_LOGITS_BF16: tgt / src / rgb_rec / ph_map / stash must be 8-byte aligned");
-      return PD_ERR_UNSUPPORTED;
-    }
-    return rowshift_fwd(d, a, rgb_rec, ph_map, stash, stream);   // unaligned tensors: the one-pixel-per-lane forward
-  }
   const FsShape sh = fwdstream_shape(d);
   const dim3 grid(sh.nbk * sh.cblocks, 1), block(sh.segs * sh.rows * kWave);
   const FsRows rowtab = fwdstream_rows(d->H, sh.rows, a.row_eps);

@@ -394,16 +394,6 @@ __global__ __launch_bounds__(kRowThreadsMax, PD_BWD_OCC) void rowshift_bwd_kerne
   else                rowshift_bwd_body<MIX, HASMASK, 1, RENDER>(a, o, row, sdisp, kshift, red, bnd, lds4);
 }
 
-// partials [B][R][M] -> out [B][M]; one wave per (b, j): lanes stride over R, then wave-reduce.  Deterministic.
-__global__ void reduce_rows_kernel(const float* __restrict__ partials, float* __restrict__ out, int R, int M) {
-  const int j = blockIdx.x, b = blockIdx.y;
-  const float* p = partials + (long)b * R * M + j;
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < R; i += kWave) acc += p[(long)i * M];
-  acc = wave_sum(acc);
-  if (threadIdx.x == 0) out[(long)b * M + j] = acc;
-}
-
 // Device self-check used by the tests: div_by(refined reciprocal) == IEEE division, bit for bit.
 __global__ void div_check_kernel(float Wm1, int count, float lo, float step, int* __restrict__ mismatches) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -503,8 +493,7 @@ int rowshift_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o_in,
   }
   int rc = check_launch("rowshift_bwd_kernel");
   if (rc || !o.g_plane || (d->flags & PD_DISP_ROWS)) return rc;
-  reduce_rows_kernel<<<dim3(d->N, d->B), kWave, 0, stream>>>(o.partials, o.g_plane, d->H, d->N);
-  return check_launch("reduce_rows_kernel");
+  return reduce_partials(o.partials, o.g_plane, d->H, d->N, d->B, stream);
 }
 
 }  // namespace pd

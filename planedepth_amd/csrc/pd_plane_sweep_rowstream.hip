@@ -738,15 +738,6 @@ __global__ __launch_bounds__(kStreamThreadsMax, (TAIL || sizeof(T) == 2) ? 6 : P
   else                stream_body<T, MIX, 1, PK, TAIL>(a, o, b, y, row, L);
 }
 
-__global__ void reduce_rows_stream_kernel(const float* __restrict__ partials, float* __restrict__ out, int R, int M) {
-  const int j = blockIdx.x, b = blockIdx.y;   // partials [B][R][M] -> out [B][M]; lanes stride over R; deterministic
-  const float* p = partials + (long)b * R * M + j;
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < R; i += kWave) acc += p[(long)i * M];
-  acc = wave_sum(acc);
-  if (threadIdx.x == 0) out[(long)b * M + j] = acc;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
@@ -779,8 +770,8 @@ static StreamShape rowstream_shape(const pd_sweep_desc* d, bool tail = false) {
   return s;
 }
 
-bool rowstream_bwd_applicable(const pd_sweep_desc* d, const SweepArgs& a) {
-  return rowshift_applicable(d) && !(d->flags & PD_RENDER_PROB) && !a.has_mask && (d->W % 2 == 0) &&
+bool rowstream_bwd_applicable(const pd_sweep_desc* d, bool per_pixel_mask) {
+  return rowshift_applicable(d) && !(d->flags & PD_RENDER_PROB) && !per_pixel_mask && (d->W % 2 == 0) &&
          rowstream_shape(d).lds <= device_lds_bytes();   // else: the row-shift backward, which needs less
 }
 
@@ -797,8 +788,8 @@ static int rowstream_launch(const SweepArgs& a, const BwdOut& o, dim3 grid, dim3
 
 // The fused decoder tail rides along (pd_plane_sweep_bwd_tail) where the plain LDS layout with one more float4 per cell fits:
 // mixture, one disparity per plane, unit sign.
-bool rowstream_bwd_tail_applicable(const pd_sweep_desc* d, const SweepArgs& a) {
-  return rowstream_bwd_applicable(d, a) && (d->flags & PD_MIXTURE) && !(d->flags & (PD_DISP_ROWS | PD_MASK_ROWS)) &&
+bool rowstream_bwd_tail_applicable(const pd_sweep_desc* d, bool per_pixel_mask) {
+  return rowstream_bwd_applicable(d, per_pixel_mask) && (d->flags & PD_MIXTURE) && !(d->flags & (PD_DISP_ROWS | PD_MASK_ROWS)) &&
          (d->sign == 1.0f || d->sign == -1.0f) && rowstream_shape(d, true).lds <= device_lds_bytes();
 }
 
@@ -821,8 +812,7 @@ int rowstream_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, h
   if (rc) return rc;
   rc = check_launch("rowstream_bwd_kernel");
   if (rc || !o.g_plane || (d->flags & (PD_DISP_ROWS | PD_BWD_PLANE_ZEROED))) return rc;
-  reduce_rows_stream_kernel<<<dim3(d->N, d->B), kWave, 0, stream>>>(o.partials, o.g_plane, d->H, d->N);
-  return check_launch("reduce_rows_kernel");
+  return reduce_partials(o.partials, o.g_plane, d->H, d->N, d->B, stream);
 }
 
 }  // namespace pd

@@ -887,16 +887,6 @@ __global__ __launch_bounds__(kStageThreads) void uniform_bwd_pass2_pair_kernel(P
   }
 }
 
-// partials [B][nblk][M] of the first pass -> out [B][M]
-__global__ void uniform_reduce_kernel(const float* __restrict__ partials, int nblk, float* __restrict__ out, int M) {
-  const int j = blockIdx.x, b = blockIdx.y;
-  const float* p = partials + (long)b * nblk * M + j;
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < nblk; i += kWave) acc += p[(long)i * M];
-  acc = wave_sum(acc);
-  if (threadIdx.x == 0) out[(long)b * M + j] = acc;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
@@ -991,8 +981,7 @@ int uniform_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, flo
   }
   rc = check_launch("uniform_bwd_pass kernels");
   if (rc || !o.g_plane) return rc;
-  uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(part_two, nblk, o.g_plane, kUniG * 9);
-  return check_launch("uniform_reduce_kernel");
+  return reduce_partials(part_two, o.g_plane, nblk, kUniG * 9, d->B, stream);
 }
 
 int uniform_gather_pair(const pd_sweep_desc* d, const float* plane_a, const float* inv_K3_a, float* workspace_a,
@@ -1055,9 +1044,9 @@ int uniform_bwd_pair(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o
     rc = uniform_gather_pair(d, a.plane, a.inv_K3, workspace_a, b.plane, b.inv_K3, workspace_b, g_logits, g_sigma, stream);
     if (rc) return rc;
   }
-  if (oa.g_plane) uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(wa.part_two, nblk, oa.g_plane, kUniG * 9);
-  if (ob.g_plane) uniform_reduce_kernel<<<dim3(kUniG * 9, d->B), kWave, 0, stream>>>(wb.part_two, nblk, ob.g_plane, kUniG * 9);
-  return check_launch("uniform_reduce_kernel");
+  if (oa.g_plane) rc = reduce_partials(wa.part_two, oa.g_plane, nblk, kUniG * 9, d->B, stream);
+  if (!rc && ob.g_plane) rc = reduce_partials(wb.part_two, ob.g_plane, nblk, kUniG * 9, d->B, stream);
+  return rc;
 }
 
 }  // namespace pd

@@ -254,6 +254,39 @@ __device__ __forceinline__ PlaneGrad plane_grad(const PixelCtx& c, float l, floa
   return g;
 }
 
+// ---- host side: which kernel family serves a call -----------------------------------------------------------------
+// What the decision may depend on besides the descriptor.
+struct CallFacts {
+  bool per_pixel_mask;  // disp mode with a [B,N,H,W] padding mask (not PD_MASK_ROWS): its bits travel in the stash words
+  bool pixels_aligned;  // forward: tgt / src / rgb_rec / ph_map / stash are 8-byte aligned (pixel pairs)
+  bool dists_aligned;   // PD_RENDER_PROB: dists is 8-byte aligned
+  bool wants_grads;     // backward: g_logits or g_sigma is asked for (else the gather's two passes have nothing to write)
+  bool tail;            // pd_plane_sweep_bwd_tail: the decoder tail's backward rides along
+};
+// A capability query has no call at hand: no per-pixel mask, aligned tensors, gradients wanted, no tail.
+inline CallFacts assumed_facts() { return CallFacts{false, true, true, true, false}; }
+
+enum class FwdFamily { General, Uniform, RowShift, SegmentStream, Unsupported };
+enum class BwdFamily { Scatter, Gather, Uniform, RowShift, RowStream, RowStreamTail, Unsupported };
+
+struct SweepRoute {
+  FwdFamily fwd;
+  BwdFamily bwd;
+  int fwd_err, bwd_err;   // Unsupported: the code to return (PD_ERR_UNSUPPORTED, or PD_ERR_ARG where validate() refused
+  const char* fwd_why;    // the call already) and the text for set_error
+  const char* bwd_why;
+  bool rows;              // served by the row kernels of disp mode (pd_sweep_uses_rowshift)
+  bool accumulates;       // the backward honours PD_BWD_ACCUMULATE (pd_sweep_bwd_accumulates)
+  bool plane_adds;        // ... adds the plane gradient into a zeroed block under PD_BWD_PLANE_ZEROED (pd_sweep_bwd_plane_adds)
+  bool tail_fuses;        // ... can take the decoder tail along (pd_sweep_bwd_tail_fuses)
+  bool serves_bf16;       // d->flags has PD_LOGITS_BF16 and both kernels that read bf16 serve it (pd_sweep_native_bf16 sets the flag)
+  bool rowshift_fits, gather_fits;   // the families' own limits whatever `impl` asks for: what pd_sweep_bwd_workspace_floats sizes for
+};
+// The one place where descriptor + call facts become a kernel family (pd_plane_sweep.hip).  The dispatchers switch on the
+// family, the capability queries return a field.
+SweepRoute sweep_route(const pd_sweep_desc* d, const CallFacts& f);
+
+// The per-family predicates own their family's LDS and shape limits; only sweep_route asks them.
 // Row-shift specialisation (pd_plane_sweep_rowshift.hip): disp mode, per-plane scalar disparities.
 bool rowshift_applicable(const pd_sweep_desc* d);
 int rowshift_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, float* ph_map, float* stash,
@@ -263,12 +296,12 @@ size_t rowshift_bwd_workspace_floats(const pd_sweep_desc* d);
 
 // Segment-stream forward (pd_plane_sweep_fwdstream.hip): one wave per 128-pixel segment of a target row, two pixels per
 // lane, one plane per iteration behind a deep register ring of 12-byte tap loads.
-bool fwdstream_applicable(const pd_sweep_desc* d, const SweepArgs& a);
+bool fwdstream_applicable(const pd_sweep_desc* d, bool per_pixel_mask, bool dists_aligned);
 int fwdstream_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, float* ph_map, float* stash, hipStream_t stream);
 
 // Row-stream backward (pd_plane_sweep_rowstream.hip): lanes own aligned source slots, waves stream along plane rows.
-bool rowstream_bwd_applicable(const pd_sweep_desc* d, const SweepArgs& a);
-bool rowstream_bwd_tail_applicable(const pd_sweep_desc* d, const SweepArgs& a);
+bool rowstream_bwd_applicable(const pd_sweep_desc* d, bool per_pixel_mask);
+bool rowstream_bwd_tail_applicable(const pd_sweep_desc* d, bool per_pixel_mask);
 int rowstream_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, hipStream_t stream);
 size_t rowstream_bwd_workspace_floats(const pd_sweep_desc* d);
 
@@ -293,7 +326,5 @@ size_t uniform_bwd_workspace_floats(const pd_sweep_desc* d);
 int uniform_gather_pair(const pd_sweep_desc* d, const float* plane_a, const float* inv_K3_a, float* workspace_a,
                         const float* plane_b, const float* inv_K3_b, float* workspace_b, float* g_logits, float* g_sigma,
                         hipStream_t stream);
-// partials [B][nblk][M] -> out [B][M], fixed summation order (pd_plane_sweep.hip)
-int reduce_partials(const float* partials, float* out, int nblk, int M, int B, hipStream_t stream);
 
 }  // namespace pd

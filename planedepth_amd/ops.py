@@ -17,8 +17,8 @@ from ._buffers import (  # noqa: F401
     _timed, _desc, _contig, _ZERO_POOL, _zero_scalar, _ZERO_BLOCKS,
     _ZERO_BLOCK_FLOATS, _zero_block, _plane_grad_buffer)
 from .sweep import (  # noqa: F401
-    _sweep_forward, _sweep_forward_pair, _sweep_backward_pair, _sweep_backward, _sweep_backward_tail, _gather_pair,
-    TailLink, _GradTap, tail_taps, _PlaneSweep, _PER_SIDE, _MultiPlaneSweep,
+    SweepCall, SweepSaved, _sweep_forward, _sweep_forward_pair, _sweep_backward_pair, _sweep_backward, _sweep_backward_tail,
+    TailLink, _GradTap, tail_taps, _PlaneSweep, _SIDE_FIELDS, _PER_SIDE, _MultiPlaneSweep,
     plane_sweep_multi, as_f32, _storage_route, _flags, _SIGN, _per_plane_view, _FirstColumn, plane_sweep_disp,
     homography_matrices, _HomographyMatrices, homography_matrices_fused, plane_sweep_homography, _stereo_rows_sweep, plane_sweep_layers)
 from .tails import (  # noqa: F401
@@ -43,18 +43,20 @@ class _OpsModule(types.ModuleType):
     bench.py, monkeypatch) takes effect everywhere."""
 
     def __getattr__(self, name):
+        name = _state.ALIASES.get(name, name)
         if name in _state.SWITCHES:
             return getattr(_state, name)
         raise AttributeError("module %r has no attribute %r" % (self.__name__, name))
 
     def __setattr__(self, name, value):
+        name = _state.ALIASES.get(name, name)
         if name in _state.SWITCHES:
             setattr(_state, name, value)
         else:
             super().__setattr__(name, value)
 
     def __delattr__(self, name):
-        if name in _state.SWITCHES:
+        if name in _state.SWITCHES or name in _state.ALIASES:
             raise AttributeError("%s is a switch of planedepth_amd._state" % name)
         super().__delattr__(name)
 

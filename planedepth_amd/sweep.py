@@ -5,7 +5,8 @@ Every function launches hand-written HIP kernels through ctypes on torch's curre
 implementation behind these operators.
 """
 import ctypes
-import os
+import functools
+from typing import NamedTuple
 
 from . import _capi as C
 from . import _state as S
@@ -15,17 +16,77 @@ from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, 
 # ---------------------------------------------------------------------------------------------------------------------
 # Fused plane sweep + photometric loss
 # ---------------------------------------------------------------------------------------------------------------------
-def _sweep_forward(src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists, mode, flags, sign):
-    """One target view through pd_plane_sweep_fwd -> ((rgb_rec, ph_map, ph_mean[1]), tensors the backward needs)."""
+class SweepCall(NamedTuple):
+    """One target view's sweep: what ``plane_sweep_disp(..., defer=True)`` / ``plane_sweep_homography(..., defer=True)`` return,
+    what ``_PlaneSweep.apply(*call)`` takes.  ``link``: the fused decoder tail whose backward this sweep's backward applies
+    (single-view nodes only)."""
+    src: object
+    tgt: object
+    logits: object
+    sigma: object
+    plane: object
+    plane_aux: object
+    inv_K3: object
+    padding_mask: object
+    dists: object
+    mode: int
+    flags: int
+    sign: float
+    link: object = None
+
+
+# What a view's forward keeps for its backward (contiguous tensors or None).
+SweepSaved = NamedTuple("SweepSaved", [(k, object) for k in ("src", "tgt", "logits", "sigma", "plane", "plane_aux", "inv_K3",
+                                                              "padding_mask", "dists", "rgb_rec", "stash")])
+
+
+_GRAD_FIELDS = ("logits", "sigma", "plane", "dists")   # the inputs of ``_PlaneSweep.apply(*call)`` that can take a gradient
+_GRAD_AT = tuple(SweepCall._fields.index(k) for k in _GRAD_FIELDS)
+
+
+def _call_grads(*grads):
+    """backward()'s return value of ``_PlaneSweep``: ``grads`` (in _GRAD_FIELDS' order) at their inputs' places, None elsewhere."""
+    out = [None] * len(SweepCall._fields)
+    for i, g in zip(_GRAD_AT, grads):
+        out[i] = g
+    return tuple(out)
+
+
+def _scalar_grad(g_ph_mean):
+    """The upstream gradient of ph_mean as the kernels read it: a contiguous fp32 [1] (or None)."""
+    return None if g_ph_mean is None else g_ph_mean.reshape(1).to(torch.float32).contiguous()
+
+
+def _workspace(lib, d, device):
+    """Scratch of one backward call: partial sums of the plane-parameter gradient, the row-shift kernels' boundary spill,
+    the gather kernels' per-pixel gradients."""
+    return torch.empty(max(int(lib.pd_sweep_bwd_workspace_floats(ctypes.byref(d))), 1), device=device, dtype=torch.float32)
+
+
+def _forward_view(lib, call, first=None):
+    """What every forward does per view: argument checks, contiguous tensors, the descriptor, outputs and stash.  ``first``:
+    what this function returned for another view of the same src / logits / sigma and configuration (the pair forward) —
+    the shared tensors, the descriptor and the stash depth are taken from there instead of being checked and asked again.
+    Returns (descriptor, stash depth, SweepSaved, ph_map, ph_mean)."""
+    src, logits, sigma = call.src, call.logits, call.sigma
+    tgt, plane, plane_aux, inv_K3, padding_mask, dists = call.tgt, call.plane, call.plane_aux, call.inv_K3, call.padding_mask, call.dists
+    mode, flags, sign = call.mode, call.flags, call.sign
     S.LAST_SWEEP_FLAGS = flags
-    lib = C.load()
     B, N, H, W = logits.shape
-    edt = torch.bfloat16 if flags & C.PD_LOGITS_BF16 else torch.float32   # storage of logits / sigma and their gradients
-    C.require_gpu_tensor("logits", logits, dtype=edt)
-    C.require_gpu_tensor("src", src, (B, 3, H, W))
+    if first is None:
+        edt = torch.bfloat16 if flags & C.PD_LOGITS_BF16 else torch.float32   # storage of logits / sigma and their gradients
+        C.require_gpu_tensor("logits", logits, dtype=edt)
+        C.require_gpu_tensor("src", src, (B, 3, H, W))
+        if flags & C.PD_MIXTURE:
+            C.require_gpu_tensor("sigma", sigma, (B, N, H, W), dtype=edt)
+        src, logits, sigma = _contig(src), _contig(logits), _contig(sigma)
+        d = _desc(B, N, H, W, mode, flags, sign)
+        k = lib.pd_sweep_stash_floats(ctypes.byref(d)) // (H * W)
+        d.flags |= C.PD_PH_MEAN_ZEROED   # ph_mean is a pre-zeroed slot: the entry point then launches no memset
+    else:
+        d, k, shared, _, _ = first
+        src, logits, sigma = shared.src, shared.logits, shared.sigma
     C.require_gpu_tensor("tgt", tgt, (B, 3, H, W))
-    if flags & C.PD_MIXTURE:
-        C.require_gpu_tensor("sigma", sigma, (B, N, H, W), dtype=edt)
     if mode == C.PD_WARP_DISP:
         C.require_gpu_tensor("disp", plane, (B, N, H, W) if flags & C.PD_DISP_DENSE else
                              ((B, N, H) if flags & C.PD_DISP_ROWS else (B, N)))
@@ -41,128 +102,101 @@ def _sweep_forward(src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_ma
         C.require_gpu_tensor("dists", dists, (B, N - 1, H, W))
     else:
         dists = None
-    src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists = map(
-        _contig, (src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists))
-    d = _desc(B, N, H, W, mode, flags, sign)
-    k = lib.pd_sweep_stash_floats(ctypes.byref(d)) // (H * W)
-    rgb_rec = torch.empty(B, 3, H, W, device=logits.device, dtype=torch.float32)
-    ph_map = torch.empty(B, 1, H, W, device=logits.device, dtype=torch.float32)
-    ph_mean = _zero_scalar(logits.device)   # a pre-zeroed slot: the entry point then launches no memset (PD_PH_MEAN_ZEROED)
-    d.flags |= C.PD_PH_MEAN_ZEROED
-    stash = torch.empty(B, k, H, W, device=logits.device, dtype=torch.float32)
-    with C.on_device(logits.device), _timed("fwd"):
-        rc = lib.pd_plane_sweep_fwd(ctypes.byref(d), C.ptr(src), C.ptr(tgt), C.ptr(logits), C.ptr(sigma),
-                                    C.ptr(plane), C.ptr(plane_aux), C.ptr(inv_K3), C.ptr(padding_mask), C.ptr(dists),
-                                    C.ptr(rgb_rec), C.ptr(ph_map), C.ptr(ph_mean), C.ptr(stash),
-                                    C.stream_handle(logits.device))
-    C.check(rc, "pd_plane_sweep_fwd")
+    dev = logits.device
+    rgb_rec = torch.empty(B, 3, H, W, device=dev, dtype=torch.float32)
+    ph_map = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
+    ph_mean = _zero_scalar(dev)
+    stash = torch.empty(B, k, H, W, device=dev, dtype=torch.float32)
     if S.DEBUG_STASH is not None:
         S.DEBUG_STASH.append(stash)
-    return (rgb_rec, ph_map, ph_mean), (src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists, rgb_rec, stash)
+    saved = SweepSaved(src, _contig(tgt), logits, sigma, _contig(plane), _contig(plane_aux), _contig(inv_K3),
+                       _contig(padding_mask), _contig(dists), rgb_rec, stash)
+    return d, k, saved, ph_map, ph_mean
 
 
-def _sweep_forward_pair(src, logits, sigma, side_a, side_b):
-    """pd_uniform_fwd_pair: two plane-uniform target views (``side_*`` = (tgt, plane, plane_aux, inv_K3, padding_mask, dists,
-    mode, flags, sign) with equal mode / flags / sign) of the same src / logits / sigma in one launch.  Returns what two
-    ``_sweep_forward`` calls return."""
+def _sweep_forward(*call):
+    """One target view (the fields of a SweepCall, with or without its link) through pd_plane_sweep_fwd ->
+    ((rgb_rec, ph_map, ph_mean[1]), SweepSaved)."""
     lib = C.load()
-    mode, flags, sign = side_a[6:9]
-    S.LAST_SWEEP_FLAGS = flags
-    B, N, H, W = logits.shape
-    C.require_gpu_tensor("logits", logits)
-    C.require_gpu_tensor("src", src, (B, 3, H, W))
-    if flags & C.PD_MIXTURE:
-        C.require_gpu_tensor("sigma", sigma, (B, N, H, W))
-    src, logits, sigma = _contig(src), _contig(logits), _contig(sigma)
-    d = _desc(B, N, H, W, mode, flags, sign)
-    k = lib.pd_sweep_stash_floats(ctypes.byref(d)) // (H * W)
-    d.flags |= C.PD_PH_MEAN_ZEROED
-    views, results = [], []
-    for tgt, plane, plane_aux, inv_K3, padding_mask, dists, _, _, _ in (side_a, side_b):
-        C.require_gpu_tensor("tgt", tgt, (B, 3, H, W))
-        C.require_gpu_tensor("H_t2s", plane, (B, 4, 3, 3))
-        C.require_gpu_tensor("Rn", plane_aux, (B * N, 3))
-        C.require_gpu_tensor("inv_K3", inv_K3, (B, 3, 3))
-        if padding_mask is not None:
-            C.require_gpu_tensor("translation weights", padding_mask, (B, N, 3))
-        if flags & C.PD_RENDER_PROB:
-            C.require_gpu_tensor("dists", dists, (B, N - 1, H, W))
-        else:
-            dists = None
-        tgt, plane, plane_aux, inv_K3, padding_mask, dists = map(_contig, (tgt, plane, plane_aux, inv_K3, padding_mask, dists))
-        rgb_rec = torch.empty(B, 3, H, W, device=logits.device, dtype=torch.float32)
-        ph_map = torch.empty(B, 1, H, W, device=logits.device, dtype=torch.float32)
-        ph_mean = _zero_scalar(logits.device)
-        stash = torch.empty(B, k, H, W, device=logits.device, dtype=torch.float32)
-        views.append(C.sweep_view(tgt=tgt, plane=plane, plane_aux=plane_aux, inv_K3=inv_K3, dists=dists, rgb_rec=rgb_rec,
-                                  ph_map=ph_map, ph_mean=ph_mean, stash=stash))
-        results.append(((rgb_rec, ph_map, ph_mean),
-                        (src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists, rgb_rec, stash)))
-        if S.DEBUG_STASH is not None:
-            S.DEBUG_STASH.append(stash)
-    with C.on_device(logits.device), _timed("fwd"):
-        rc = lib.pd_uniform_fwd_pair(ctypes.byref(d), C.ptr(src), C.ptr(logits), C.ptr(sigma), ctypes.byref(views[0]),
-                                     ctypes.byref(views[1]), C.stream_handle(logits.device))
+    d, _, s, ph_map, ph_mean = _forward_view(lib, SweepCall(*call))
+    dev = s.logits.device
+    with C.on_device(dev), _timed("fwd"):
+        rc = lib.pd_plane_sweep_fwd(ctypes.byref(d), C.ptr(s.src), C.ptr(s.tgt), C.ptr(s.logits), C.ptr(s.sigma),
+                                    C.ptr(s.plane), C.ptr(s.plane_aux), C.ptr(s.inv_K3), C.ptr(s.padding_mask), C.ptr(s.dists),
+                                    C.ptr(s.rgb_rec), C.ptr(ph_map), C.ptr(ph_mean), C.ptr(s.stash), C.stream_handle(dev))
+    C.check(rc, "pd_plane_sweep_fwd")
+    return (s.rgb_rec, ph_map, ph_mean), s
+
+
+def _sweep_forward_pair(call_a, call_b):
+    """pd_uniform_fwd_pair: two plane-uniform target views (SweepCalls of equal mode / flags / sign over the same src / logits /
+    sigma) in one launch.  Returns what two ``_sweep_forward`` calls return."""
+    lib = C.load()
+    view_a = _forward_view(lib, call_a)
+    d, _, sa, ph_map_a, ph_mean_a = view_a
+    _, _, sb, ph_map_b, ph_mean_b = _forward_view(lib, call_b, first=view_a)
+    views = [C.sweep_view(tgt=s.tgt, plane=s.plane, plane_aux=s.plane_aux, inv_K3=s.inv_K3, dists=s.dists, rgb_rec=s.rgb_rec,
+                          ph_map=ph_map, ph_mean=ph_mean, stash=s.stash)
+             for s, ph_map, ph_mean in ((sa, ph_map_a, ph_mean_a), (sb, ph_map_b, ph_mean_b))]
+    dev = sa.logits.device
+    with C.on_device(dev), _timed("fwd"):
+        rc = lib.pd_uniform_fwd_pair(ctypes.byref(d), C.ptr(sa.src), C.ptr(sa.logits), C.ptr(sa.sigma), ctypes.byref(views[0]),
+                                     ctypes.byref(views[1]), C.stream_handle(dev))
     C.check(rc, "pd_uniform_fwd_pair")
-    return results
+    return ((sa.rgb_rec, ph_map_a, ph_mean_a), sa), ((sb.rgb_rec, ph_map_b, ph_mean_b), sb)
 
 
 def _sweep_backward_pair(view_a, view_b, cfg, need_a, need_b, g_logits, g_sigma, accumulate):
-    """pd_uniform_bwd_pair: the backward of two plane-uniform views (``view_*`` = (saved tensors, upstream gradients)) of the
+    """pd_uniform_bwd_pair: the backward of two plane-uniform views (``view_*`` = (SweepSaved, upstream gradients)) of the
     same logits / sigma — both first passes in one launch, then the pair gather into (``accumulate``: added to)
     g_logits / g_sigma (None: only the views' own gradients).  Returns ((g_plane_a, g_dists_a), (g_plane_b, g_dists_b))."""
     lib = C.load()
     mode, flags, sign = cfg
-    logits = view_a[0][2]
-    B, N, H, W = logits.shape
+    first = view_a[0]
+    B, N, H, W = first.logits.shape
+    dev = first.logits.device
     mix = bool(flags & C.PD_MIXTURE)
     d = _desc(B, N, H, W, mode, flags | C.PD_BWD_DEFER_GATHER | (C.PD_BWD_ACCUMULATE if accumulate else 0), sign)
-    nws = max(int(lib.pd_sweep_bwd_workspace_floats(ctypes.byref(d))), 1)
+    ws_floats = max(int(lib.pd_sweep_bwd_workspace_floats(ctypes.byref(d))), 1)   # (asked once: both views are d's)
     views, outs, keep = [], [], []
-    for (saved, grads), need in ((view_a, need_a), (view_b, need_b)):
-        src, tgt, _, sigma, plane, plane_aux, inv_K3, padding_mask, dists, rgb_rec, stash = saved
+    for (s, grads), need in ((view_a, need_a), (view_b, need_b)):
         g_rgb_rec, g_ph_map, g_ph_mean = grads
-        g_rgb_rec, g_ph_map = _contig(g_rgb_rec), _contig(g_ph_map)
-        if g_ph_mean is not None:
-            g_ph_mean = g_ph_mean.reshape(1).to(torch.float32).contiguous()
-        g_plane = torch.empty_like(plane) if need[2] else None
-        g_dists = torch.empty_like(dists) if (dists is not None and need[3]) else None
-        ws = torch.empty(nws, device=logits.device, dtype=torch.float32)
-        views.append(C.sweep_view(tgt=tgt, plane=plane, plane_aux=plane_aux, inv_K3=inv_K3, padding_mask=padding_mask,
-                                  dists=dists, rgb_rec=rgb_rec, stash=stash, g_rgb_rec=g_rgb_rec, g_ph_map=g_ph_map,
+        g_rgb_rec, g_ph_map, g_ph_mean = _contig(g_rgb_rec), _contig(g_ph_map), _scalar_grad(g_ph_mean)
+        _, _, need_plane, need_dists = need
+        g_plane = torch.empty_like(s.plane) if need_plane else None
+        g_dists = torch.empty_like(s.dists) if (s.dists is not None and need_dists) else None
+        ws = torch.empty(ws_floats, device=dev, dtype=torch.float32)
+        views.append(C.sweep_view(tgt=s.tgt, plane=s.plane, plane_aux=s.plane_aux, inv_K3=s.inv_K3, padding_mask=s.padding_mask,
+                                  dists=s.dists, rgb_rec=s.rgb_rec, stash=s.stash, g_rgb_rec=g_rgb_rec, g_ph_map=g_ph_map,
                                   g_ph_mean=g_ph_mean, g_plane=g_plane, g_dists=g_dists, workspace=ws))
         outs.append((g_plane, g_dists))
         keep.append((g_rgb_rec, g_ph_map, g_ph_mean, ws))   # alive until the call is enqueued
         if S.DEBUG_WORKSPACE is not None:
             S.DEBUG_WORKSPACE.append((d, ws))
-    src, sigma = view_a[0][0], view_a[0][3]
-    with C.on_device(logits.device), _timed("bwd"):
-        rc = lib.pd_uniform_bwd_pair(ctypes.byref(d), C.ptr(src), C.ptr(logits), C.ptr(sigma), ctypes.byref(views[0]),
-                                     ctypes.byref(views[1]), C.ptr(g_logits), C.ptr(g_sigma if mix else None),
-                                     C.stream_handle(logits.device))
+    with C.on_device(dev), _timed("bwd"):
+        rc = lib.pd_uniform_bwd_pair(ctypes.byref(d), C.ptr(first.src), C.ptr(first.logits), C.ptr(first.sigma),
+                                     ctypes.byref(views[0]), ctypes.byref(views[1]), C.ptr(g_logits),
+                                     C.ptr(g_sigma if mix else None), C.stream_handle(dev))
     C.check(rc, "pd_uniform_bwd_pair")
     del keep
     return outs
 
 
-def _sweep_backward(saved, cfg, grads, need, into=None, accumulate=False, defer=False):
+def _sweep_backward(saved, cfg, grads, need, into=None, accumulate=False):
     """pd_plane_sweep_bwd of one target view.  ``need`` = (logits, sigma, plane, dists) gradients wanted; ``into`` =
     (g_logits, g_sigma) buffers to write (or, ``accumulate``: add) into instead of fresh ones.
-    Returns (g_logits, g_sigma, g_plane, g_dists).  ``defer`` (plane-uniform views only): the first pass only
-    (PD_BWD_DEFER_GATHER) -> (g_plane, g_dists, workspace); ``_gather_pair`` finishes two such views in one kernel."""
+    Returns (g_logits, g_sigma, g_plane, g_dists)."""
     lib = C.load()
-    src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists, rgb_rec, stash = saved
+    s = SweepSaved(*saved)
     mode, flags, sign = cfg
     g_rgb_rec, g_ph_map, g_ph_mean = grads
-    B, N, H, W = logits.shape
+    B, N, H, W = s.logits.shape
+    dev = s.logits.device
     need_logits, need_sigma, need_plane, need_dists = need
-    g_plane, plane_flag = _plane_grad_buffer(plane, mode, flags) if need_plane else (None, 0)
-    d = _desc(B, N, H, W, mode, flags | plane_flag | (C.PD_BWD_ACCUMULATE if accumulate else 0) |
-              (C.PD_BWD_DEFER_GATHER if defer else 0), sign)
+    g_plane, plane_flag = _plane_grad_buffer(s.plane, B, N, H, W, mode, flags, sign) if need_plane else (None, 0)
+    d = _desc(B, N, H, W, mode, flags | plane_flag | (C.PD_BWD_ACCUMULATE if accumulate else 0), sign)
     mix = bool(flags & C.PD_MIXTURE)
-    if defer:
-        g_logits = g_sigma = None
-    elif into is not None:
+    if into is not None:
         g_logits, g_sigma = into
         edt = torch.bfloat16 if flags & C.PD_LOGITS_BF16 else torch.float32   # the buffers hold what the flag says
         if g_logits is not None:
@@ -170,26 +204,20 @@ def _sweep_backward(saved, cfg, grads, need, into=None, accumulate=False, defer=
         if g_sigma is not None:
             C.require_gpu_tensor("g_sigma", g_sigma, dtype=edt)
     else:
-        g_logits = torch.empty_like(logits) if need_logits else None
-        g_sigma = torch.empty_like(sigma) if (need_sigma and mix) else None
-    g_dists = torch.empty_like(dists) if (dists is not None and need_dists) else None
-    # scratch: partial sums of the plane-parameter gradient and the row-shift kernels' boundary spill
-    ws = torch.empty(max(int(lib.pd_sweep_bwd_workspace_floats(ctypes.byref(d))), 1), device=logits.device,
-                     dtype=torch.float32)
-    g_rgb_rec, g_ph_map = _contig(g_rgb_rec), _contig(g_ph_map)
-    if g_ph_mean is not None:
-        g_ph_mean = g_ph_mean.reshape(1).to(torch.float32).contiguous()
-    with C.on_device(logits.device), _timed("bwd"):
-        rc = lib.pd_plane_sweep_bwd(ctypes.byref(d), C.ptr(src), C.ptr(tgt), C.ptr(logits), C.ptr(sigma),
-                                    C.ptr(plane), C.ptr(plane_aux), C.ptr(inv_K3), C.ptr(padding_mask), C.ptr(dists),
-                                    C.ptr(rgb_rec), C.ptr(stash), C.ptr(g_rgb_rec), C.ptr(g_ph_map), C.ptr(g_ph_mean),
+        g_logits = torch.empty_like(s.logits) if need_logits else None
+        g_sigma = torch.empty_like(s.sigma) if (need_sigma and mix) else None
+    g_dists = torch.empty_like(s.dists) if (s.dists is not None and need_dists) else None
+    ws = _workspace(lib, d, dev)
+    g_rgb_rec, g_ph_map, g_ph_mean = _contig(g_rgb_rec), _contig(g_ph_map), _scalar_grad(g_ph_mean)
+    with C.on_device(dev), _timed("bwd"):
+        rc = lib.pd_plane_sweep_bwd(ctypes.byref(d), C.ptr(s.src), C.ptr(s.tgt), C.ptr(s.logits), C.ptr(s.sigma),
+                                    C.ptr(s.plane), C.ptr(s.plane_aux), C.ptr(s.inv_K3), C.ptr(s.padding_mask), C.ptr(s.dists),
+                                    C.ptr(s.rgb_rec), C.ptr(s.stash), C.ptr(g_rgb_rec), C.ptr(g_ph_map), C.ptr(g_ph_mean),
                                     C.ptr(g_logits), C.ptr(g_sigma if mix else None), C.ptr(g_plane), C.ptr(g_dists),
-                                    C.ptr(ws), C.stream_handle(logits.device))
+                                    C.ptr(ws), C.stream_handle(dev))
     C.check(rc, "pd_plane_sweep_bwd")
     if S.DEBUG_WORKSPACE is not None:
         S.DEBUG_WORKSPACE.append((d, ws))
-    if defer:
-        return g_plane, g_dists, ws
     return g_logits, (g_sigma if mix else None), g_plane, g_dists
 
 
@@ -198,44 +226,28 @@ def _sweep_backward_tail(saved, cfg, grads, need, link):
     (g_raw_logits, g_raw_sigma, g_plane) — handed to autograd as the gradients of logits / sigma; the tail's node passes them
     through (TailLink)."""
     lib = C.load()
-    src, tgt, logits, sigma, plane, _, _, _, _, rgb_rec, stash = saved
+    s = SweepSaved(*saved)
     mode, flags, sign = cfg
     g_rgb_rec, g_ph_map, g_ph_mean = grads
-    B, N, H, W = logits.shape
-    g_plane, plane_flag = _plane_grad_buffer(plane, mode, flags) if need[2] else (None, 0)
+    B, N, H, W = s.logits.shape
+    dev = s.logits.device
+    _, _, need_plane, _ = need
+    g_plane, plane_flag = _plane_grad_buffer(s.plane, B, N, H, W, mode, flags, sign) if need_plane else (None, 0)
     d = _desc(B, N, H, W, mode, flags | plane_flag, sign)
     g_disp, g_depth = link.seen.pop("disp", None), link.seen.pop("depth", None)   # (taken: state of THIS backward pass only)
-    gl, gs = torch.empty_like(logits), torch.empty_like(sigma)
-    ws = torch.empty(max(int(lib.pd_sweep_bwd_workspace_floats(ctypes.byref(d))), 1), device=logits.device, dtype=torch.float32)
+    gl, gs = torch.empty_like(s.logits), torch.empty_like(s.sigma)
+    ws = _workspace(lib, d, dev)
     g_rgb_rec, g_ph_map, gd, gz = map(_contig, (g_rgb_rec, g_ph_map, g_disp, g_depth))
-    if g_ph_mean is not None:
-        g_ph_mean = g_ph_mean.reshape(1).to(torch.float32).contiguous()
-    with C.on_device(logits.device), _timed("bwd"):
-        rc = lib.pd_plane_sweep_bwd_tail(ctypes.byref(d), C.ptr(src), C.ptr(tgt), C.ptr(logits), C.ptr(sigma), C.ptr(plane),
-                                         C.ptr(rgb_rec), C.ptr(stash), C.ptr(g_rgb_rec), C.ptr(g_ph_map), C.ptr(g_ph_mean),
+    g_ph_mean = _scalar_grad(g_ph_mean)
+    with C.on_device(dev), _timed("bwd"):
+        rc = lib.pd_plane_sweep_bwd_tail(ctypes.byref(d), C.ptr(s.src), C.ptr(s.tgt), C.ptr(s.logits), C.ptr(s.sigma), C.ptr(s.plane),
+                                         C.ptr(s.rgb_rec), C.ptr(s.stash), C.ptr(g_rgb_rec), C.ptr(g_ph_map), C.ptr(g_ph_mean),
                                          C.ptr(link.raw_sigma), C.ptr(link.stash), C.ptr(link.disp), C.ptr(gd), C.ptr(gz),
-                                         C.ptr(gl), C.ptr(gs), C.ptr(g_plane), C.ptr(ws), C.stream_handle(logits.device))
+                                         C.ptr(gl), C.ptr(gs), C.ptr(g_plane), C.ptr(ws), C.stream_handle(dev))
     C.check(rc, "pd_plane_sweep_bwd_tail")
     link.applied = {"disp": g_disp, "depth": g_depth}   # until the tail's node of this pass has consumed it
     link.fused_passes += 1
     return gl, gs, g_plane
-
-
-def _gather_pair(view_a, view_b, cfg, g_logits, g_sigma, accumulate):
-    """pd_uniform_gather_pair: the second pass of two deferred plane-uniform backward calls (``view_*`` = (saved tensors,
-    workspace)) into (or, ``accumulate``: added to) g_logits / g_sigma."""
-    lib = C.load()
-    (saved_a, ws_a), (saved_b, ws_b) = view_a, view_b
-    logits = saved_a[2]
-    B, N, H, W = logits.shape
-    mode, flags, sign = cfg
-    mix = bool(flags & C.PD_MIXTURE)
-    d = _desc(B, N, H, W, mode, flags | C.PD_BWD_DEFER_GATHER | (C.PD_BWD_ACCUMULATE if accumulate else 0), sign)
-    with C.on_device(logits.device), _timed("bwd"):
-        rc = lib.pd_uniform_gather_pair(ctypes.byref(d), C.ptr(saved_a[4]), C.ptr(saved_a[6]), C.ptr(ws_a),
-                                        C.ptr(saved_b[4]), C.ptr(saved_b[6]), C.ptr(ws_b), C.ptr(g_logits),
-                                        C.ptr(g_sigma if mix else None), C.stream_handle(logits.device))
-    C.check(rc, "pd_uniform_gather_pair")
 
 
 class TailLink:
@@ -287,12 +299,12 @@ def tail_taps(outputs):
 
 
 class _PlaneSweep(torch.autograd.Function):
-    """(src, tgt, logits, sigma, plane, ...) -> (rgb_rec [B,3,H,W], ph_map [B,1,H,W], ph_mean []).
+    """apply(*SweepCall) -> (rgb_rec [B,3,H,W], ph_map [B,1,H,W], ph_mean []).
 
     ``ph_mean`` is ``ph_map.mean()`` accumulated inside the sweep kernel (the `.mean()` of trainer.py:742 without a
     reduction kernel of its own); its upstream gradient is a device scalar that the backward kernel applies per pixel.
 
-    Gradients: logits, sigma, plane (disp_layered or H_t2s).  src / tgt are images (no gradient, as in the reference
+    Gradients: logits, sigma, plane (disp_layered or H_t2s), dists.  src / tgt are images (no gradient, as in the reference
     where they are dataset tensors).
     """
 
@@ -308,18 +320,26 @@ class _PlaneSweep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb_rec, g_ph_map, g_ph_mean):
-        need = (ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4], ctx.needs_input_grad[8])
+        need = tuple(ctx.needs_input_grad[i] for i in _GRAD_AT)
+        need_logits, need_sigma, _, _ = need
         link = ctx.link
-        if link is not None and link.consumers == 1 and need[0] and need[1]:
+        if link is not None and link.consumers == 1 and need_logits and need_sigma:
             g_logits, g_sigma, g_plane = _sweep_backward_tail(ctx.saved_tensors, ctx.cfg, (g_rgb_rec, g_ph_map, g_ph_mean),
                                                               need, link)
-            return None, None, g_logits, g_sigma, g_plane, None, None, None, None, None, None, None, None
+            return _call_grads(g_logits, g_sigma, g_plane, None)
         g_logits, g_sigma, g_plane, g_dists = _sweep_backward(ctx.saved_tensors, ctx.cfg,
                                                               (g_rgb_rec, g_ph_map, g_ph_mean), need)
-        return None, None, g_logits, g_sigma, g_plane, None, None, None, g_dists, None, None, None, None
+        return _call_grads(g_logits, g_sigma, g_plane, g_dists)
 
 
-_PER_SIDE = 9   # tgt, plane, plane_aux, inv_K3, padding_mask, dists, mode, flags, sign
+_SHARED = ("src", "logits", "sigma")   # what every view of a _MultiPlaneSweep node sweeps, in apply()'s order
+_SIDE_FIELDS = tuple(k for k in SweepCall._fields if k not in _SHARED + ("link",))   # what each view brings along
+_PER_SIDE = len(_SIDE_FIELDS)
+_SIDE_PLANE, _SIDE_DISTS = _SIDE_FIELDS.index("plane"), _SIDE_FIELDS.index("dists")
+
+
+def _plane_uniform(mode, flags):
+    return mode == C.PD_WARP_HOMOGRAPHY and bool(flags & C.PD_HOMO_UNIFORM)
 
 
 class _MultiPlaneSweep(torch.autograd.Function):
@@ -328,34 +348,32 @@ class _MultiPlaneSweep(torch.autograd.Function):
     kernels (PD_BWD_ACCUMULATE) instead of by [B,N,H,W]-sized add kernels between separate nodes (at 8x49x192x640 each
     such add moves 0.58 GB; three views need four of them).
 
-    apply(src, logits, sigma, *flat) with ``flat`` = per view (tgt, plane, plane_aux, inv_K3, padding_mask, dists, mode,
-    flags, sign) -> per view (rgb_rec, ph_map, ph_mean)."""
+    apply(src, logits, sigma, *flat) with ``flat`` = per view its ``_SIDE_FIELDS`` (tgt, plane, plane_aux, inv_K3,
+    padding_mask, dists, mode, flags, sign) -> per view (rgb_rec, ph_map, ph_mean)."""
 
     @staticmethod
     def forward(ctx, src, logits, sigma, *flat):
         n = len(flat) // _PER_SIDE
-        outs, tensors, cfgs, layout = [], [], [], []
-        sides = [flat[i * _PER_SIDE:(i + 1) * _PER_SIDE] for i in range(n)]
+        calls = []
+        for i in range(n):
+            tgt, plane, plane_aux, inv_K3, padding_mask, dists, mode, flags, sign = flat[i * _PER_SIDE:(i + 1) * _PER_SIDE]   # _SIDE_FIELDS
+            calls.append(SweepCall(src, tgt, logits, sigma if flags & C.PD_MIXTURE else None, plane, plane_aux, inv_K3,
+                                   padding_mask, dists, mode, flags, sign))
+        cfgs = [(c.mode, c.flags, c.sign) for c in calls]
         done = {}   # plane-uniform views of equal configuration go through the forward two at a time (pd_uniform_fwd_pair)
-        if S.PAIR_FORWARD:
-            uni = [i for i in range(n) if sides[i][6] == C.PD_WARP_HOMOGRAPHY and sides[i][7] & C.PD_HOMO_UNIFORM]
+        if S.PAIR_VIEWS:
+            uni = [i for i in range(n) if _plane_uniform(calls[i].mode, calls[i].flags)]
             while len(uni) >= 2:
                 i = uni.pop(0)
-                j = next((q for q in uni if tuple(sides[q][6:9]) == tuple(sides[i][6:9])), None)
+                j = next((q for q in uni if cfgs[q] == cfgs[i]), None)
                 if j is None:
                     continue
                 uni.remove(j)
-                done[i], done[j] = _sweep_forward_pair(src, logits, sigma if sides[i][7] & C.PD_MIXTURE else None,
-                                                       sides[i], sides[j])
+                done[i], done[j] = _sweep_forward_pair(calls[i], calls[j])
+        outs, tensors, layout = [], [], []
         for i in range(n):
-            tgt, plane, plane_aux, inv_K3, padding_mask, dists, mode, flags, sign = sides[i]
-            if i in done:
-                (rgb_rec, ph_map, ph_mean), saved = done[i]
-            else:
-                (rgb_rec, ph_map, ph_mean), saved = _sweep_forward(src, tgt, logits, sigma if flags & C.PD_MIXTURE else None,
-                                                                   plane, plane_aux, inv_K3, padding_mask, dists, mode, flags, sign)
+            (rgb_rec, ph_map, ph_mean), saved = done[i] if i in done else _sweep_forward(*calls[i])
             outs += [rgb_rec, ph_map, ph_mean.reshape(())]
-            cfgs.append((mode, flags, sign))
             idx = []
             for t in saved:     # save_for_backward takes tensors only: remember where the Nones were
                 if t is None:
@@ -374,54 +392,40 @@ class _MultiPlaneSweep(torch.autograd.Function):
         lib = C.load()
         tensors = ctx.saved_tensors
         n = ctx.n
-        need_logits, need_sigma = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_logits, need_sigma = (ctx.needs_input_grad[_SHARED.index(k)] for k in ("logits", "sigma"))
         views = []
         for i in range(n):
             g = grads[3 * i:3 * i + 3]
             if all(x is None for x in g):
                 continue   # this view took no part in the loss
-            saved = tuple(None if j < 0 else tensors[j] for j in ctx.layout[i])
-            logits = saved[2]
-            B, N, H, W = logits.shape
-            mode, flags, sign = ctx.cfgs[i]
-            can = bool(lib.pd_sweep_bwd_accumulates(ctypes.byref(_desc(B, N, H, W, mode, flags, sign))))
-            views.append((i, saved, g, can))
+            saved = SweepSaved(*(None if j < 0 else tensors[j] for j in ctx.layout[i]))
+            B, N, H, W = saved.logits.shape
+            can = bool(lib.pd_sweep_bwd_accumulates(ctypes.byref(_desc(B, N, H, W, *ctx.cfgs[i]))))
+            base = len(_SHARED) + i * _PER_SIDE
+            need = (need_logits, need_sigma, ctx.needs_input_grad[base + _SIDE_PLANE], ctx.needs_input_grad[base + _SIDE_DISTS])
+            views.append((i, saved, g, can, need))
         views.sort(key=lambda v: v[3])   # kernels that cannot add in place (the row-shift ones) first: one of them starts the sum
         g_logits = g_sigma = None
         per_view = {}
 
-        def pairable(v):   # plane-uniform views with the same kernel configuration gather together (pd_uniform_gather_pair)
-            mode, flags, sign = ctx.cfgs[v[0]]
-            return (S.PAIR_GATHER and mode == C.PD_WARP_HOMOGRAPHY and
-                    bool(flags & C.PD_HOMO_UNIFORM) and (need_logits or need_sigma))
+        def pairable(i):   # plane-uniform views with the same kernel configuration go through the backward together
+            mode, flags, _ = ctx.cfgs[i]
+            return S.PAIR_VIEWS and _plane_uniform(mode, flags) and (need_logits or need_sigma)
         k = 0
         while k < len(views):
-            i, saved, g, can = views[k]
-            base = 3 + i * _PER_SIDE
-            need = (need_logits, need_sigma, ctx.needs_input_grad[base + 1], ctx.needs_input_grad[base + 5])
+            i, saved, g, can, need = views[k]
             nxt = views[k + 1] if k + 1 < len(views) else None
-            if nxt is not None and pairable(views[k]) and pairable(nxt) and ctx.cfgs[i] == ctx.cfgs[nxt[0]]:
-                j, saved_j, g_j, _ = nxt
-                base_j = 3 + j * _PER_SIDE
-                need_j = (need_logits, need_sigma, ctx.needs_input_grad[base_j + 1], ctx.needs_input_grad[base_j + 5])
+            if nxt is not None and pairable(i) and pairable(nxt[0]) and ctx.cfgs[i] == ctx.cfgs[nxt[0]]:
+                # both first passes in one launch, the pair gather, the reductions: one call (pd_uniform_bwd_pair)
+                j, saved_j, g_j, _, need_j = nxt
                 started = g_logits is not None or g_sigma is not None
-                logits = saved[2]
-                mix = bool(ctx.cfgs[i][1] & C.PD_MIXTURE)
+                _, flags, _ = ctx.cfgs[i]
                 if g_logits is None:
-                    g_logits = torch.zeros_like(logits) if started else torch.empty_like(logits)
-                if mix and g_sigma is None:
-                    g_sigma = torch.zeros_like(logits) if started else torch.empty_like(logits)
-                if S.PAIR_FORWARD:   # both first passes in one launch, the pair gather, the reductions: one call
-                    (gp, gd), (gp_j, gd_j) = _sweep_backward_pair((saved, g), (saved_j, g_j), ctx.cfgs[i], need, need_j,
-                                                                  g_logits, g_sigma, accumulate=started)
-                else:
-                    gp, gd, ws = _sweep_backward(saved, ctx.cfgs[i], g, need, defer=True)
-                    gp_j, gd_j, ws_j = _sweep_backward(saved_j, ctx.cfgs[j], g_j, need_j, defer=True)
-                    _gather_pair((saved, ws), (saved_j, ws_j), ctx.cfgs[i], g_logits, g_sigma, accumulate=started)
-                    # the two (g_l, g_s) scratch workspaces (2 x [B,N,H,W,2] floats: 770 MB at 8x49x192x640, twice what
-                    # sequential views hold at a time) go back to the allocator now, not when the node's frame dies
-                    del ws, ws_j
-                per_view[i], per_view[j] = (gp, gd), (gp_j, gd_j)
+                    g_logits = torch.zeros_like(saved.logits) if started else torch.empty_like(saved.logits)
+                if flags & C.PD_MIXTURE and g_sigma is None:
+                    g_sigma = torch.zeros_like(saved.logits) if started else torch.empty_like(saved.logits)
+                per_view[i], per_view[j] = _sweep_backward_pair((saved, g), (saved_j, g_j), ctx.cfgs[i], need, need_j,
+                                                                g_logits, g_sigma, accumulate=started)
                 k += 2
                 continue
             if g_logits is None and g_sigma is None:
@@ -439,8 +443,9 @@ class _MultiPlaneSweep(torch.autograd.Function):
             k += 1
         out = [None, g_logits, g_sigma]
         for i in range(n):
-            gp, gd = per_view.get(i, (None, None))
-            out += [None, gp, None, None, None, gd, None, None, None]
+            side = [None] * _PER_SIDE
+            side[_SIDE_PLANE], side[_SIDE_DISTS] = per_view.get(i, (None, None))
+            out += side
         return tuple(out)
 
 
@@ -464,7 +469,7 @@ def as_f32(t):
 
 
 def _storage_route(logits, sigma, mix, desc):
-    """Where the call tuple is built: (logits, sigma, extra flags).  fp32 inputs pass as they are; bf16 logits (and bf16
+    """Where the SweepCall is built: (logits, sigma, extra flags).  fp32 inputs pass as they are; bf16 logits (and bf16
     sigma with the mixture) go to the kernels as bf16 with PD_LOGITS_BF16 where pd_sweep_native_bf16(desc) says the
     descriptor is served (desc None: never); everything else — mixed dtypes, fp16, a descriptor outside the native set —
     runs the fp32 route on as_f32 copies (their backward rounds each fp32 gradient once)."""
@@ -478,20 +483,20 @@ def _storage_route(logits, sigma, mix, desc):
 
 
 def plane_sweep_multi(deferred):
-    """``deferred``: one argument tuple per target view as returned by ``plane_sweep_disp(..., defer=True)`` /
+    """``deferred``: one SweepCall per target view as returned by ``plane_sweep_disp(..., defer=True)`` /
     ``plane_sweep_homography(..., defer=True)`` — all over the same (src, logits, sigma).  Returns a list of
     ``(rgb_rec, ph_map, ph_mean)`` per view; see _MultiPlaneSweep."""
-    if any(d[10] & C.PD_LOGITS_BF16 for d in deferred):
+    deferred = [SweepCall(*d) for d in deferred]
+    if any(d.flags & C.PD_LOGITS_BF16 for d in deferred):
         # one node sums the views' gradients in place (PD_BWD_ACCUMULATE): fp32 only — every view sweeps ONE fp32 copy
-        deferred = [(d[0], d[1], as_f32(d[2]), as_f32(d[3])) + tuple(d[4:10]) + (d[10] & ~C.PD_LOGITS_BF16,) + tuple(d[11:])
-                    for d in deferred]
-    src, _, logits = deferred[0][0], deferred[0][1], deferred[0][2]
-    sigma = next((d[3] for d in deferred if d[3] is not None), None)
+        deferred = [d._replace(logits=as_f32(d.logits), sigma=as_f32(d.sigma), flags=d.flags & ~C.PD_LOGITS_BF16) for d in deferred]
+    src, logits = deferred[0].src, deferred[0].logits
+    sigma = next((d.sigma for d in deferred if d.sigma is not None), None)
     flat = []
     for d in deferred:
-        if d[0] is not src or d[2] is not logits or (d[3] is not None and d[3] is not sigma):
+        if d.src is not src or d.logits is not logits or (d.sigma is not None and d.sigma is not sigma):
             raise ValueError("plane_sweep_multi: every view must sweep the same src / logits / sigma tensors")
-        flat += [d[1]] + list(d[4:12])   # (a 13th element, the decoder tail's link, serves single-view nodes only)
+        flat += [getattr(d, k) for k in _SIDE_FIELDS]   # (the decoder tail's link serves single-view nodes only)
     outs = _MultiPlaneSweep.apply(src, logits, sigma, *flat)
     return [tuple(outs[3 * i:3 * i + 3]) for i in range(len(deferred))]
 
@@ -540,6 +545,22 @@ class _FirstColumn(torch.autograd.Function):
         return (g * (1.0 / ctx.W)).unsqueeze(-1).expand(*g.shape, ctx.W)
 
 
+@functools.lru_cache(maxsize=None)
+def _row_kernels(B, N, H, W, impl):
+    """Do the row kernels serve disp mode at this shape under ``impl``?  pd_sweep_uses_rowshift (the per-row flags do not
+    enter its answer), asked once per shape."""
+    return bool(C.load().pd_sweep_uses_rowshift(ctypes.byref(C.SweepDesc(B, N, H, W, C.PD_WARP_DISP, 0, 1.0, impl))))
+
+
+def _finish(call, defer, return_mean):
+    """The end of plane_sweep_disp / plane_sweep_homography: the SweepCall itself (``defer``: for plane_sweep_multi, several
+    target views as one autograd node) or its node's (rgb_rec, ph_map[, ph_map.mean() fused into the kernel])."""
+    if defer:
+        return call
+    out = _PlaneSweep.apply(*call)
+    return out if return_mean else out[:2]
+
+
 def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *, target_side="r",
                      use_mixture_loss=True, automask=False, render_probability=False, dists=None, row_uniform=False,
                      return_mean=False, defer=False, _rows=None):
@@ -562,22 +583,17 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
     the row totals on column 0, zeros elsewhere.
     """
     B, N, H, W = logits.shape
+    lib = C.load()
+    sign = _SIGN.get(target_side, 0.0)  # any other key leaves the grid untouched (trainer.py:546-549)
     if _rows is not None:
         # internal (the stereo view of homography_warp): per-row shifts [B,N,H] and per-row mask [B,N,H] as they are — no
         # [B,N,H,W] view whose slice-backward would zero-fill and reduce 190 MB per step
-        probe = C.SweepDesc(B, N, H, W, C.PD_WARP_DISP, C.PD_DISP_ROWS | C.PD_MASK_ROWS, 1.0, S.SWEEP_IMPL)
-        if C.load().pd_sweep_uses_rowshift(ctypes.byref(probe)):
+        if _row_kernels(B, N, H, W, S.SWEEP_IMPL):
             shift, mask = _rows
             flags = _flags(use_mixture_loss, automask, rows=True, render=render_probability) | C.PD_MASK_ROWS
-            logits, sigma, bf = _storage_route(logits, sigma, use_mixture_loss,
-                                               _desc(B, N, H, W, C.PD_WARP_DISP, flags, _SIGN.get(target_side, 0.0)))
-            flags |= bf
-            call = (src, tgt, logits, sigma if use_mixture_loss else None, shift, None, None, mask,
-                    dists if render_probability else None, C.PD_WARP_DISP, flags, _SIGN.get(target_side, 0.0))
-            if defer:
-                return call
-            out = _PlaneSweep.apply(*call)
-            return out if return_mean else out[:2]
+            logits, sigma, bf = _storage_route(logits, sigma, use_mixture_loss, _desc(B, N, H, W, C.PD_WARP_DISP, flags, sign))
+            return _finish(SweepCall(src, tgt, logits, sigma if use_mixture_loss else None, shift, None, None, mask,
+                                     dists if render_probability else None, C.PD_WARP_DISP, flags | bf, sign), defer, return_mean)
         disp_layered, padding_mask = (t[..., None].expand(B, N, H, W) for t in _rows)   # PD_IMPL_GENERAL & co.
     if tuple(disp_layered.shape) != (B, N, H, W):
         disp_layered = disp_layered.expand(B, N, H, W)
@@ -586,8 +602,7 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
     if per_plane:
         plane = _per_plane_view(disp_layered)
     elif row_uniform:
-        probe = C.SweepDesc(B, N, H, W, C.PD_WARP_DISP, C.PD_DISP_ROWS, 1.0, S.SWEEP_IMPL)
-        rows = bool(C.load().pd_sweep_uses_rowshift(ctypes.byref(probe)))
+        rows = _row_kernels(B, N, H, W, S.SWEEP_IMPL)
         if rows:   # a LEAF map keeps the exact select gradient (g on column 0, zeros elsewhere); see the docstring
             plane = disp_layered[..., 0].contiguous() if disp_layered.is_leaf else _FirstColumn.apply(disp_layered)
         else:
@@ -601,32 +616,28 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
     flags = _flags(use_mixture_loss, automask, dense=not (per_plane or rows), render=render_probability, rows=rows)
     if padding_mask is not None and row_uniform and (per_plane or rows):
         # the mask of xy / xz planes is constant along x as well (depth_decoder.py:157, 166): hand over its first column
-        probe = C.SweepDesc(B, N, H, W, C.PD_WARP_DISP, flags, 1.0, S.SWEEP_IMPL)
-        if C.load().pd_sweep_uses_rowshift(ctypes.byref(probe)):
+        if _row_kernels(B, N, H, W, S.SWEEP_IMPL):
             padding_mask = padding_mask[..., 0]
             flags |= C.PD_MASK_ROWS
-    sign = _SIGN.get(target_side, 0.0)  # any other key leaves the grid untouched (trainer.py:546-549)
-    # bf16 logits / sigma: native where the descriptor is served (a per-pixel mask never is); else fp32 copies
-    native_ok = padding_mask is None or bool(flags & C.PD_MASK_ROWS)
+    # bf16 logits / sigma: native where the library serves the descriptor; a per-pixel mask is a fact of the call that no
+    # descriptor shows, and PD_LOGITS_BF16 is refused with one — fp32 copies there and everywhere else
+    per_pixel_mask = padding_mask is not None and not flags & C.PD_MASK_ROWS
     logits, sigma, bf = _storage_route(logits, sigma, use_mixture_loss,
-                                       _desc(B, N, H, W, C.PD_WARP_DISP, flags, sign) if native_ok else None)
+                                       None if per_pixel_mask else _desc(B, N, H, W, C.PD_WARP_DISP, flags, sign))
     flags |= bf
-    call = (src, tgt, logits, sigma if use_mixture_loss else None, plane, None, None, padding_mask,
-            dists if render_probability else None, C.PD_WARP_DISP, flags, sign)
+    call = SweepCall(src, tgt, logits, sigma if use_mixture_loss else None, plane, None, None, padding_mask,
+                     dists if render_probability else None, C.PD_WARP_DISP, flags, sign)
     # a fused decoder tail that asked for it (decoder_tail(..., fuse_sweep_backward=True)) gets its backward applied by this
-    # sweep's backward kernel — where the library serves that form for this descriptor
+    # sweep's backward kernel — where the library serves that form for this descriptor (mixture, one disparity per plane, ...:
+    # pd_sweep_bwd_tail_fuses) and the call has no padding mask and fp32 storage
     link = getattr(logits, "_pd_tail_link", None)
-    if (link is not None and not bf and per_plane and use_mixture_loss and padding_mask is None and not render_probability
-            and sigma is not None and getattr(sigma, "_pd_tail_link", None) is link
-            and C.load().pd_sweep_bwd_tail_fuses(ctypes.byref(_desc(B, N, H, W, C.PD_WARP_DISP, flags, sign)))):
+    if (link is not None and not bf and padding_mask is None and getattr(sigma, "_pd_tail_link", None) is link
+            and lib.pd_sweep_bwd_tail_fuses(ctypes.byref(_desc(B, N, H, W, C.PD_WARP_DISP, flags, sign)))):
         link.consumers += 1
-        call = call + (link,)
+        call = call._replace(link=link)
     elif link is not None:
         link.consumers += 2   # a consumer the fused form does not serve: nobody fuses
-    if defer:      # the argument tuple for plane_sweep_multi (several target views as one autograd node)
-        return call
-    out = _PlaneSweep.apply(*call)
-    return out if return_mean else out[:2]  # (rgb_rec, ph_map[, ph_map.mean() fused into the kernel])
+    return _finish(call, defer, return_mean)
 
 
 def homography_matrices(d, n, T, K, inv_K):
@@ -777,12 +788,9 @@ def plane_sweep_homography(src, tgt, logits, sigma, distance, norm, T, K, inv_K,
     else:
         H_t2s, Rn = homography_matrices_fused(distance, norm, T, K, inv_K)
         H_t2s, Rn = H_t2s.reshape(B * N, 3, 3), Rn.reshape(B * N, 3)
-    call = (src, tgt, logits, sigma if use_mixture_loss else None, H_t2s, Rn.detach().contiguous(), inv_K3.detach(), tw,
-            dists if render_probability else None, C.PD_WARP_HOMOGRAPHY, flags, 0.0)
-    if defer:
-        return call
-    out = _PlaneSweep.apply(*call)
-    return out if return_mean else out[:2]
+    call = SweepCall(src, tgt, logits, sigma if use_mixture_loss else None, H_t2s, Rn.detach().contiguous(), inv_K3.detach(), tw,
+                     dists if render_probability else None, C.PD_WARP_HOMOGRAPHY, flags, 0.0)
+    return _finish(call, defer, return_mean)
 
 
 def _stereo_rows_sweep(src, tgt, logits, sigma, distance, norm, T, K, inv_K, mix, automask, return_mean, defer=False,
