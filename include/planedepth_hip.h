@@ -432,6 +432,34 @@ int pd_masked_photometric_bwd(int B, int H, int W, int mixture, const float* rgb
                               float* g_rgb_rec, float* g_ph_map, pd_stream_t stream);
 
 /*
+ * Perceptual feature distance (trainer.py:672-685; pd_feature_distance.hip), ONE feature level of the perceptual net per call:
+ *   l_p = mean_c (pred - target)^2;  with `source` (opt.automask): l_p = min(l_p, mean_c (source - target)^2);
+ *   loss[0] = (accumulate ? loss[0] : 0) + mean over [B,h,w] of l_p
+ * so the reference's three levels are three calls with accumulate = 0, 1, 1 on one `loss`.  The net itself is not part of this
+ * library.
+ *   dtype     PD_DTYPE_F32 or PD_DTYPE_BF16: the element type of pred / target / source / g_pred, all [B,C,h,w] contiguous NCHW.
+ *             bf16 (what the net emits under torch.autocast) widens exactly on load, every sum is fp32, and a gradient element
+ *             is rounded to bf16 once, to nearest even — the rule of PD_LOGITS_BF16.  Anything else: PD_ERR_ARG naming it.
+ *   source    may be NULL (no automask)
+ *   sel       out (forward) / in (backward): [B,h,w] bytes, 1 where the prediction's distance is the minimum.  A TIE selects the
+ *             prediction (torch.min over cat([l_p, l_a]) returns the first index); both sums are formed in the same order, so
+ *             source == pred is a tie at every pixel, bit for bit.  All ones without a source.
+ *   partials  workspace, B * ceil(h*w / 64) floats, contents unspecified afterwards (no zero-fill needed)
+ *   loss      one float.  Deterministic: workgroup partial sums finished by one wave in index order, no float atomics
+ *   g_loss    one float (device): the gradient of the scalar
+ *   g_pred    [B,C,h,w], overwritten: g_loss * 2 (pred - target) / (C * B*h*w) where sel, exact zeros elsewhere (pred / target are
+ *             not read there).  target and source get no gradient (dataset images through a frozen net in the reference).
+ * A lane owns 16 bytes of adjacent pixels (four fp32, eight bf16) when h*w is a multiple of that count, the tensors are
+ * 16-byte aligned and sel is 4-byte aligned; one pixel per lane otherwise.  Per pixel the arithmetic is the same either way (the mean's summation order differs).
+ * Limits, refused on the host: B <= 65535, B*h*w < 2^31.
+ */
+enum pd_dtype { PD_DTYPE_F32 = 0, PD_DTYPE_BF16 = 1 };
+int pd_feature_distance_fwd(int B, int C, int h, int w, int dtype, const void* pred, const void* target, const void* source,
+                            uint8_t* sel, float* partials, float* loss, int accumulate, pd_stream_t stream);
+int pd_feature_distance_bwd(int B, int C, int h, int w, int dtype, const void* pred, const void* target, const uint8_t* sel,
+                            const float* g_loss, void* g_pred, pd_stream_t stream);
+
+/*
  * The O(B*N) 3x3 algebra of HomographyWarp.forward (layers.py:206-219, 223-225) and its adjoint, one launch each:
  *   M = R + t n^T / d;  H_t2s = inverse(K M K^-1);  Rn = R n          (R, t from T [B,4,4]; K, inv_K [B,4,4])
  * evaluated in fp64 and rounded once to fp32.  distance [B,N], norm [B,N,3].

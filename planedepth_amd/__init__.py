@@ -7,7 +7,7 @@ from .decoder_tail import fused_decoder_tail  # noqa: F401
 from .layers import (SSIM, BackprojectDepth, HomographyWarp, Project3D, disp_to_depth,  # noqa: F401
                      get_smooth_loss_disp, multimodal_loss)
 from .trainer_path import (add_flip_right_inputs, compute_depth_losses, compute_losses, compute_reprojection_loss,  # noqa: F401
-                           generate_post_process_disp, patch_trainer, patch_trainer_metrics, pred_novel_images,
-                           pred_self_images)
+                           generate_post_process_disp, patch_trainer, patch_trainer_metrics, patch_trainer_perceptual,
+                           perceptual_loss, pred_novel_images, pred_self_images)
 
 __version__ = "0.2.7"   # = pd_version() 270 of the library (tests/test_capi.py checks that they agree)

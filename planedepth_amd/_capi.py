@@ -26,6 +26,7 @@ PD_IMPL_AUTO, PD_IMPL_GENERAL, PD_IMPL_FAST_ROWS, PD_IMPL_TILE, PD_IMPL_ROWS1, P
 PD_IMPL_EXACT_ROWS = 6
 PD_EVAL_POST_PROCESS, PD_EVAL_EIGEN, PD_EVAL_MEDIAN, PD_EVAL_TRAINER = 1, 2, 4, 8
 PD_EVAL_TILE = 16384   # GT pixels per tile of pd_depth_eval (enum in the header)
+PD_DTYPE_F32, PD_DTYPE_BF16 = 0, 1   # pd_dtype: the element type of pd_feature_distance_*'s feature tensors
 
 
 class SweepDesc(ctypes.Structure):
@@ -122,6 +123,8 @@ SIGNATURES = {
     "pd_depth_eval_workspace_bytes": (ctypes.c_size_t, [_I] * 3),
     "pd_depth_eval": (_I, [_I] * 5 + [_F, _F, _P, _P, _I] + [_P] * 8),
     "pd_depth_eval_resize": (_I, [_I] * 5 + [_P] * 4),
+    "pd_feature_distance_fwd": (_I, [_I] * 5 + [_P] * 6 + [_I, _P]),
+    "pd_feature_distance_bwd": (_I, [_I] * 5 + [_P] * 6),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 """Loss operators: SSIM / reprojection loss (layers.py:276-306, trainer.py:687-699), the mixture NLL (layers.py:454-466), the
-photometric loss under mask_novel (trainer.py:724-742), the smoothness loss (layers.py:243-256).
+photometric loss under mask_novel (trainer.py:724-742), the perceptual feature distance (trainer.py:672-685), the smoothness
+loss (layers.py:243-256).
 """
 import ctypes
 import os
@@ -176,6 +177,105 @@ def masked_photometric(rgb_rec, target, mask, *, source=None, ph_map=None):
     ``ph_map`` given (mixture): ``(ph_map * mask).mean()``; otherwise L1 on ``pred`` with the automask's ``min`` against
     ``source`` when that is given.  One kernel each way (pd_masked_loss.hip)."""
     return _MaskedPhotometric.apply(rgb_rec, ph_map, target, source, mask)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Perceptual feature distance (trainer.py:672-685)
+# ---------------------------------------------------------------------------------------------------------------------
+_FEATURE_DTYPES = {torch.float32: C.PD_DTYPE_F32, torch.bfloat16: C.PD_DTYPE_BF16}
+
+
+class _FeatureDistance(torch.autograd.Function):
+    """All levels in one node: ``args`` = the prediction's features, then the target's, then (``has_source``) the source's."""
+
+    @staticmethod
+    def forward(ctx, levels, has_source, *args):
+        lib = C.load()
+        preds, targets = args[:levels], args[levels:2 * levels]
+        sources = args[2 * levels:] if has_source else (None,) * levels
+        dev = preds[0].device
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        saved = []
+        with C.on_device(dev):
+            stream = C.stream_handle(dev)
+            for i, (p, t, s) in enumerate(zip(preds, targets, sources)):
+                p, t, s = _contig(p.detach()), _contig(t), _contig(s)   # channels-last or sliced features are copied
+                B, Cc, h, w = p.shape
+                sel = torch.empty(B, h, w, device=dev, dtype=torch.uint8)
+                partials = torch.empty(B * ((h * w + 63) // 64), device=dev, dtype=torch.float32)
+                C.check(lib.pd_feature_distance_fwd(B, Cc, h, w, _FEATURE_DTYPES[p.dtype], C.ptr(p), C.ptr(t), C.ptr(s),
+                                                    C.ptr(sel), C.ptr(partials), C.ptr(loss), int(i > 0), stream),
+                        "pd_feature_distance_fwd")
+                saved += [p, t, sel]
+        ctx.save_for_backward(*saved)
+        ctx.levels = levels
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        lib = C.load()
+        saved = ctx.saved_tensors
+        dev = saved[0].device
+        g_loss = g_loss.reshape(1).contiguous().float()
+        grads = []
+        with C.on_device(dev):
+            stream = C.stream_handle(dev)
+            for i in range(ctx.levels):
+                p, t, sel = saved[3 * i:3 * i + 3]
+                if not ctx.needs_input_grad[2 + i]:
+                    grads.append(None)
+                    continue
+                B, Cc, h, w = p.shape
+                g = torch.empty_like(p)
+                C.check(lib.pd_feature_distance_bwd(B, Cc, h, w, _FEATURE_DTYPES[p.dtype], C.ptr(p), C.ptr(t), C.ptr(sel),
+                                                    C.ptr(g_loss), C.ptr(g), stream), "pd_feature_distance_bwd")
+                grads.append(g)
+        return (None, None) + tuple(grads) + (None,) * (len(ctx.needs_input_grad) - 2 - ctx.levels)
+
+
+def _feature_levels(name, feats):
+    if torch.is_tensor(feats):
+        return [feats]
+    feats = list(feats)
+    if not feats:
+        raise ValueError("feature_distance: %s holds no feature level" % name)
+    return feats
+
+
+def feature_distance(pred_feats, target_feats, source_feats=None):
+    """Trainer.perceptual_loss (trainer.py:672-685) on the perceptual net's OUTPUTS: over the feature levels (a sequence of
+    [B,C,h,w] tensors each; a bare tensor is one level) the sum of ``((pred_f - target_f) ** 2).mean(1, True)``, with
+    ``source_feats`` (opt.automask) its per-pixel ``min`` with the source's distance, ``.mean()`` -> a 0-dim fp32 tensor.  One
+    kernel per level each way, added up on the device (pd_feature_distance.hip).
+
+    fp32 or bf16 features (a level's tensors share one dtype); the gradient has the prediction's dtype.  Only the prediction's
+    features get a gradient: in the reference the target's and the source's are dataset images through a frozen net, and the
+    kernels produce none for them — a target or source feature that requires grad is refused rather than silently detached.
+    Non-contiguous (channels-last, sliced) features are copied."""
+    preds, targets = _feature_levels("pred_feats", pred_feats), _feature_levels("target_feats", target_feats)
+    sources = _feature_levels("source_feats", source_feats) if source_feats is not None else None
+    if len(targets) != len(preds) or (sources is not None and len(sources) != len(preds)):
+        raise ValueError("feature_distance: %d prediction levels, %d target levels%s" % (
+            len(preds), len(targets), "" if sources is None else ", %d source levels" % len(sources)))
+    for i, p in enumerate(preds):
+        if not torch.is_tensor(p) or p.dim() != 4:
+            raise ValueError("feature_distance: pred_feats[%d] must be a [B,C,h,w] tensor" % i)
+        if p.dtype not in _FEATURE_DTYPES:
+            raise TypeError("feature_distance: pred_feats[%d] is %s; float32 and bfloat16 features are served" % (i, p.dtype))
+        others = [("target_feats", targets[i])] + ([("source_feats", sources[i])] if sources is not None else [])
+        for name, t in others:
+            if torch.is_tensor(t) and t.requires_grad:
+                raise ValueError("feature_distance: %s[%d] requires grad, but the fused operator produces a gradient for the "
+                                 "prediction's features only (the reference feeds dataset images through a frozen net "
+                                 "there); detach it, or freeze the perceptual net" % (name, i))
+        C.require_gpu_tensor("pred_feats[%d]" % i, p, dtype=p.dtype)
+        for name, t in others:
+            C.require_gpu_tensor("%s[%d]" % (name, i), t, p.shape, dtype=p.dtype)
+            if t.device != p.device:
+                raise ValueError("feature_distance: %s[%d] is on %s, pred_feats[%d] on %s" % (name, i, t.device, i, p.device))
+        if p.device != preds[0].device:
+            raise ValueError("feature_distance: pred_feats[%d] is on %s, pred_feats[0] on %s" % (i, p.device, preds[0].device))
+    return _FeatureDistance.apply(len(preds), sources is not None, *preds, *targets, *(sources or ()))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

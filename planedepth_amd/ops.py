@@ -1,6 +1,6 @@
 """Autograd-aware operators over the C ABI (``include/planedepth_hip.h``) — the one namespace the rest of the package, the tests
 and ``bench.py`` use.  The operators live in ``sweep`` (the fused plane sweep: autograd nodes, routing, homography algebra),
-``tails`` (decoder / PladeNet tails), ``losses`` (SSIM, mixture NLL, masked photometric, smoothness), ``postprocess``
+``tails`` (decoder / PladeNet tails), ``losses`` (SSIM, mixture NLL, masked photometric, smoothness, perceptual feature distance), ``postprocess``
 (self-distillation warps, batch doubling, crop grid), ``metrics`` (depth evaluation), ``geometry`` (backproject / project /
 homography grids, grid_sample) and ``_buffers`` (descriptors, pre-zeroed pools); the switches tests flip between calls (``ops.SWEEP_IMPL = ...``) are attributes
 of ``_state`` that this module forwards both ways.
@@ -27,7 +27,8 @@ from .tails import (  # noqa: F401
     plade_tail)
 from .losses import (  # noqa: F401
     _SSIM, ssim, _ReprojLoss, reprojection_loss, _MixtureNLL, multimodal_loss,
-    _MaskedPhotometric, masked_photometric, _row_strided, _SmoothLoss, smooth_loss_disp)
+    _MaskedPhotometric, masked_photometric, _row_strided, _SmoothLoss, smooth_loss_disp,
+    _FeatureDistance, feature_distance)
 from .postprocess import (  # noqa: F401
     _pp_disp, warp_softmax, warp_sum, pp_combine, post_process_disp, post_process_disp_stepwise, cat_flip,
     crop_grid)

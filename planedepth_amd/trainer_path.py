@@ -343,6 +343,22 @@ def patch_trainer_metrics(trainer_cls):
     return trainer_cls
 
 
+def perceptual_loss(self, pred, target, source=None):
+    """Trainer.perceptual_loss (reference trainer.py:672-685): ``self.pc_net`` on each image exactly as the reference calls it
+    (stock convolutions, not part of this package), then the distance over its first three feature levels as one fused
+    operator (ops.feature_distance) instead of the per-level sub / pow / mean / cat / min chain.  Returns the 0-dim loss."""
+    pred_f = self.pc_net(pred)
+    target_f = self.pc_net(target)
+    source_f = self.pc_net(source) if source is not None else None
+    return ops.feature_distance(pred_f[:3], target_f[:3], None if source_f is None else source_f[:3])
+
+
+def patch_trainer_perceptual(trainer_cls):
+    """Opt-in: bind :func:`perceptual_loss` to a reference ``Trainer`` class (``patch_trainer`` leaves it alone)."""
+    trainer_cls.perceptual_loss = perceptual_loss
+    return trainer_cls
+
+
 def patch_trainer(trainer_cls):
     """Bind the fused hot path onto a reference-style Trainer class (drop-in)."""
     trainer_cls.pred_novel_images = pred_novel_images
