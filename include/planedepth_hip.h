@@ -294,8 +294,20 @@ int pd_mixture_nll_bwd(int B, int N, int H, int W, int laplacian, const float* e
  * bwd: upstream g_logits, g_sigma [B,N,H,W], g_disp, g_depth [B,1,H,W] (each may be NULL = zero) -> g_raw_logits,
  * g_raw_sigma [B,N,H,W], g_disp_layered (same layout as disp_layered; the [B,N] form needs `workspace` of
  * pd_decoder_tail_bwd_workspace_floats floats); outputs that are NULL are skipped.
+ *
+ * PD_TAIL_BF16 (torch.autocast: the conv outputs are bf16; fwd, layers and bwd of both tails take it): the signatures do not
+ * change, but these `float*` parameters hold torch.bfloat16 bit patterns: raw_logits, raw_sigma; fwd's outputs logits, sigma;
+ * bwd's inputs g_logits, g_sigma and outputs g_raw_logits, g_raw_sigma.  Everything else stays fp32: padding_mask,
+ * disp_layered, disp, depth, stash, g_disp, g_depth, g_disp_layered, workspace, pi, probability.  A bf16 element widens exactly
+ * on load, every operation is the fp32 kernel's in the same order, and every bf16 output element is rounded once, to nearest
+ * even, from the fp32 value that holds all of its contributions.  So disp, depth, stash, pi and probability are what the fp32
+ * entry gives on the widened inputs (they come from the UNROUNDED fp32 sigma, where the reference under autocast would carry a
+ * bf16-rounded sigma into probability), `sigma` is that fp32 sigma rounded once (bf16(0.01) = 0.010009765625 >= 0.01: it never
+ * falls below the sweep's clamp), and bwd decides the clamp gate in fp32 on the sigmoid it recomputes from raw_sigma.
+ * NULL and shape checks are the same with and without the flag; bf16 tensors need 2-byte alignment only (8-byte alignment of
+ * all of them, 16-byte of the fp32 ones, and H*W % 4 == 0 select the form with 4 pixels per lane).
  */
-enum pd_tail_flags { PD_TAIL_MIXTURE = 1, PD_TAIL_DISP_DENSE = 2 };
+enum pd_tail_flags { PD_TAIL_MIXTURE = 1, PD_TAIL_DISP_DENSE = 2, PD_TAIL_BF16 = 4 };
 size_t pd_decoder_tail_bwd_workspace_floats(int B, int N, int H, int W);
 int pd_decoder_tail_fwd(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
                         const float* padding_mask, const float* disp_layered, float* logits, float* sigma, float* disp,
@@ -323,6 +335,9 @@ int pd_decoder_tail_bwd(int B, int N, int H, int W, int flags, const float* raw_
  * ones plane), g_dists [B,N-1,H,W], g_sigma [B,N,H,W], g_disp, g_depth (each may be NULL = zero) -> g_raw_logits [B,N-1,H,W],
  * g_raw_sigma, g_disp_layered (layout of disp_layered; the [B,N] form needs `workspace` of
  * pd_decoder_tail_bwd_workspace_floats floats); outputs that are NULL are skipped.
+ * PD_TAIL_BF16, under the rule stated above: bf16 are raw_logits, raw_sigma, fwd's logits and sigma (the appended ones channel
+ * is an exact bf16 1), bwd's g_logits, g_sigma, g_raw_logits and g_raw_sigma; ray_norm, dists, g_dists and everything the
+ * decoder tail keeps in fp32 stay fp32.
  */
 int pd_plade_tail_fwd(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
                       const float* disp_layered, const float* ray_norm, float* logits, float* dists, float* sigma, float* disp,

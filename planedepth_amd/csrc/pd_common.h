@@ -354,6 +354,21 @@ __device__ __forceinline__ void lds_add(float* p, float v) {
   __builtin_amdgcn_ds_faddf((__attribute__((address_space(3))) float*)(p), v, 0, 0, false);
 }
 
+// ---- bf16 storage (PD_LOGITS_BF16, PD_TAIL_BF16) ---------------------------------------------------------------------
+// A `float*` parameter that holds bf16 under a flag is read as `Bf16` bit patterns.  The arithmetic is fp32 either way: an
+// element widens exactly on load, and an output element is rounded to bf16 once, from the fp32 value that holds all of its
+// contributions (pack_bf16x2: v_cvt_pk_bf16_f32, round to nearest even).
+typedef unsigned short Bf16;
+template <class T> __device__ __forceinline__ const T* elems(const float* p) { return reinterpret_cast<const T*>(p); }
+template <class T> __device__ __forceinline__ T* elems(float* p) { return reinterpret_cast<T*>(p); }
+__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }           // element 2j of a dword
+__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }   // element 2j + 1
+__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
+  unsigned w;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(lo), "v"(hi));
+  return w;
+}
+
 __device__ __forceinline__ float fast_exp(float x) { return __expf(x); }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float sgn(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }

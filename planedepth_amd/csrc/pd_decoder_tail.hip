@@ -10,6 +10,11 @@
 // from the per-pixel stash {log-sum-exp, sum(pi*mask/sigma)}.
 // Algorithmic bytes per pixel: forward reads 2N (+N mask) floats, writes N (sigma) (+N logits when there is a mask)
 // + 4; backward reads 4N (+N) and writes 2N.  HBM-bound streaming, no reuse.
+// PD_TAIL_BF16 (torch.autocast: the conv outputs are bf16): raw_logits / raw_sigma, logits / sigma and the four [B,N,H,W]
+// gradients hold bf16, which halves those terms.  The kernels are the same templates with the storage type ST = Bf16: every
+// element widens exactly on load, the arithmetic is the fp32 kernel's in the same order, and each bf16 output element is
+// rounded once from its fp32 value.  disp / depth / stash (and pi / probability) come from the UNROUNDED fp32 sigma; the
+// backward recomputes the sigmoid from raw_sigma, so its clamp gate is decided in fp32 as well.
 #include "pd_tail_common.h"
 
 namespace pd {
@@ -23,7 +28,7 @@ struct TailArgs {
   const float* dl;     // [B,N] or [B,N,H,W]
 };
 
-template <bool MIX, bool HASMASK, int PX>
+template <class ST, bool MIX, bool HASMASK, int PX>
 __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __restrict__ logits, float* __restrict__ sigma,
                                                           float* __restrict__ disp, float* __restrict__ depth,
                                                           float* __restrict__ stash) {
@@ -33,12 +38,15 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __r
   float m[PX], Z[PX], Sw[PX], Sd[PX];  // running reference, sum e^(l-m), sum of weights, sum w*d
 #pragma unroll
   for (int j = 0; j < PX; ++j) { m[j] = -INFINITY; Z[j] = Sw[j] = Sd[j] = 0.0f; }
-#pragma unroll 2
+  // (bf16: not unrolled.  The store's pack_bf16x2 is inline assembly, which the compiler treats as convergent and will not
+  // duplicate into an unrolled body with a run-time remainder.)
+  constexpr int kUnroll = sizeof(ST) == sizeof(float) ? 2 : 1;
+#pragma unroll kUnroll
   for (int n = 0; n < a.N; ++n) {
     const long i = base + (long)n * a.HW;
     const Px<PX> mk = HASMASK ? ldv<PX>(a.mask + i) : splat<PX>(1.0f);
-    const Px<PX> rl = ldv<PX>(a.raw_logits + i);
-    const Px<PX> rs = MIX ? ldv<PX>(a.raw_sigma + i) : splat<PX>(0.0f);
+    const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
+    const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
     const Px<PX> dv = a.dense ? ldv<PX>(a.dl + i) : splat<PX>(a.dl[b * a.N + n]);
     Px<PX> lo, so;
 #pragma unroll
@@ -62,8 +70,8 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __r
       Sw[j] += w;
       Sd[j] += w * dv.v[j];
     }
-    if (HASMASK) stv<PX>(logits + i, lo);
-    if (MIX) stv<PX>(sigma + i, so);
+    if (HASMASK) stv<PX>(elems<ST>(logits) + i, lo);
+    if (MIX) stv<PX>(elems<ST>(sigma) + i, so);
   }
   Px<PX> o_disp, o_depth, o_lse, o_sn;
 #pragma unroll
@@ -81,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __r
 }
 
 // pi and probability (depth_decoder.py:275, 281-285) for callers that want the tensors.
-template <bool MIX, bool HASMASK, int PX>
+template <class ST, bool MIX, bool HASMASK, int PX>
 __global__ __launch_bounds__(kBlock) void tail_layers_kernel(TailArgs a, const float* __restrict__ stash,
                                                              float* __restrict__ pi, float* __restrict__ prob) {
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
@@ -93,8 +101,8 @@ __global__ __launch_bounds__(kBlock) void tail_layers_kernel(TailArgs a, const f
   for (int n = 0; n < a.N; ++n) {
     const long i = base + (long)n * a.HW;
     const Px<PX> mk = HASMASK ? ldv<PX>(a.mask + i) : splat<PX>(1.0f);
-    const Px<PX> rl = ldv<PX>(a.raw_logits + i);
-    const Px<PX> rs = MIX ? ldv<PX>(a.raw_sigma + i) : splat<PX>(0.0f);
+    const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
+    const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
     Px<PX> op, oq;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
@@ -111,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void tail_layers_kernel(TailArgs a, const f
 // (+ the depth term): d disp / d w_n = (d_n - disp) / S, and since sum_k pi_k (d loss / d pi_k) = gD/S * sum_k w_k
 // (d_k - disp) = 0 exactly, the softmax backward needs no second reduction:
 //   g_logits_n += gD (d_n - disp) P_n;   g_sigma_n -= gD (d_n - disp) P_n / sigma_n;   g_d_n = gD P_n.
-template <bool MIX, bool HASMASK, int PX>
+template <class ST, bool MIX, bool HASMASK, int PX>
 __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const float* __restrict__ stash,
                                                           const float* __restrict__ disp,
                                                           const float* __restrict__ g_logits,
@@ -148,11 +156,11 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const floa
     float gd = 0.0f;
     if (active) {
       const Px<PX> mk = HASMASK ? ldv<PX>(a.mask + i) : splat<PX>(1.0f);
-      const Px<PX> rl = ldv<PX>(a.raw_logits + i);
-      const Px<PX> rs = MIX ? ldv<PX>(a.raw_sigma + i) : splat<PX>(0.0f);
+      const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
+      const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
       const Px<PX> dv = a.dense ? ldv<PX>(a.dl + i) : splat<PX>(a.dl[b * a.N + n]);
-      const Px<PX> gl = g_logits ? ldv<PX>(g_logits + i) : splat<PX>(0.0f);
-      const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(g_sigma + i) : splat<PX>(0.0f);
+      const Px<PX> gl = g_logits ? ldv<PX>(elems<ST>(g_logits) + i) : splat<PX>(0.0f);
+      const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(elems<ST>(g_sigma) + i) : splat<PX>(0.0f);
       Px<PX> o_l, o_s, o_d;
 #pragma unroll
       for (int j = 0; j < PX; ++j) {
@@ -170,8 +178,8 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const floa
         o_d.v[j] = gD.v[j] * P;
         gd += o_d.v[j];
       }
-      if (g_raw_logits) stv<PX>(g_raw_logits + i, o_l);
-      if (MIX && g_raw_sigma) stv<PX>(g_raw_sigma + i, o_s);
+      if (g_raw_logits) stv<PX>(elems<ST>(g_raw_logits) + i, o_l);
+      if (MIX && g_raw_sigma) stv<PX>(elems<ST>(g_raw_sigma) + i, o_s);
       if (g_dl && a.dense) stv<PX>(g_dl + i, o_d);
     }
     if (reduce) {
@@ -190,7 +198,7 @@ static int tail_validate(int B, int N, int H, int W, int flags, const float* raw
                          const float* dl) {
   PD_REQUIRE(B > 0 && B <= 65535 && N > 0 && H > 0 && W > 0, "bad shape");
   PD_REQUIRE((long)H * W < (1L << 31), "image too large");
-  PD_REQUIRE((flags & ~(PD_TAIL_MIXTURE | PD_TAIL_DISP_DENSE)) == 0, "unknown flags");
+  PD_REQUIRE((flags & ~(PD_TAIL_MIXTURE | PD_TAIL_DISP_DENSE | PD_TAIL_BF16)) == 0, "unknown flags");
   PD_REQUIRE(raw_logits && dl, "NULL pointer");
   PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || raw_sigma, "mixture needs raw_sigma");
   return 0;
@@ -206,20 +214,25 @@ static TailArgs tail_args(int N, int H, int W, int flags, const float* raw_logit
   return a;
 }
 
-#define PD_TAIL_DISPATCH_PX(KERNEL, PX, mix, hasmask, grid, shmem, stream, ...)                             \
+#define PD_TAIL_DISPATCH_PX(KERNEL, T, PX, mix, hasmask, grid, shmem, stream, ...)                          \
   do {                                                                                                       \
     if (mix) {                                                                                               \
-      if (hasmask) KERNEL<true, true, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                     \
-      else         KERNEL<true, false, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                    \
+      if (hasmask) KERNEL<T, true, true, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                  \
+      else         KERNEL<T, true, false, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                 \
     } else {                                                                                                 \
-      if (hasmask) KERNEL<false, true, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                    \
-      else         KERNEL<false, false, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                   \
+      if (hasmask) KERNEL<T, false, true, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                 \
+      else         KERNEL<T, false, false, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                \
     }                                                                                                        \
   } while (0)
-#define PD_TAIL_DISPATCH(KERNEL, px, mix, hasmask, grid, shmem, stream, ...)                                 \
+#define PD_TAIL_DISPATCH_T(KERNEL, T, px, mix, hasmask, grid, shmem, stream, ...)                            \
   do {                                                                                                       \
-    if ((px) == 4) PD_TAIL_DISPATCH_PX(KERNEL, 4, mix, hasmask, grid, shmem, stream, __VA_ARGS__);           \
-    else           PD_TAIL_DISPATCH_PX(KERNEL, 1, mix, hasmask, grid, shmem, stream, __VA_ARGS__);           \
+    if ((px) == 4) PD_TAIL_DISPATCH_PX(KERNEL, T, 4, mix, hasmask, grid, shmem, stream, __VA_ARGS__);        \
+    else           PD_TAIL_DISPATCH_PX(KERNEL, T, 1, mix, hasmask, grid, shmem, stream, __VA_ARGS__);        \
+  } while (0)
+#define PD_TAIL_DISPATCH(KERNEL, bf16, px, mix, hasmask, grid, shmem, stream, ...)                           \
+  do {                                                                                                       \
+    if (bf16) PD_TAIL_DISPATCH_T(KERNEL, Bf16, px, mix, hasmask, grid, shmem, stream, __VA_ARGS__);          \
+    else      PD_TAIL_DISPATCH_T(KERNEL, float, px, mix, hasmask, grid, shmem, stream, __VA_ARGS__);         \
   } while (0)
 
 }  // namespace pd
@@ -239,10 +252,11 @@ extern "C" int pd_decoder_tail_fwd(int B, int N, int H, int W, int flags, const 
   PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || sigma, "mixture needs the sigma output");
   PD_REQUIRE(!padding_mask || logits, "a padding mask needs the logits output");
   const TailArgs a = tail_args(N, H, W, flags, raw_logits, raw_sigma, padding_mask, disp_layered);
-  const int px = tail_px(H, W, {raw_logits, raw_sigma, padding_mask, a.dense ? disp_layered : nullptr, logits, sigma,
-                                disp, depth, stash});
+  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
+  const int px = tail_px(H, W, {padding_mask, a.dense ? disp_layered : nullptr, disp, depth, stash},
+                         {raw_logits, raw_sigma, logits, sigma}, bf16);
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  PD_TAIL_DISPATCH(tail_fwd_kernel, px, a.mix, padding_mask != nullptr, grid, 0, (hipStream_t)stream, a, logits, sigma,
+  PD_TAIL_DISPATCH(tail_fwd_kernel, bf16, px, a.mix, padding_mask != nullptr, grid, 0, (hipStream_t)stream, a, logits, sigma,
                    disp, depth, stash);
   return check_launch("tail_fwd_kernel");
 }
@@ -253,9 +267,10 @@ extern "C" int pd_decoder_tail_layers(int B, int N, int H, int W, int flags, con
   if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, raw_logits)) return rc;
   PD_REQUIRE(stash && (pi || probability), "NULL pointer");
   const TailArgs a = tail_args(N, H, W, flags, raw_logits, raw_sigma, padding_mask, nullptr);
-  const int px = tail_px(H, W, {raw_logits, raw_sigma, padding_mask, stash, pi, probability});
+  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
+  const int px = tail_px(H, W, {padding_mask, stash, pi, probability}, {raw_logits, raw_sigma}, bf16);
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  PD_TAIL_DISPATCH(tail_layers_kernel, px, a.mix, padding_mask != nullptr, grid, 0, (hipStream_t)stream, a, stash, pi,
+  PD_TAIL_DISPATCH(tail_layers_kernel, bf16, px, a.mix, padding_mask != nullptr, grid, 0, (hipStream_t)stream, a, stash, pi,
                    probability);
   return check_launch("tail_layers_kernel");
 }
@@ -272,12 +287,13 @@ extern "C" int pd_decoder_tail_bwd(int B, int N, int H, int W, int flags, const 
   const bool reduce = g_disp_layered && !a.dense;
   PD_REQUIRE(!reduce || workspace, "per-plane disparity gradient needs the workspace");
   PD_REQUIRE((size_t)N * sizeof(float) <= 64 * 1024, "too many planes");
-  const int px = tail_px(H, W, {raw_logits, raw_sigma, padding_mask, a.dense ? disp_layered : nullptr, stash, disp,
-                                g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma,
-                                a.dense ? g_disp_layered : nullptr});
+  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
+  const int px = tail_px(H, W, {padding_mask, a.dense ? disp_layered : nullptr, stash, disp, g_disp, g_depth,
+                                a.dense ? g_disp_layered : nullptr},
+                         {raw_logits, raw_sigma, g_logits, g_sigma, g_raw_logits, g_raw_sigma}, bf16);
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
   const size_t shmem = reduce ? (size_t)N * sizeof(float) : 0;
-  PD_TAIL_DISPATCH(tail_bwd_kernel, px, a.mix, padding_mask != nullptr, grid, shmem, (hipStream_t)stream, a, stash, disp,
+  PD_TAIL_DISPATCH(tail_bwd_kernel, bf16, px, a.mix, padding_mask != nullptr, grid, shmem, (hipStream_t)stream, a, stash, disp,
                    g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
   if (int rc = check_launch("tail_bwd_kernel")) return rc;
   if (reduce) {

@@ -12,6 +12,9 @@
 // 1e-10), and sum_k g_p_k p_k is known in closed form — 0 with the mixture weights (d disp / d u_k = (d_k - disp) / S sums
 // to zero against u), g_disp * disp without — so the backward is one front-to-back pass too; the distance gradient
 // reaches disp_layered through the two depth layers it subtracts.
+// PD_TAIL_BF16: raw_logits / raw_sigma, logits / sigma and their gradients hold bf16 (storage type ST = Bf16; the rule of
+// pd_decoder_tail.hip: exact widening, the fp32 arithmetic in the same order, one rounding per bf16 output element); dists and
+// its gradient, the disparities and the per-pixel maps stay fp32.
 #include "pd_tail_common.h"
 
 namespace pd {
@@ -30,7 +33,7 @@ __device__ __forceinline__ Px<PX> plade_disp(const PladeArgs& a, int b, int n, l
   return a.dense ? ldv<PX>(a.dl + ((long)b * a.N + n) * a.HW + pix) : splat<PX>(a.dl[b * a.N + n]);
 }
 
-template <bool MIX, int PX>
+template <class ST, bool MIX, int PX>
 __global__ __launch_bounds__(kBlock) void plade_fwd_kernel(PladeArgs a, float* __restrict__ logits, float* __restrict__ dists,
                                                            float* __restrict__ sigma, float* __restrict__ disp,
                                                            float* __restrict__ depth, float* __restrict__ stash) {
@@ -46,8 +49,8 @@ __global__ __launch_bounds__(kBlock) void plade_fwd_kernel(PladeArgs a, float* _
   for (int n = 0; n < N; ++n) {
     const bool last = (n == N - 1);
     const Px<PX> dn = last ? dv : plade_disp<PX>(a, b, n + 1, pix);       // disparity of the NEXT plane
-    const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(a.raw_logits + ((long)b * (N - 1) + n) * a.HW + pix);
-    const Px<PX> rs = MIX ? ldv<PX>(a.raw_sigma + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
+    const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(elems<ST>(a.raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix);
+    const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
     Px<PX> o_l, o_t, o_s;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
@@ -73,9 +76,9 @@ __global__ __launch_bounds__(kBlock) void plade_fwd_kernel(PladeArgs a, float* _
       }
       zc[j] = zn;
     }
-    stv<PX>(logits + ((long)b * N + n) * a.HW + pix, o_l);
+    stv<PX>(elems<ST>(logits) + ((long)b * N + n) * a.HW + pix, o_l);
     if (!last) stv<PX>(dists + ((long)b * (N - 1) + n) * a.HW + pix, o_t);
-    if (MIX) stv<PX>(sigma + ((long)b * N + n) * a.HW + pix, o_s);
+    if (MIX) stv<PX>(elems<ST>(sigma) + ((long)b * N + n) * a.HW + pix, o_s);
     dv = dn;
   }
   Px<PX> o_disp, o_depth, o_sw;
@@ -92,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void plade_fwd_kernel(PladeArgs a, float* _
 }
 
 // pi and probability (plade_net.py:320, 330-333) for callers that want the tensors
-template <bool MIX, int PX>
+template <class ST, bool MIX, int PX>
 __global__ __launch_bounds__(kBlock) void plade_layers_kernel(PladeArgs a, const float* __restrict__ stash, float* __restrict__ pi,
                                                               float* __restrict__ prob) {
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
@@ -107,8 +110,8 @@ __global__ __launch_bounds__(kBlock) void plade_layers_kernel(PladeArgs a, const
   for (int n = 0; n < N; ++n) {
     const bool last = (n == N - 1);
     const Px<PX> dn = last ? dv : plade_disp<PX>(a, b, n + 1, pix);
-    const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(a.raw_logits + ((long)b * (N - 1) + n) * a.HW + pix);
-    const Px<PX> rs = MIX ? ldv<PX>(a.raw_sigma + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
+    const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(elems<ST>(a.raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix);
+    const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
     Px<PX> op, oq;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(kBlock) void plade_layers_kernel(PladeArgs a, const
   }
 }
 
-template <bool MIX, int PX>
+template <class ST, bool MIX, int PX>
 __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const float* __restrict__ stash, const float* __restrict__ disp,
                                                            const float* __restrict__ g_logits, const float* __restrict__ g_dists,
                                                            const float* __restrict__ g_sigma, const float* __restrict__ g_disp,
@@ -169,11 +172,11 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
     float gd_sum = 0.0f;
     if (active) {
       const Px<PX> dn = last ? dv : plade_disp<PX>(a, b, n + 1, px0);
-      const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(a.raw_logits + ((long)b * (N - 1) + n) * a.HW + pix);
-      const Px<PX> rs = MIX ? ldv<PX>(a.raw_sigma + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
-      const Px<PX> gl = (g_logits && !last) ? ldv<PX>(g_logits + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
+      const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(elems<ST>(a.raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix);
+      const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
+      const Px<PX> gl = (g_logits && !last) ? ldv<PX>(elems<ST>(g_logits) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
       const Px<PX> gt = (g_dists && !last) ? ldv<PX>(g_dists + ((long)b * (N - 1) + n) * a.HW + pix) : splat<PX>(0.0f);
-      const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(g_sigma + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
+      const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(elems<ST>(g_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
       Px<PX> o_l, o_s, o_d;
 #pragma unroll
       for (int j = 0; j < PX; ++j) {
@@ -216,8 +219,8 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
         gprev[j] = g_dist;
         zc[j] = zn;
       }
-      if (g_raw_logits && !last) stv<PX>(g_raw_logits + ((long)b * (N - 1) + n) * a.HW + pix, o_l);
-      if (MIX && g_raw_sigma) stv<PX>(g_raw_sigma + ((long)b * N + n) * a.HW + pix, o_s);
+      if (g_raw_logits && !last) stv<PX>(elems<ST>(g_raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix, o_l);
+      if (MIX && g_raw_sigma) stv<PX>(elems<ST>(g_raw_sigma) + ((long)b * N + n) * a.HW + pix, o_s);
       if (g_dl && a.dense) stv<PX>(g_dl + ((long)b * N + n) * a.HW + pix, o_d);
       dv = dn;
     }
@@ -237,7 +240,7 @@ static int plade_validate(int B, int N, int H, int W, int flags, const float* ra
                           const float* dl, const float* ray) {
   PD_REQUIRE(B > 0 && B <= 65535 && N >= 2 && H > 0 && W > 0, "bad shape (alpha compositing needs N >= 2 planes)");
   PD_REQUIRE((long)H * W < (1L << 31), "image too large");
-  PD_REQUIRE((flags & ~(PD_TAIL_MIXTURE | PD_TAIL_DISP_DENSE)) == 0, "unknown flags");
+  PD_REQUIRE((flags & ~(PD_TAIL_MIXTURE | PD_TAIL_DISP_DENSE | PD_TAIL_BF16)) == 0, "unknown flags");
   PD_REQUIRE(raw_logits && dl && ray, "NULL pointer");
   PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || raw_sigma, "mixture needs raw_sigma");
   return 0;
@@ -253,12 +256,17 @@ static PladeArgs plade_args(int N, int H, int W, int flags, const float* raw_log
   return a;
 }
 
-#define PD_PLADE_DISPATCH(KERNEL, px, mix, grid, shmem, stream, ...)                                        \
+#define PD_PLADE_DISPATCH_T(KERNEL, T, px, mix, grid, shmem, stream, ...)                                   \
   do {                                                                                                       \
-    if ((px) == 4) { if (mix) KERNEL<true, 4><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                 \
-                     else     KERNEL<false, 4><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__); }              \
-    else           { if (mix) KERNEL<true, 1><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                 \
-                     else     KERNEL<false, 1><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__); }              \
+    if ((px) == 4) { if (mix) KERNEL<T, true, 4><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);              \
+                     else     KERNEL<T, false, 4><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__); }           \
+    else           { if (mix) KERNEL<T, true, 1><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);              \
+                     else     KERNEL<T, false, 1><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__); }           \
+  } while (0)
+#define PD_PLADE_DISPATCH(KERNEL, bf16, px, mix, grid, shmem, stream, ...)                                  \
+  do {                                                                                                       \
+    if (bf16) PD_PLADE_DISPATCH_T(KERNEL, Bf16, px, mix, grid, shmem, stream, __VA_ARGS__);                  \
+    else      PD_PLADE_DISPATCH_T(KERNEL, float, px, mix, grid, shmem, stream, __VA_ARGS__);                 \
   } while (0)
 
 }  // namespace pd
@@ -272,10 +280,11 @@ extern "C" int pd_plade_tail_fwd(int B, int N, int H, int W, int flags, const fl
   PD_REQUIRE(logits && dists && disp && depth && stash, "NULL output");
   PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || sigma, "mixture needs the sigma output");
   const PladeArgs a = plade_args(N, H, W, flags, raw_logits, raw_sigma, disp_layered, ray_norm);
-  const int px = tail_px(H, W, {raw_logits, raw_sigma, a.dense ? disp_layered : nullptr, ray_norm, logits, dists, sigma, disp,
-                                depth, stash});
+  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
+  const int px = tail_px(H, W, {a.dense ? disp_layered : nullptr, ray_norm, dists, disp, depth, stash},
+                         {raw_logits, raw_sigma, logits, sigma}, bf16);
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  PD_PLADE_DISPATCH(plade_fwd_kernel, px, a.mix, grid, 0, (hipStream_t)stream, a, logits, dists, sigma, disp, depth, stash);
+  PD_PLADE_DISPATCH(plade_fwd_kernel, bf16, px, a.mix, grid, 0, (hipStream_t)stream, a, logits, dists, sigma, disp, depth, stash);
   return check_launch("plade_fwd_kernel");
 }
 
@@ -285,9 +294,10 @@ extern "C" int pd_plade_tail_layers(int B, int N, int H, int W, int flags, const
   if (int rc = plade_validate(B, N, H, W, flags, raw_logits, raw_sigma, disp_layered, ray_norm)) return rc;
   PD_REQUIRE(stash && (pi || probability), "NULL pointer");
   const PladeArgs a = plade_args(N, H, W, flags, raw_logits, raw_sigma, disp_layered, ray_norm);
-  const int px = tail_px(H, W, {raw_logits, raw_sigma, a.dense ? disp_layered : nullptr, ray_norm, stash, pi, probability});
+  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
+  const int px = tail_px(H, W, {a.dense ? disp_layered : nullptr, ray_norm, stash, pi, probability}, {raw_logits, raw_sigma}, bf16);
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  PD_PLADE_DISPATCH(plade_layers_kernel, px, a.mix, grid, 0, (hipStream_t)stream, a, stash, pi, probability);
+  PD_PLADE_DISPATCH(plade_layers_kernel, bf16, px, a.mix, grid, 0, (hipStream_t)stream, a, stash, pi, probability);
   return check_launch("plade_layers_kernel");
 }
 
@@ -303,11 +313,13 @@ extern "C" int pd_plade_tail_bwd(int B, int N, int H, int W, int flags, const fl
   const bool reduce = g_disp_layered && !a.dense;
   PD_REQUIRE(!reduce || workspace, "per-plane disparity gradient needs the workspace (pd_decoder_tail_bwd_workspace_floats)");
   PD_REQUIRE((size_t)N * sizeof(float) <= 64 * 1024, "too many planes");
-  const int px = tail_px(H, W, {raw_logits, raw_sigma, a.dense ? disp_layered : nullptr, ray_norm, stash, disp, g_logits, g_dists,
-                                g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, a.dense ? g_disp_layered : nullptr});
+  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
+  const int px = tail_px(H, W, {a.dense ? disp_layered : nullptr, ray_norm, stash, disp, g_dists, g_disp, g_depth,
+                                a.dense ? g_disp_layered : nullptr},
+                         {raw_logits, raw_sigma, g_logits, g_sigma, g_raw_logits, g_raw_sigma}, bf16);
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
   const size_t shmem = reduce ? (size_t)N * sizeof(float) : 0;
-  PD_PLADE_DISPATCH(plade_bwd_kernel, px, a.mix, grid, shmem, (hipStream_t)stream, a, stash, disp, g_logits, g_dists, g_sigma,
+  PD_PLADE_DISPATCH(plade_bwd_kernel, bf16, px, a.mix, grid, shmem, (hipStream_t)stream, a, stash, disp, g_logits, g_dists, g_sigma,
                     g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
   if (int rc = check_launch("plade_bwd_kernel")) return rc;
   if (reduce) {

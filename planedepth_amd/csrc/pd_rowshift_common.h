@@ -132,11 +132,7 @@ __device__ __forceinline__ float* plane_ptr(float* image_base, int n, int HW) {
 }
 
 // Storage type of the [B,N,H,W] tensors logits / sigma / g_logits / g_sigma: float, or bf16 bit patterns (PD_LOGITS_BF16) held
-// as `Bf16`.  The arithmetic is fp32 either way: a bf16 element widens exactly on load, and a gradient element is rounded to
-// bf16 once, from the fp32 value that holds all of its contributions (pack_bf16x2: v_cvt_pk_bf16_f32, round to nearest even).
-typedef unsigned short Bf16;
-template <class T> __device__ __forceinline__ const T* elems(const float* p) { return reinterpret_cast<const T*>(p); }
-template <class T> __device__ __forceinline__ T* elems(float* p) { return reinterpret_cast<T*>(p); }
+// as `Bf16` (pd_common.h, with elems, bf16_lo / bf16_hi and pack_bf16x2: the decoder tails use them too).
 template <class T> __device__ __forceinline__ const T* plane_ptr_t(const T* image_base, int n, int HW) {
   return image_base + (unsigned)(n * HW);
 }
@@ -144,19 +140,12 @@ template <class T> __device__ __forceinline__ T* plane_ptr_t(T* image_base, int 
 template <class T> __device__ __forceinline__ Rsrc row_rsrc_t(const T* row, int W) {   // `row` must be wave-uniform
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(row), 0, W * (int)sizeof(T), 0x00020000);
 }
-__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }           // element 2j of a dword
-__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }   // element 2j + 1
 __device__ __forceinline__ float elem_f32(const float* p, long i) { return p[i]; }
 __device__ __forceinline__ float elem_f32(const Bf16* p, long i) { return __uint_as_float((unsigned)p[i] << 16); }
 // one element at column `col` through a row descriptor (range-checked like buf_load)
 __device__ __forceinline__ float buf_load_elem(Rsrc r, int col, float*) { return buf_load(r, (unsigned)col << 2); }
 __device__ __forceinline__ float buf_load_elem(Rsrc r, int col, Bf16*) {
   return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, (int)((unsigned)col << 1), 0, 0) << 16);
-}
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-  unsigned w;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(lo), "v"(hi));
-  return w;
 }
 
 // The (up to) four taps of one scalar plane, loaded up-front.  Out-of-image taps come back as 0 from the hardware.

@@ -22,6 +22,16 @@ padding mask has N channels, ``dispconv`` N-1).  The live producer of ``outputs[
     from planedepth_amd.decoder_tail import fused_plade_tail
     fused_plade_tail(self.outputs, self.conv0(dlog), self.conv_sigma(features) if self.use_mixture_loss else None,
                      use_mixture_loss=self.use_mixture_loss)
+
+Mixed precision.  Under ``torch.autocast("cuda", dtype=torch.bfloat16)`` the convolutions emit bf16, and both tails take it as
+it is (``PD_TAIL_BF16``; no ``.float()`` on the conv outputs, which would bring the [B,N,H,W] fp32 activations and gradients
+back).  ``outputs["logits"]`` / ``["sigma"]`` are then bf16 — what the plane sweep reads natively — and so
+are the gradients handed back to the convolutions; ``disp``, ``depth``, ``dists``, ``pi`` and ``probability`` stay fp32.
+The arithmetic is the fp32 kernels' on the exactly widened inputs, and every bf16 element is rounded once from its fp32
+value.  One deliberate difference from the reference under autocast, which would carry a bf16-rounded sigma into
+``probability``: here ``disp`` / ``depth`` / ``probability`` use the unrounded fp32 sigma, and ``outputs["sigma"]`` is that
+sigma rounded once (never below the sweep's clamp: bf16(0.01) >= 0.01).  Both conv outputs must have one dtype; fp16 and a
+bf16 / fp32 mix raise ``TypeError``.
 """
 import torch
 
@@ -81,7 +91,9 @@ def fused_decoder_tail(outputs, dispconv_out, sigmaconv_out=None, *, use_mixture
     then applies this tail's backward on the values it holds anyway and writes the conv outputs' gradients directly
     (``ops.TailLink``, ``pd_plane_sweep_bwd_tail``); the tail's own backward kernel, which re-reads the [B,N,H,W]-sized
     gradients the sweep has just written, no longer runs.  NOT detected: another differentiable consumer of ``outputs["sigma"]``
-    (a regulariser) — its gradient would be added, in sigma space, to one already in conv-output space; keep the flag off then."""
+    (a regulariser) — its gradient would be added, in sigma space, to one already in conv-output space; keep the flag off then.
+    With bf16 conv outputs (autocast) the flag is accepted and no link is made: the sweep's fused backward has no bf16 form, so
+    the sweep's native bf16 backward and then this tail's run as two kernels, with the results of ``fuse_sweep_backward=False``."""
     mask = None if all_ones_mask else outputs["padding_mask"]
     logits, sigma, disp, depth, layers = ops.decoder_tail(dispconv_out, sigmaconv_out, mask, outputs["disp_layered"],
                                                           use_mixture_loss=use_mixture_loss,
@@ -96,7 +108,7 @@ def fused_decoder_tail(outputs, dispconv_out, sigmaconv_out=None, *, use_mixture
         if use_mixture_loss:
             outputs["pi"] = pi
     else:
-        dev, dt = dispconv_out.device, dispconv_out.dtype
+        dev, dt = dispconv_out.device, torch.float32    # (pi / probability are fp32 with bf16 conv outputs too)
         outputs["probability"] = LazyLayers(shape, lambda: layers(False, True)[1], dev, dt)
         if use_mixture_loss:
             outputs["pi"] = LazyLayers(shape, lambda: layers(True, False)[0], dev, dt)
@@ -124,7 +136,7 @@ def fused_plade_tail(outputs, conv0_out, conv_sigma_out=None, *, use_mixture_los
         if use_mixture_loss:
             outputs["pi"] = pi
     else:
-        dev, dt = conv0_out.device, conv0_out.dtype
+        dev, dt = conv0_out.device, torch.float32
         outputs["probability"] = LazyLayers(shape, lambda: layers(False, True)[1], dev, dt)
         if use_mixture_loss:
             outputs["pi"] = LazyLayers(shape, lambda: layers(True, False)[0], dev, dt)

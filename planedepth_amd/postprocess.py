@@ -79,13 +79,19 @@ def post_process_disp(logits, probability, disp, disp_layered, row_uniform=False
     """trainer.py:421-466 given the fixed model's outputs for cat([image, mirrored image]) -> (disp_pp, mask_novel): ONE C-ABI
     call (pd_post_process: row chains where a row's softmax fits the CU's LDS, else two warp-softmaxes, three warp-sums and the
     blend).  ``row_uniform=True`` promises a dense ``disp_layered`` that is constant along x (no yz planes): it is then read as
-    one disparity per (plane, row) and the row kernels / chains serve it instead of the per-pixel gather form."""
+    one disparity per (plane, row) and the row kernels / chains serve it instead of the per-pixel gather form.
+    bf16 ``logits`` / ``probability`` (a teacher run under ``torch.autocast``) are widened with ``.float()`` first — exact, and
+    no native bf16 kernel yet; any other dtype raises."""
     lib = C.load()
-    C.require_gpu_tensor("logits", logits)
+    C.require_gpu_tensor("logits", logits, dtype=torch.bfloat16 if logits.dtype == torch.bfloat16 else torch.float32)
     B2, N, H, W = logits.shape
     B = B2 // 2
     with torch.no_grad():
         prob = probability.tensor() if hasattr(probability, "tensor") else probability
+        if logits.dtype == torch.bfloat16:
+            logits = logits.float()
+        if torch.is_tensor(prob) and prob.dtype == torch.bfloat16:
+            prob = prob.float()
         logits, prob, disp = (_contig(t.detach()) for t in (logits, prob, disp))
         dl, flags = _pp_disp(disp_layered.detach(), B2, N, H, W, row_uniform)
         dev = logits.device

@@ -9,6 +9,27 @@ from . import _state as S
 from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, _plane_grad_buffer
 from .sweep import TailLink, _per_plane_view
 
+
+def _storage_flag(raw_logits, raw_sigma, mix):
+    """PD_TAIL_BF16 or 0 from the conv outputs' dtype: fp32, or bf16 as ``torch.autocast`` emits it (the kernels read and write
+    bf16 natively then).  Anything else — and a mixture whose two conv outputs disagree — is a TypeError: no widening copy, no
+    torch fall-back."""
+    for name, t in (("raw_logits", raw_logits),) + ((("raw_sigma", raw_sigma),) if mix else ()):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor" % name)
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("%s must be torch.float32 or torch.bfloat16, got %s" % (name, t.dtype))
+    if mix and raw_sigma.dtype != raw_logits.dtype:
+        raise TypeError("raw_logits and raw_sigma must have one dtype, got %s and %s" % (raw_logits.dtype, raw_sigma.dtype))
+    return C.PD_TAIL_BF16 if raw_logits.dtype == torch.bfloat16 else 0
+
+
+def _storage_grad(name, g, dtype):
+    """An upstream gradient of a storage-typed output (logits / sigma) arrives in that output's dtype."""
+    if g is not None and g.dtype != dtype:
+        raise TypeError("%s must be %s, got %s" % (name, dtype, g.dtype))
+    return g
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Decoder tail (SURVEY.md 8f rank 1)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -21,17 +42,18 @@ class _DecoderTail(torch.autograd.Function):
         B, N, H, W = raw_logits.shape
         mix = bool(flags & C.PD_TAIL_MIXTURE)
         ctx.link = link
-        C.require_gpu_tensor("raw_logits", raw_logits)
+        st = raw_logits.dtype   # storage type of logits / sigma and their gradients (decoder_tail checked it: PD_TAIL_BF16)
+        C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
         if mix:
-            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W))
+            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
         C.require_gpu_tensor("disp_layered", disp_layered, (B, N, H, W) if flags & C.PD_TAIL_DISP_DENSE else (B, N))
         if padding_mask is not None:
             C.require_gpu_tensor("padding_mask", padding_mask, (B, N, H, W))
         raw_logits, raw_sigma, disp_layered, padding_mask = map(_contig, (raw_logits, raw_sigma, disp_layered, padding_mask))
         dev = raw_logits.device
-        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
-        logits = new(B, N, H, W) if padding_mask is not None else None
-        sigma = new(B, N, H, W) if mix else None
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)  # noqa: E731
+        logits = new(B, N, H, W, dtype=st) if padding_mask is not None else None
+        sigma = new(B, N, H, W, dtype=st) if mix else None
         disp, depth, stash = new(B, 1, H, W), new(B, 1, H, W), new(B, 2, H, W)
         with C.on_device(dev), _timed("tail_fwd"):
             C.check(lib.pd_decoder_tail_fwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(padding_mask),
@@ -91,6 +113,8 @@ class _DecoderTail(torch.autograd.Function):
             ws = torch.empty(lib.pd_decoder_tail_bwd_workspace_floats(B, N, H, W), device=raw_logits.device,
                              dtype=torch.float32)
         g_logits, g_sigma, g_disp, g_depth = map(_contig, (g_logits, g_sigma if mix else None, g_disp, g_depth))
+        _storage_grad("g_logits", g_logits, raw_logits.dtype)
+        _storage_grad("g_sigma", g_sigma, raw_logits.dtype)
         with C.on_device(raw_logits.device), _timed("tail_bwd"):
             C.check(lib.pd_decoder_tail_bwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(padding_mask),
                                             C.ptr(disp_layered), C.ptr(stash), C.ptr(disp), C.ptr(g_logits),
@@ -111,13 +135,20 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     Returns (logits, sigma | None, disp, depth, layers) where ``layers()`` materialises ``(pi, probability)`` on demand
     (no gradient: nothing in the reference's losses reads them).  ``disp_layered`` may be the decoder's expanded view of
     per-plane scalars or a dense map; ``padding_mask=None`` means all ones (xy planes only).
+
+    ``raw_logits`` / ``raw_sigma`` are fp32, or both bf16 (``torch.autocast``: PD_TAIL_BF16).  ``logits`` / ``sigma`` and the
+    conv outputs' gradients then are bf16 too, each element rounded once from the fp32 value; ``disp``, ``depth``, ``pi`` and
+    ``probability`` stay fp32 and come from the unrounded fp32 sigma (the fp32 route on the widened inputs).  With bf16,
+    ``fuse_sweep_backward`` takes no tail link: the sweep's bf16 backward and this tail's run as two kernels, with the results of
+    ``fuse_sweep_backward=False``.
     """
     B, N, H, W = raw_logits.shape
+    bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
     if tuple(disp_layered.shape) != (B, N, H, W):
         disp_layered = disp_layered.expand(B, N, H, W)
     per_plane = disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
     plane = _per_plane_view(disp_layered) if per_plane else disp_layered
-    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | (0 if per_plane else C.PD_TAIL_DISP_DENSE)
+    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | (0 if per_plane else C.PD_TAIL_DISP_DENSE) | bf16
     if padding_mask is not None:
         if padding_mask.dtype != torch.float32:
             padding_mask = padding_mask.float()
@@ -129,8 +160,9 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     # of ``sigma`` (a regulariser on outputs["sigma"]) is NOT detected: its gradient would arrive in sigma space on top of one
     # the sweep already wrote in conv-output space, without the sigmoid' factor and the clamp gate.  (``logits`` are safe:
     # d logits / d raw_logits is the identity here.)  Leave the flag off for such a graph.
+    # bf16 conv outputs: no link (the row-stream backward's tail form has no bf16 instantiation); two kernels, the same results.
     link = TailLink(None, None, None) if (fuse_sweep_backward and use_mixture_loss and padding_mask is None and per_plane
-                                           and torch.is_grad_enabled()) else None
+                                           and not bf16 and torch.is_grad_enabled()) else None
     logits, sigma, disp, depth, stash = _DecoderTail.apply(raw_logits, raw_sigma if use_mixture_loss else None, plane,
                                                            padding_mask, flags, link)
     if link is not None:
@@ -140,8 +172,8 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     def layers(want_pi=True, want_probability=True):
         lib = C.load()
         with torch.no_grad():
-            pi = torch.empty_like(raw_logits) if want_pi else None
-            prob = torch.empty_like(raw_logits) if want_probability else None
+            pi = torch.empty_like(raw_logits, dtype=torch.float32) if want_pi else None     # (fp32 with bf16 conv outputs too)
+            prob = torch.empty_like(raw_logits, dtype=torch.float32) if want_probability else None
             rl, rs, pm = map(_contig, (raw_logits.detach(), raw_sigma.detach() if use_mixture_loss else None, padding_mask))
             with C.on_device(raw_logits.device):
                 C.check(lib.pd_decoder_tail_layers(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pm), C.ptr(stash),
@@ -161,16 +193,17 @@ class _PladeTail(torch.autograd.Function):
         B, Nm1, H, W = raw_logits.shape
         N = Nm1 + 1
         mix = bool(flags & C.PD_TAIL_MIXTURE)
-        C.require_gpu_tensor("raw_logits", raw_logits)
+        st = raw_logits.dtype   # storage type of logits / sigma and their gradients (plade_tail checked it: PD_TAIL_BF16)
+        C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
         if mix:
-            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W))
+            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
         C.require_gpu_tensor("disp_layered", disp_layered, (B, N, H, W) if flags & C.PD_TAIL_DISP_DENSE else (B, N))
         C.require_gpu_tensor("ray_norm", ray_norm, (H, W))
         raw_logits, raw_sigma, disp_layered, ray_norm = map(_contig, (raw_logits, raw_sigma, disp_layered, ray_norm))
         dev = raw_logits.device
-        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
-        logits, dists = new(B, N, H, W), new(B, N - 1, H, W)
-        sigma = new(B, N, H, W) if mix else None
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)  # noqa: E731
+        logits, dists = new(B, N, H, W, dtype=st), new(B, N - 1, H, W)
+        sigma = new(B, N, H, W, dtype=st) if mix else None
         disp, depth, stash = new(B, 1, H, W), new(B, 1, H, W), new(B, 1, H, W)
         with C.on_device(dev):
             C.check(lib.pd_plade_tail_fwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(disp_layered),
@@ -202,6 +235,8 @@ class _PladeTail(torch.autograd.Function):
         if need_d and not (flags & C.PD_TAIL_DISP_DENSE):
             ws = torch.empty(lib.pd_decoder_tail_bwd_workspace_floats(B, N, H, W), device=raw_logits.device, dtype=torch.float32)
         g_logits, g_dists, g_sigma, g_disp, g_depth = map(_contig, (g_logits, g_dists, g_sigma if mix else None, g_disp, g_depth))
+        _storage_grad("g_logits", g_logits, raw_logits.dtype)
+        _storage_grad("g_sigma", g_sigma, raw_logits.dtype)
         with C.on_device(raw_logits.device):
             C.check(lib.pd_plade_tail_bwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(disp_layered),
                                           C.ptr(ray_norm), C.ptr(stash), C.ptr(disp), C.ptr(g_logits), C.ptr(g_dists),
@@ -237,14 +272,16 @@ def plade_tail(raw_logits, raw_sigma, disp_layered, ray_norm=None, use_mixture_l
     ``raw_logits`` [B,N-1,H,W] = conv0's output, ``raw_sigma`` [B,N,H,W] = conv_sigma's (mixture only), ``disp_layered`` the
     network's expanded view of per-plane scalars or a dense map (ground planes).  Returns (logits [B,N,H,W], dists
     [B,N-1,H,W], sigma | None, disp, depth, layers) where ``layers()`` materialises ``(pi, probability)`` on demand (no
-    gradient: nothing in the reference's losses reads them)."""
+    gradient: nothing in the reference's losses reads them).  bf16 conv outputs (``torch.autocast``) are taken natively under the
+    rule of ``decoder_tail``: ``logits`` / ``sigma`` and the conv outputs' gradients are bf16, ``dists`` and the rest fp32."""
     B, Nm1, H, W = raw_logits.shape
     N = Nm1 + 1
+    bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
     if tuple(disp_layered.shape) != (B, N, H, W):
         disp_layered = disp_layered.expand(B, N, H, W)
     per_plane = disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
     plane = _per_plane_view(disp_layered) if per_plane else disp_layered
-    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | (0 if per_plane else C.PD_TAIL_DISP_DENSE)
+    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | (0 if per_plane else C.PD_TAIL_DISP_DENSE) | bf16
     if ray_norm is None:
         ray_norm = camera_ray_norm(H, W, raw_logits.device)
     logits, dists, sigma, disp, depth, stash = _PladeTail.apply(raw_logits, raw_sigma if use_mixture_loss else None, plane,
@@ -253,8 +290,8 @@ def plade_tail(raw_logits, raw_sigma, disp_layered, ray_norm=None, use_mixture_l
     def layers(want_pi=True, want_probability=True):
         lib = C.load()
         rl, rs, pl = _contig(raw_logits.detach()), _contig(raw_sigma.detach()) if use_mixture_loss else None, _contig(plane.detach())
-        pi = torch.empty(B, N, H, W, device=rl.device) if want_pi else None
-        prob = torch.empty(B, N, H, W, device=rl.device) if want_probability else None
+        pi = torch.empty(B, N, H, W, device=rl.device, dtype=torch.float32) if want_pi else None
+        prob = torch.empty(B, N, H, W, device=rl.device, dtype=torch.float32) if want_probability else None
         with C.on_device(rl.device):
             C.check(lib.pd_plade_tail_layers(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pl), C.ptr(ray_norm), C.ptr(stash),
                                              C.ptr(pi), C.ptr(prob), C.stream_handle(rl.device)), "pd_plade_tail_layers")

@@ -246,7 +246,9 @@ def compute_losses(self, inputs, outputs):
 def generate_post_process_disp(self, inputs):
     """Self-distillation targets (reference trainer.py:404-466): run the FIXED networks on cat([image, mirrored image])
     exactly as the reference does (:405-419 — the networks are the reference's own, untouched), then the occlusion-aware
-    blend of the two predictions through the fused warp kernels instead of five grid_samples."""
+    blend of the two predictions through the fused warp kernels instead of five grid_samples.  A teacher run under
+    ``torch.autocast`` may hand over bf16 ``logits`` (the fused tail's, or the stock decoder's): ``ops.post_process_disp`` widens
+    them; the maps come back in fp32."""
     opt = self.opt
     image = inputs[("color_aug", "l")]
     input_images = ops.cat_flip(image, image)                                  # [image ; mirrored image]
