@@ -306,8 +306,29 @@ int pd_mixture_nll_bwd(int B, int N, int H, int W, int laplacian, const float* e
  * falls below the sweep's clamp), and bwd decides the clamp gate in fp32 on the sigmoid it recomputes from raw_sigma.
  * NULL and shape checks are the same with and without the flag; bf16 tensors need 2-byte alignment only (8-byte alignment of
  * all of them, 16-byte of the fp32 ones, and H*W % 4 == 0 select the form with 4 pixels per lane).
+ *
+ * Row form (fwd, layers and bwd of the decoder tail, fp32 and PD_TAIL_BF16; the PladeNet tail does not take it).  xy and xz
+ * planes have a disparity and a padding mask that are constant along x (depth_decoder.py:153-181; pd_plane_geometry_fwd makes
+ * them in this form):
+ *   PD_TAIL_DISP_ROWS   disp_layered is [B,N,H] and g_disp_layered is written as [B,N,H]: g[b,n,y] = the sum over x of what the
+ *                       dense form writes, reduced on the device by the workgroup that owns row y — no atomics, no workspace,
+ *                       the same bits on every run.  Refused together with PD_TAIL_DISP_DENSE.
+ *   PD_TAIL_MASK_ROWS   padding_mask is [B,N,H].  Refused with a NULL mask.
+ *                       (A NULL-pointer refusal under either flag names the flag and the layout it announces.)
+ * Either flag may stand alone (a dense map next to a row mask, and the reverse).  Per pixel the arithmetic and its order are
+ * the dense form's on the expanded values: fwd's outputs, pi / probability and g_raw_logits / g_raw_sigma have the dense
+ * route's bits.  The row tensors are read one scalar per plane and row and need 4-byte alignment only.  4 pixels per lane are
+ * taken for a row form only when additionally W % 4 == 0, so that a group of 4 never straddles two rows (H = 2, W = 6 has
+ * H*W % 4 == 0 and would); every other width runs one pixel per lane.
+ * pd_decoder_tail_bwd_workspace_floats is the per-plane form's need and the maximum over the forms (dense and rows: none).
  */
-enum pd_tail_flags { PD_TAIL_MIXTURE = 1, PD_TAIL_DISP_DENSE = 2, PD_TAIL_BF16 = 4 };
+enum pd_tail_flags {
+  PD_TAIL_MIXTURE = 1,
+  PD_TAIL_DISP_DENSE = 2,
+  PD_TAIL_BF16 = 4,
+  PD_TAIL_DISP_ROWS = 8,
+  PD_TAIL_MASK_ROWS = 16
+};
 size_t pd_decoder_tail_bwd_workspace_floats(int B, int N, int H, int W);
 int pd_decoder_tail_fwd(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
                         const float* padding_mask, const float* disp_layered, float* logits, float* sigma, float* disp,
@@ -427,6 +448,36 @@ int pd_plane_levels_fwd(int M, int no_levels, float disp_min, float disp_max, fl
                         float* distance, pd_stream_t stream);
 int pd_plane_levels_bwd(int M, int no_levels, float disp_min, float disp_max, float dist_num, const float* disp,
                         const float* g_disp, const float* g_distance, float* g_levels, pd_stream_t stream);
+
+/*
+ * The geometry head of DepthDecoder.forward without yz planes (networks/depth_decoder.py:148-207) in ROW form, one launch each
+ * way.  N = no_levels + xz_levels planes: no_levels fronto-parallel (xy) planes and xz_levels ground (xz) planes.
+ *   residual [B,N]   sigmoid(residualconv) - 0.5 (:151); NULL without --plane_residual (all zeros)
+ *   grid [B,2,H,W]   inputs["grid"]; read are grid[b,1,y,0] (the row's y coordinate), grid[b,0,y,0] and grid[b,0,y,W-1] (its x
+ *                    extent, :172) and the corners grid[b,1,0,0], grid[b,1,H-1,0], grid[b,0,0,0], grid[b,0,0,W-1] (:197-199).  The
+ *                    y channel is taken to be constant along x, which holds for every grid datasets/pair_transforms.py makes; a
+ *                    sheared or rotated grid must keep the reference's dense lines.
+ * fwd writes
+ *   disp_rows [B,N,H]   xy: disp_max * (disp_min / disp_max) ** ((n + residual) / (no_levels - 1)) on every row (:153);
+ *                       xz: 0.1 * 0.58 * W / ((x_last - x_first) / 2 * (h * 1.92 / (max(y, 1e-7) / 2))) with the height
+ *                       h = xz_min + (xz_max - xz_min) * (m + residual) / (xz_levels - 1) (:163-181)
+ *   mask_rows [B,N,H]   float 0 / 1: ones for xy, y >= 1e-7 for xz (:168, decided on the fp32 grid value)
+ *   distance [B,N]      0.1 * 0.58 * W / disp (xy, :154); h / sqrt(1 + t^2) (xz, :204), t the principal point's offset (:197-200)
+ *   norm [B,N,3]        [0,0,1] (xy); [0, 1, t] / sqrt(1 + t^2) (xz, :201-203)
+ * in fp32 and the reference's operation order (no contraction), as pd_plane_levels does for :153-154; xz_levels == 0 gives
+ * pd_plane_levels' values on every row.  mask_rows / distance / norm may be NULL (skipped).
+ * bwd: upstream g_disp_rows [B,N,H] and g_distance [B,N] (either may be NULL = zero, not both), the forward's residual, grid and
+ * disp_rows -> g_residual [B,N].  norm and mask_rows carry no gradient.  One wave per (image, plane) adds the rows in a fixed
+ * order: no atomics, the same bits on every run.
+ * Refused: no_levels < 2, xz_levels == 1 or < 0 (the reference divides by levels - 1), flags != 0 (none defined yet), NULL
+ * pointers, bwd with a NULL residual.
+ */
+int pd_plane_geometry_fwd(int B, int no_levels, int xz_levels, int H, int W, int flags, float disp_min, float disp_max,
+                          float xz_min, float xz_max, const float* residual, const float* grid, float* disp_rows,
+                          float* mask_rows, float* distance, float* norm, pd_stream_t stream);
+int pd_plane_geometry_bwd(int B, int no_levels, int xz_levels, int H, int W, int flags, float disp_min, float disp_max,
+                          float xz_min, float xz_max, const float* residual, const float* grid, const float* disp_rows,
+                          const float* g_disp_rows, const float* g_distance, float* g_residual, pd_stream_t stream);
 
 /*
  * Photometric loss under the occlusion mask `mask_novel` (trainer.py:724-742; the mask is produced after

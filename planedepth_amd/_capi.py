@@ -21,6 +21,7 @@ PD_LOGITS_BF16 = 2048   # logits / sigma / g_logits / g_sigma hold bf16 (pd_swee
 PD_PAD_ZEROS, PD_PAD_BORDER = 0, 1
 PD_TAIL_MIXTURE, PD_TAIL_DISP_DENSE = 1, 2
 PD_TAIL_BF16 = 4   # raw_logits / raw_sigma / logits / sigma and their gradients hold bf16 (both decoder tails)
+PD_TAIL_DISP_ROWS, PD_TAIL_MASK_ROWS = 8, 16   # disp_layered (and its gradient) / padding_mask are [B,N,H] (decoder tail only)
 PD_PP_DISP_DENSE, PD_PP_FLIP_SRC, PD_PP_DISP_ROWS = 1, 2, 4
 PD_HMAT_PLANES, PD_HMAT_UNIFORM, PD_HMAT_STEREO_ROWS = 0, 1, 2
 PD_IMPL_AUTO, PD_IMPL_GENERAL, PD_IMPL_FAST_ROWS, PD_IMPL_TILE, PD_IMPL_ROWS1, PD_IMPL_UNIFORM_DIRECT = 0, 1, 2, 3, 4, 5
@@ -102,6 +103,8 @@ SIGNATURES = {
     "pd_cat_flip": (_I, [_I] * 4 + [_P, _P, _I, _P, _P]),
     "pd_plane_levels_fwd": (_I, [_I, _I, _F, _F, _F, _P, _P, _P, _P]),
     "pd_plane_levels_bwd": (_I, [_I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "pd_plane_geometry_fwd": (_I, [_I] * 6 + [_F] * 4 + [_P] * 7),
+    "pd_plane_geometry_bwd": (_I, [_I] * 6 + [_F] * 4 + [_P] * 7),
     "pd_crop_grid": (_I, [_I] * 3 + [_P, _P, _P]),
     "pd_selftest_division": (_I, [_F, _I, _F, _F, _P, _P]),
     "pd_experiments": (_I, []),

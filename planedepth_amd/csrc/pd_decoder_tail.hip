@@ -15,6 +15,14 @@
 // element widens exactly on load, the arithmetic is the fp32 kernel's in the same order, and each bf16 output element is
 // rounded once from its fp32 value.  disp / depth / stash (and pi / probability) come from the UNROUNDED fp32 sigma; the
 // backward recomputes the sigmoid from raw_sigma, so its clamp gate is decided in fp32 as well.
+// Row form (PD_TAIL_DISP_ROWS / PD_TAIL_MASK_ROWS; template parameter RF = kRowDisp | kRowMask): xy and xz planes have a
+// disparity and a padding mask that are constant along x (depth_decoder.py:153-181), so disp_layered / padding_mask come as
+// [B,N,H] — one scalar load per plane and row instead of a [B,N,H,W] stream.  Per pixel the arithmetic is the dense kernels' on
+// the expanded values (same expressions, same order).  4 pixels per lane are taken for a row form only when W % 4 == 0: a
+// group of 4 then never straddles two rows (H*W % 4 == 0 alone does not give that: H = 2, W = 6) and one row value serves
+// the lane; any other width runs one pixel per lane.  The row gradient g_disp_layered [B,N,H] is reduced by the workgroup that
+// OWNS the row (tail_bwd_rows_kernel: one workgroup per (row, image), per-wave sums in LDS slots of their own, added in wave
+// order): no atomics, no workspace, the same bits on every run.
 #include "pd_tail_common.h"
 
 namespace pd {
@@ -25,16 +33,25 @@ struct TailArgs {
   const float* raw_logits;
   const float* raw_sigma;
   const float* mask;   // may be NULL (all ones)
-  const float* dl;     // [B,N] or [B,N,H,W]
+  const float* dl;     // [B,N] or [B,N,H,W]; [B,N,H] in the row form (so is `mask` then)
 };
 
-template <class ST, bool MIX, bool HASMASK, int PX>
+constexpr int kRowDisp = 1, kRowMask = 2;   // RF bits: disp_layered / padding_mask are [B,N,H]
+// the row-form operand of plane n for a lane whose PX pixels lie in row y; `rows` = the image's [N,H] block
+template <int PX>
+__device__ __forceinline__ Px<PX> ld_row(const float* __restrict__ rows, int n, int H, int y) {
+  return splat<PX>(rows[(long)n * H + y]);
+}
+
+template <class ST, bool MIX, bool HASMASK, int PX, int RF>
 __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __restrict__ logits, float* __restrict__ sigma,
                                                           float* __restrict__ disp, float* __restrict__ depth,
                                                           float* __restrict__ stash) {
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
   if (pix >= a.HW) return;
   const long base = (long)b * a.N * a.HW + pix;
+  const int H = RF ? a.HW / a.W : 0, y = RF ? pix / a.W : 0;   // row form: the lane's row (W % PX == 0 there)
+  const long rbase = (long)b * a.N * H;
   float m[PX], Z[PX], Sw[PX], Sd[PX];  // running reference, sum e^(l-m), sum of weights, sum w*d
 #pragma unroll
   for (int j = 0; j < PX; ++j) { m[j] = -INFINITY; Z[j] = Sw[j] = Sd[j] = 0.0f; }
@@ -44,10 +61,11 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __r
 #pragma unroll kUnroll
   for (int n = 0; n < a.N; ++n) {
     const long i = base + (long)n * a.HW;
-    const Px<PX> mk = HASMASK ? ldv<PX>(a.mask + i) : splat<PX>(1.0f);
+    const Px<PX> mk = !HASMASK ? splat<PX>(1.0f) : (RF & kRowMask) ? ld_row<PX>(a.mask + rbase, n, H, y) : ldv<PX>(a.mask + i);
     const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
     const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
-    const Px<PX> dv = a.dense ? ldv<PX>(a.dl + i) : splat<PX>(a.dl[b * a.N + n]);
+    const Px<PX> dv = (RF & kRowDisp) ? ld_row<PX>(a.dl + rbase, n, H, y)
+                                      : a.dense ? ldv<PX>(a.dl + i) : splat<PX>(a.dl[b * a.N + n]);
     Px<PX> lo, so;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
@@ -89,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __r
 }
 
 // pi and probability (depth_decoder.py:275, 281-285) for callers that want the tensors.
-template <class ST, bool MIX, bool HASMASK, int PX>
+template <class ST, bool MIX, bool HASMASK, int PX, int RF>
 __global__ __launch_bounds__(kBlock) void tail_layers_kernel(TailArgs a, const float* __restrict__ stash,
                                                              float* __restrict__ pi, float* __restrict__ prob) {
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
@@ -97,10 +115,12 @@ __global__ __launch_bounds__(kBlock) void tail_layers_kernel(TailArgs a, const f
   const long base = (long)b * a.N * a.HW + pix;
   const Px<PX> lse = ldv<PX>(stash + ((long)b * 2 + 0) * a.HW + pix);
   const Px<PX> sn = ldv<PX>(stash + ((long)b * 2 + 1) * a.HW + pix);
+  const int H = RF ? a.HW / a.W : 0, y = RF ? pix / a.W : 0;
+  const long rbase = (long)b * a.N * H;
 #pragma unroll 2
   for (int n = 0; n < a.N; ++n) {
     const long i = base + (long)n * a.HW;
-    const Px<PX> mk = HASMASK ? ldv<PX>(a.mask + i) : splat<PX>(1.0f);
+    const Px<PX> mk = !HASMASK ? splat<PX>(1.0f) : (RF & kRowMask) ? ld_row<PX>(a.mask + rbase, n, H, y) : ldv<PX>(a.mask + i);
     const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
     const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
     Px<PX> op, oq;
@@ -119,7 +139,26 @@ __global__ __launch_bounds__(kBlock) void tail_layers_kernel(TailArgs a, const f
 // (+ the depth term): d disp / d w_n = (d_n - disp) / S, and since sum_k pi_k (d loss / d pi_k) = gD/S * sum_k w_k
 // (d_k - disp) = 0 exactly, the softmax backward needs no second reduction:
 //   g_logits_n += gD (d_n - disp) P_n;   g_sigma_n -= gD (d_n - disp) P_n / sigma_n;   g_d_n = gD P_n.
-template <class ST, bool MIX, bool HASMASK, int PX>
+// One pixel of one plane (shared by the pixel-linear and the row-owned kernel: the same expressions in the same order).
+template <bool MIX>
+__device__ __forceinline__ void tail_bwd_px(float rl, float rs, float mk, float dv, float gl, float gs, float lse, float sn,
+                                            float dsp, float gD, float& o_l, float& o_s, float& o_d) {
+  const float p = __expf(rl * mk - lse);
+  float sgu = 1.0f, sg = 1.0f, P = p;
+  if (MIX) {
+    sgu = sigmoid_f(rs);
+    sg = clamp_sigma(sgu);
+    P = p * mk / sg / sn;
+  }
+  const float t = gD * (dv - dsp) * P;
+  o_l = (gl + t) * mk;
+  const float gsig = gs - t / sg;
+  o_s = (sgu == sg) ? gsig * sgu * (1.0f - sgu) : 0.0f;   // clamp gate (inclusive bounds), sigmoid'
+  o_d = gD * P;
+}
+
+// Pixel-linear form: per-plane or dense disparities (RF: 0, or kRowMask for a [B,N,H] mask).
+template <class ST, bool MIX, bool HASMASK, int PX, int RF>
 __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const float* __restrict__ stash,
                                                           const float* __restrict__ disp,
                                                           const float* __restrict__ g_logits,
@@ -138,6 +177,8 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const floa
   }
   const bool active = pix < a.HW;
   const long base = (long)b * a.N * a.HW + (active ? pix : 0);
+  const int H = RF ? a.HW / a.W : 0, y = RF ? (active ? pix : 0) / a.W : 0;
+  const long rbase = (long)b * a.N * H;
   Px<PX> lse = splat<PX>(0.0f), sn = splat<PX>(1.0f), dsp = splat<PX>(1.0f), gD = splat<PX>(0.0f);
   if (active) {
     lse = ldv<PX>(stash + ((long)b * 2 + 0) * a.HW + pix);
@@ -155,7 +196,7 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const floa
     const long i = base + (long)n * a.HW;
     float gd = 0.0f;
     if (active) {
-      const Px<PX> mk = HASMASK ? ldv<PX>(a.mask + i) : splat<PX>(1.0f);
+      const Px<PX> mk = !HASMASK ? splat<PX>(1.0f) : (RF & kRowMask) ? ld_row<PX>(a.mask + rbase, n, H, y) : ldv<PX>(a.mask + i);
       const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
       const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
       const Px<PX> dv = a.dense ? ldv<PX>(a.dl + i) : splat<PX>(a.dl[b * a.N + n]);
@@ -164,18 +205,8 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const floa
       Px<PX> o_l, o_s, o_d;
 #pragma unroll
       for (int j = 0; j < PX; ++j) {
-        const float p = __expf(rl.v[j] * mk.v[j] - lse.v[j]);
-        float sgu = 1.0f, sg = 1.0f, P = p;
-        if (MIX) {
-          sgu = sigmoid_f(rs.v[j]);
-          sg = clamp_sigma(sgu);
-          P = p * mk.v[j] / sg / sn.v[j];
-        }
-        const float t = gD.v[j] * (dv.v[j] - dsp.v[j]) * P;
-        o_l.v[j] = (gl.v[j] + t) * mk.v[j];
-        const float gsig = gs.v[j] - t / sg;
-        o_s.v[j] = (sgu == sg) ? gsig * sgu * (1.0f - sgu) : 0.0f;   // clamp gate (inclusive bounds), sigmoid'
-        o_d.v[j] = gD.v[j] * P;
+        tail_bwd_px<MIX>(rl.v[j], rs.v[j], mk.v[j], dv.v[j], gl.v[j], gs.v[j], lse.v[j], sn.v[j], dsp.v[j], gD.v[j], o_l.v[j],
+                         o_s.v[j], o_d.v[j]);
         gd += o_d.v[j];
       }
       if (g_raw_logits) stv<PX>(elems<ST>(g_raw_logits) + i, o_l);
@@ -194,12 +225,93 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const floa
   }
 }
 
+// Row-owned form (PD_TAIL_DISP_ROWS; RF holds kRowDisp): workgroup (y, b) walks row y of image b in steps of blockDim.x * PX
+// pixels, so every contribution to g_disp_layered[b,n,y] is its own.  Each wave keeps its sums in LDS slots of its own
+// (red[wave][n]: plain read-add-write by one lane, no atomics), and plane n's thread adds the waves' in wave order.
+template <class ST, bool MIX, bool HASMASK, int PX, int RF>
+__global__ __launch_bounds__(kBlock) void tail_bwd_rows_kernel(TailArgs a, const float* __restrict__ stash,
+                                                               const float* __restrict__ disp,
+                                                               const float* __restrict__ g_logits,
+                                                               const float* __restrict__ g_sigma,
+                                                               const float* __restrict__ g_disp,
+                                                               const float* __restrict__ g_depth,
+                                                               float* __restrict__ g_raw_logits,
+                                                               float* __restrict__ g_raw_sigma, float* __restrict__ g_dl) {
+  extern __shared__ float red[];  // [waves][N]
+  const int y = blockIdx.x, b = blockIdx.y, H = gridDim.x;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nwaves = blockDim.x / kWave;
+  const long rbase = (long)b * a.N * H;
+  if (g_dl) {
+    for (int i = threadIdx.x; i < nwaves * a.N; i += blockDim.x) red[i] = 0.0f;
+    __syncthreads();
+  }
+  for (int x0 = 0; x0 < a.W; x0 += blockDim.x * PX) {   // (workgroup-uniform trip count: the wave sums below see every lane)
+    const int x = x0 + threadIdx.x * PX;
+    const bool active = x < a.W;
+    const int pix = y * a.W + (active ? x : 0);
+    const long base = (long)b * a.N * a.HW + pix;
+    Px<PX> lse = splat<PX>(0.0f), sn = splat<PX>(1.0f), dsp = splat<PX>(1.0f), gD = splat<PX>(0.0f);
+    if (active) {
+      lse = ldv<PX>(stash + ((long)b * 2 + 0) * a.HW + pix);
+      sn = ldv<PX>(stash + ((long)b * 2 + 1) * a.HW + pix);
+      dsp = ldv<PX>(disp + (long)b * a.HW + pix);
+      if (g_disp) gD = ldv<PX>(g_disp + (long)b * a.HW + pix);
+      if (g_depth) {
+        const Px<PX> gz = ldv<PX>(g_depth + (long)b * a.HW + pix);
+#pragma unroll
+        for (int j = 0; j < PX; ++j) gD.v[j] -= gz.v[j] * (0.1f * 0.58f * (float)a.W) / (dsp.v[j] * dsp.v[j]);
+      }
+    }
+    for (int n = 0; n < a.N; ++n) {
+      const long i = base + (long)n * a.HW;
+      float gd = 0.0f;
+      if (active) {
+        const Px<PX> mk = !HASMASK ? splat<PX>(1.0f) : (RF & kRowMask) ? ld_row<PX>(a.mask + rbase, n, H, y) : ldv<PX>(a.mask + i);
+        const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
+        const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
+        const Px<PX> dv = ld_row<PX>(a.dl + rbase, n, H, y);
+        const Px<PX> gl = g_logits ? ldv<PX>(elems<ST>(g_logits) + i) : splat<PX>(0.0f);
+        const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(elems<ST>(g_sigma) + i) : splat<PX>(0.0f);
+        Px<PX> o_l, o_s, o_d;
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+          tail_bwd_px<MIX>(rl.v[j], rs.v[j], mk.v[j], dv.v[j], gl.v[j], gs.v[j], lse.v[j], sn.v[j], dsp.v[j], gD.v[j], o_l.v[j],
+                           o_s.v[j], o_d.v[j]);
+          gd += o_d.v[j];
+        }
+        if (g_raw_logits) stv<PX>(elems<ST>(g_raw_logits) + i, o_l);
+        if (MIX && g_raw_sigma) stv<PX>(elems<ST>(g_raw_sigma) + i, o_s);
+      }
+      if (g_dl) {
+        const float v = wave_sum_hi(gd);
+        if (lane == kWave - 1) red[wave * a.N + n] += v;
+      }
+    }
+  }
+  if (g_dl) {
+    __syncthreads();
+    for (int n = threadIdx.x; n < a.N; n += blockDim.x) {
+      float s = red[n];
+      for (int w = 1; w < nwaves; ++w) s += red[w * a.N + n];
+      g_dl[rbase + (long)n * H + y] = s;
+    }
+  }
+}
+
 static int tail_validate(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
-                         const float* dl) {
+                         const float* mask, const float* dl) {
   PD_REQUIRE(B > 0 && B <= 65535 && N > 0 && H > 0 && W > 0, "bad shape");
   PD_REQUIRE((long)H * W < (1L << 31), "image too large");
-  PD_REQUIRE((flags & ~(PD_TAIL_MIXTURE | PD_TAIL_DISP_DENSE | PD_TAIL_BF16)) == 0, "unknown flags");
+  PD_REQUIRE((flags & ~(PD_TAIL_MIXTURE | PD_TAIL_DISP_DENSE | PD_TAIL_BF16 | PD_TAIL_DISP_ROWS | PD_TAIL_MASK_ROWS)) == 0,
+             "unknown flags");
+  PD_REQUIRE(!((flags & PD_TAIL_DISP_ROWS) && (flags & PD_TAIL_DISP_DENSE)),
+             "PD_TAIL_DISP_ROWS and PD_TAIL_DISP_DENSE exclude each other (disp_layered is [B,N,H] or [B,N,H,W])");
+  // (a row form's refusal names its flag and the layout that flag announces: a caller that set bit 8 or 16 by accident — they
+  // were unknown flags before the row forms existed — learns from the text what the bit made of its tensors)
+  PD_REQUIRE(!(flags & PD_TAIL_DISP_ROWS) || (raw_logits && dl),
+             "NULL pointer (PD_TAIL_DISP_ROWS in flags: disp_layered is read as [B,N,H])");
   PD_REQUIRE(raw_logits && dl, "NULL pointer");
+  PD_REQUIRE(!(flags & PD_TAIL_MASK_ROWS) || mask, "NULL pointer (PD_TAIL_MASK_ROWS in flags: padding_mask is read as [B,N,H])");
   PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || raw_sigma, "mixture needs raw_sigma");
   return 0;
 }
@@ -214,25 +326,33 @@ static TailArgs tail_args(int N, int H, int W, int flags, const float* raw_logit
   return a;
 }
 
-#define PD_TAIL_DISPATCH_PX(KERNEL, T, PX, mix, hasmask, grid, shmem, stream, ...)                          \
+// RF of a call: which of disp_layered / padding_mask are [B,N,H]
+static inline int tail_rf(int flags, const float* mask) {
+  return ((flags & PD_TAIL_DISP_ROWS) ? kRowDisp : 0) | ((mask && (flags & PD_TAIL_MASK_ROWS)) ? kRowMask : 0);
+}
+// A row form takes 4 pixels per lane only when a group of 4 cannot straddle two rows
+static inline int tail_px_rows(int px, int rf, int W) { return (rf && W % 4 != 0) ? 1 : px; }
+
+#define PD_TAIL_DISPATCH_PX(KERNEL, T, PX, RF, mix, hasmask, grid, block, shmem, stream, ...)                \
   do {                                                                                                       \
     if (mix) {                                                                                               \
-      if (hasmask) KERNEL<T, true, true, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                  \
-      else         KERNEL<T, true, false, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                 \
+      if (hasmask) KERNEL<T, true, true, PX, RF><<<grid, block, shmem, stream>>>(__VA_ARGS__);               \
+      else         KERNEL<T, true, false, PX, (RF) & ~kRowMask><<<grid, block, shmem, stream>>>(__VA_ARGS__); \
     } else {                                                                                                 \
-      if (hasmask) KERNEL<T, false, true, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                 \
-      else         KERNEL<T, false, false, PX><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);                \
+      if (hasmask) KERNEL<T, false, true, PX, RF><<<grid, block, shmem, stream>>>(__VA_ARGS__);              \
+      else         KERNEL<T, false, false, PX, (RF) & ~kRowMask><<<grid, block, shmem, stream>>>(__VA_ARGS__); \
     }                                                                                                        \
   } while (0)
-#define PD_TAIL_DISPATCH_T(KERNEL, T, px, mix, hasmask, grid, shmem, stream, ...)                            \
+#define PD_TAIL_DISPATCH_T(KERNEL, T, RF, px, mix, hasmask, grid, block, shmem, stream, ...)                 \
   do {                                                                                                       \
-    if ((px) == 4) PD_TAIL_DISPATCH_PX(KERNEL, T, 4, mix, hasmask, grid, shmem, stream, __VA_ARGS__);        \
-    else           PD_TAIL_DISPATCH_PX(KERNEL, T, 1, mix, hasmask, grid, shmem, stream, __VA_ARGS__);        \
+    if ((px) == 4) PD_TAIL_DISPATCH_PX(KERNEL, T, 4, RF, mix, hasmask, grid, block, shmem, stream, __VA_ARGS__); \
+    else           PD_TAIL_DISPATCH_PX(KERNEL, T, 1, RF, mix, hasmask, grid, block, shmem, stream, __VA_ARGS__); \
   } while (0)
-#define PD_TAIL_DISPATCH(KERNEL, bf16, px, mix, hasmask, grid, shmem, stream, ...)                           \
+// RF is a constant here: the callers branch on tail_rf() and name the forms their kernel has
+#define PD_TAIL_DISPATCH(KERNEL, RF, bf16, px, mix, hasmask, grid, block, shmem, stream, ...)                \
   do {                                                                                                       \
-    if (bf16) PD_TAIL_DISPATCH_T(KERNEL, Bf16, px, mix, hasmask, grid, shmem, stream, __VA_ARGS__);          \
-    else      PD_TAIL_DISPATCH_T(KERNEL, float, px, mix, hasmask, grid, shmem, stream, __VA_ARGS__);         \
+    if (bf16) PD_TAIL_DISPATCH_T(KERNEL, Bf16, RF, px, mix, hasmask, grid, block, shmem, stream, __VA_ARGS__); \
+    else      PD_TAIL_DISPATCH_T(KERNEL, float, RF, px, mix, hasmask, grid, block, shmem, stream, __VA_ARGS__); \
   } while (0)
 
 }  // namespace pd
@@ -240,38 +360,53 @@ static TailArgs tail_args(int N, int H, int W, int flags, const float* raw_logit
 using namespace pd;
 
 extern "C" size_t pd_decoder_tail_bwd_workspace_floats(int B, int N, int H, int W) {
-  return (size_t)B * ceil_div(H * W, kBlock) * N;
+  return (size_t)B * ceil_div(H * W, kBlock) * N;   // the per-plane form's partial sums; the dense and the row forms need none
 }
 
 extern "C" int pd_decoder_tail_fwd(int B, int N, int H, int W, int flags, const float* raw_logits,
                                    const float* raw_sigma, const float* padding_mask, const float* disp_layered,
                                    float* logits, float* sigma, float* disp, float* depth, float* stash,
                                    pd_stream_t stream) {
-  if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, disp_layered)) return rc;
+  if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, padding_mask, disp_layered)) return rc;
   PD_REQUIRE(disp && depth && stash, "NULL output");
   PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || sigma, "mixture needs the sigma output");
   PD_REQUIRE(!padding_mask || logits, "a padding mask needs the logits output");
   const TailArgs a = tail_args(N, H, W, flags, raw_logits, raw_sigma, padding_mask, disp_layered);
   const bool bf16 = (flags & PD_TAIL_BF16) != 0;
-  const int px = tail_px(H, W, {padding_mask, a.dense ? disp_layered : nullptr, disp, depth, stash},
-                         {raw_logits, raw_sigma, logits, sigma}, bf16);
+  const int rf = tail_rf(flags, padding_mask);
+  const int px = tail_px_rows(tail_px(H, W, {(rf & kRowMask) ? nullptr : padding_mask, a.dense ? disp_layered : nullptr, disp,
+                                             depth, stash},
+                                      {raw_logits, raw_sigma, logits, sigma}, bf16), rf, W);
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  PD_TAIL_DISPATCH(tail_fwd_kernel, bf16, px, a.mix, padding_mask != nullptr, grid, 0, (hipStream_t)stream, a, logits, sigma,
-                   disp, depth, stash);
+  const bool hasmask = padding_mask != nullptr;
+#define PD_TAIL_FWD(RF) \
+  PD_TAIL_DISPATCH(tail_fwd_kernel, RF, bf16, px, a.mix, hasmask, grid, kBlock, 0, (hipStream_t)stream, a, logits, sigma, disp, depth, stash)
+  switch (rf) {
+    case 0: PD_TAIL_FWD(0); break;
+    case kRowDisp: PD_TAIL_FWD(kRowDisp); break;
+    case kRowMask: PD_TAIL_FWD(kRowMask); break;
+    default: PD_TAIL_FWD(kRowDisp | kRowMask); break;
+  }
+#undef PD_TAIL_FWD
   return check_launch("tail_fwd_kernel");
 }
 
 extern "C" int pd_decoder_tail_layers(int B, int N, int H, int W, int flags, const float* raw_logits,
                                       const float* raw_sigma, const float* padding_mask, const float* stash, float* pi,
                                       float* probability, pd_stream_t stream) {
-  if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, raw_logits)) return rc;
+  if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, padding_mask, raw_logits)) return rc;
   PD_REQUIRE(stash && (pi || probability), "NULL pointer");
   const TailArgs a = tail_args(N, H, W, flags, raw_logits, raw_sigma, padding_mask, nullptr);
   const bool bf16 = (flags & PD_TAIL_BF16) != 0;
-  const int px = tail_px(H, W, {padding_mask, stash, pi, probability}, {raw_logits, raw_sigma}, bf16);
+  const int rf = tail_rf(flags, padding_mask) & kRowMask;   // (disp_layered is not read here)
+  const int px = tail_px_rows(tail_px(H, W, {rf ? nullptr : padding_mask, stash, pi, probability}, {raw_logits, raw_sigma}, bf16),
+                              rf, W);
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  PD_TAIL_DISPATCH(tail_layers_kernel, bf16, px, a.mix, padding_mask != nullptr, grid, 0, (hipStream_t)stream, a, stash, pi,
-                   probability);
+  const bool hasmask = padding_mask != nullptr;
+  if (rf) PD_TAIL_DISPATCH(tail_layers_kernel, kRowMask, bf16, px, a.mix, hasmask, grid, kBlock, 0, (hipStream_t)stream, a, stash,
+                           pi, probability);
+  else    PD_TAIL_DISPATCH(tail_layers_kernel, 0, bf16, px, a.mix, hasmask, grid, kBlock, 0, (hipStream_t)stream, a, stash, pi,
+                           probability);
   return check_launch("tail_layers_kernel");
 }
 
@@ -280,21 +415,40 @@ extern "C" int pd_decoder_tail_bwd(int B, int N, int H, int W, int flags, const 
                                    const float* stash, const float* disp, const float* g_logits, const float* g_sigma,
                                    const float* g_disp, const float* g_depth, float* g_raw_logits, float* g_raw_sigma,
                                    float* g_disp_layered, float* workspace, pd_stream_t stream) {
-  if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, disp_layered)) return rc;
+  if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, padding_mask, disp_layered)) return rc;
   PD_REQUIRE(stash && disp, "NULL pointer");
   PD_REQUIRE(g_raw_logits || g_raw_sigma || g_disp_layered, "no gradient requested");
   const TailArgs a = tail_args(N, H, W, flags, raw_logits, raw_sigma, padding_mask, disp_layered);
-  const bool reduce = g_disp_layered && !a.dense;
+  const int rf = tail_rf(flags, padding_mask);
+  const bool reduce = g_disp_layered && !a.dense && !(rf & kRowDisp);
   PD_REQUIRE(!reduce || workspace, "per-plane disparity gradient needs the workspace");
-  PD_REQUIRE((size_t)N * sizeof(float) <= 64 * 1024, "too many planes");
+  PD_REQUIRE((size_t)N * sizeof(float) <= 64 * 1024 / ((rf & kRowDisp) ? kBlock / kWave : 1), "too many planes");
   const bool bf16 = (flags & PD_TAIL_BF16) != 0;
-  const int px = tail_px(H, W, {padding_mask, a.dense ? disp_layered : nullptr, stash, disp, g_disp, g_depth,
-                                a.dense ? g_disp_layered : nullptr},
-                         {raw_logits, raw_sigma, g_logits, g_sigma, g_raw_logits, g_raw_sigma}, bf16);
+  const bool hasmask = padding_mask != nullptr;
+  const int px = tail_px_rows(tail_px(H, W, {(rf & kRowMask) ? nullptr : padding_mask, a.dense ? disp_layered : nullptr, stash, disp,
+                                             g_disp, g_depth, a.dense ? g_disp_layered : nullptr},
+                                      {raw_logits, raw_sigma, g_logits, g_sigma, g_raw_logits, g_raw_sigma}, bf16), rf, W);
+  if (rf & kRowDisp) {   // row-owned: workgroup (y, b), as many waves as the row has work for
+    const int waves = ceil_div(ceil_div(W, px), kWave);
+    const int threads = kWave * (waves < kBlock / kWave ? waves : kBlock / kWave);
+    dim3 grid(H, B);
+    const size_t shmem = g_disp_layered ? (size_t)(threads / kWave) * N * sizeof(float) : 0;
+    if (rf & kRowMask)
+      PD_TAIL_DISPATCH(tail_bwd_rows_kernel, kRowDisp | kRowMask, bf16, px, a.mix, hasmask, grid, threads, shmem, (hipStream_t)stream,
+                       a, stash, disp, g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered);
+    else
+      PD_TAIL_DISPATCH(tail_bwd_rows_kernel, kRowDisp, bf16, px, a.mix, hasmask, grid, threads, shmem, (hipStream_t)stream, a, stash,
+                       disp, g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered);
+    return check_launch("tail_bwd_rows_kernel");
+  }
   dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
   const size_t shmem = reduce ? (size_t)N * sizeof(float) : 0;
-  PD_TAIL_DISPATCH(tail_bwd_kernel, bf16, px, a.mix, padding_mask != nullptr, grid, shmem, (hipStream_t)stream, a, stash, disp,
-                   g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
+  if (rf & kRowMask)
+    PD_TAIL_DISPATCH(tail_bwd_kernel, kRowMask, bf16, px, a.mix, hasmask, grid, kBlock, shmem, (hipStream_t)stream, a, stash, disp,
+                     g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
+  else
+    PD_TAIL_DISPATCH(tail_bwd_kernel, 0, bf16, px, a.mix, hasmask, grid, kBlock, shmem, (hipStream_t)stream, a, stash, disp,
+                     g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
   if (int rc = check_launch("tail_bwd_kernel")) return rc;
   if (reduce) {
     return reduce_partials(workspace, g_disp_layered, (int)grid.x, N, B, (hipStream_t)stream);

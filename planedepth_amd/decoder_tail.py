@@ -23,6 +23,19 @@ padding mask has N channels, ``dispconv`` N-1).  The live producer of ``outputs[
     fused_plade_tail(self.outputs, self.conv0(dlog), self.conv_sigma(features) if self.use_mixture_loss else None,
                      use_mixture_loss=self.use_mixture_loss)
 
+Geometry head.  With xy + xz planes (``--xz_levels 14``, the reference's default plane set) the lines in front of the tail,
+depth_decoder.py:148-257, build dense [B,N,H,W] maps for information that is [B,N,H]-sized.  ``fused_plane_geometry`` replaces
+them with one kernel each way and hands ``outputs["disp_layered"]`` / ``["padding_mask"]`` over as row views (reference shape,
+``stride(3) == 0``); the tail, the sweep and the post-process recognise the strides and take their row forms::
+
+    from planedepth_amd.decoder_tail import fused_plane_geometry, fused_decoder_tail
+    residual = self.sigmoid(self.convs["residualconv"](x)) - 0.5 if self.plane_residual else None
+    fused_plane_geometry(self.outputs, input_grids, residual, no_levels=self.no_levels, xz_levels=self.xz_levels,
+                         disp_min=self.disp_min, disp_max=self.disp_max, xz_min=self.xz_min, xz_max=self.xz_max)
+    fused_decoder_tail(self.outputs, self.convs["dispconv"](x), ...)
+
+With ``yz_levels > 0`` (disparities that vary along x) the reference's lines stay.
+
 Mixed precision.  Under ``torch.autocast("cuda", dtype=torch.bfloat16)`` the convolutions emit bf16, and both tails take it as
 it is (``PD_TAIL_BF16``; no ``.float()`` on the conv outputs, which would bring the [B,N,H,W] fp32 activations and gradients
 back).  ``outputs["logits"]`` / ``["sigma"]`` are then bf16 — what the plane sweep reads natively — and so
@@ -117,11 +130,35 @@ def fused_decoder_tail(outputs, dispconv_out, sigmaconv_out=None, *, use_mixture
     return outputs
 
 
+def fused_plane_geometry(outputs, input_grids, residual_levels, *, no_levels, xz_levels, disp_min, disp_max, xz_min, xz_max,
+                         check_contract=None):
+    """Opt-in drop-in for depth_decoder.py:148-257 with ``yz_levels == 0``: fills ``outputs["distance"]`` [B,N], ``["norm"]``
+    [B,N,3], ``["disp_layered"]`` and ``["padding_mask"]`` [B,N,H,W] from ``input_grids`` [B,2,H,W] and ``residual_levels``
+    (``sigmoid(residualconv(x)) - 0.5``, [B,N,1,1] or [B,N]; ``None`` without ``--plane_residual``) through
+    ``ops.plane_geometry`` — one HIP kernel each way.  The two maps are row views (``stride(3) == 0`` over [B,N,H] rows): nothing
+    [B,N,H,W]-sized is built, and ``fused_decoder_tail`` / the trainer path take their row forms on seeing the strides.
+
+    Opt-in because ``networks/*`` drop in unchanged.  With ``yz_levels > 0`` the maintainer keeps the reference's lines (yz
+    planes vary along x; they have no row form).  The operator assumes what every grid of datasets/pair_transforms.py gives: a
+    y channel that is constant along x, the x extent of a row at its first and last column.  ``check_contract=True``, or
+    ``PD_CHECK_CONTRACT=1`` in the environment (the trainer path's ``opt.pd_check_contract`` convention), checks the y channel on
+    the data and raises ``ValueError``; a sheared or rotated grid must keep the reference's lines as well."""
+    disp_layered, padding_mask, distance, norm = ops.plane_geometry(
+        input_grids, residual_levels, no_levels=no_levels, xz_levels=xz_levels, disp_min=disp_min, disp_max=disp_max,
+        xz_min=xz_min, xz_max=xz_max, check_contract=check_contract)
+    outputs["distance"] = distance
+    outputs["norm"] = norm
+    outputs["disp_layered"] = disp_layered
+    outputs["padding_mask"] = padding_mask
+    return outputs
+
+
 def fused_plade_tail(outputs, conv0_out, conv_sigma_out=None, *, use_mixture_loss=True, materialize_layers=False):
     """Fills ``outputs`` with "logits", "dists", "sigma", "pi", "probability", "disp", "depth" as plade_net.py:309-340 does
     with ``render_probability`` (alpha compositing of the N-1 logit channels of ``conv0`` against the distances between the
     depth layers).  Reads ``outputs["disp_layered"]`` (per-plane levels with the learnt residual, or the dense map with
-    ground planes)."""
+    ground planes).  A row view from ``fused_plane_geometry`` is accepted and materialised to the dense map (``_contig``): correct,
+    no faster — this tail has no row form."""
     B, Nm1, H, W = conv0_out.shape
     logits, dists, sigma, disp, depth, layers = ops.plade_tail(conv0_out, conv_sigma_out, outputs["disp_layered"],
                                                                 use_mixture_loss=use_mixture_loss)

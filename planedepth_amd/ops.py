@@ -19,10 +19,10 @@ from ._buffers import (  # noqa: F401
 from .sweep import (  # noqa: F401
     SweepCall, SweepSaved, _sweep_forward, _sweep_forward_pair, _sweep_backward_pair, _sweep_backward, _sweep_backward_tail,
     TailLink, _GradTap, tail_taps, _PlaneSweep, _SIDE_FIELDS, _PER_SIDE, _MultiPlaneSweep,
-    plane_sweep_multi, as_f32, _storage_route, _flags, _SIGN, _per_plane_view, _FirstColumn, plane_sweep_disp,
+    plane_sweep_multi, as_f32, _storage_route, _flags, _SIGN, _per_plane_view, _FirstColumn, _row_view, _rows_of, _RowView, row_view, plane_sweep_disp,
     homography_matrices, _HomographyMatrices, homography_matrices_fused, plane_sweep_homography, _stereo_rows_sweep, plane_sweep_layers)
 from .tails import (  # noqa: F401
-    _PlaneLevels, plane_disparities,
+    _PlaneLevels, plane_disparities, _PlaneGeometry, plane_geometry,
     _DecoderTail, decoder_tail, _PladeTail, _RAY_NORM, camera_ray_norm, _camera_ray_norm,
     plade_tail)
 from .losses import (  # noqa: F401

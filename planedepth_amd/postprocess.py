@@ -7,6 +7,7 @@ import os
 from . import _capi as C
 from . import _state as S
 from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, _plane_grad_buffer
+from .sweep import _row_view
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -15,8 +16,10 @@ from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, 
 def _pp_disp(disp_layered, B, N, H, W, row_uniform=False):
     """(tensor, flags): per-plane [B,N] when the map is an H/W-expanded view; [B,N,H] + PD_PP_DISP_ROWS when it is constant
     along x — an x-expanded view, or a dense map under the caller's ``row_uniform`` promise (xy and xz planes:
-    networks/depth_decoder.py:153-181; yz planes are not) —; else the dense [B,N,H,W] map."""
-    if tuple(disp_layered.shape) != (B, N, H, W):
+    networks/depth_decoder.py:153-181; yz planes are not) —; else the dense [B,N,H,W] map.  A row view (``stride(3) == 0``:
+    ``ops.plane_geometry``'s map, or a batch slice of it) is read as rows without the promise; one of another shape raises
+    ``ValueError`` (``_row_view``)."""
+    if not _row_view(disp_layered, B, N, H, W) and tuple(disp_layered.shape) != (B, N, H, W):
         disp_layered = disp_layered.expand(B, N, H, W)
     if disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0:
         return disp_layered[:, :, 0, 0].contiguous(), 0

@@ -545,6 +545,61 @@ class _FirstColumn(torch.autograd.Function):
         return (g * (1.0 / ctx.W)).unsqueeze(-1).expand(*g.shape, ctx.W)
 
 
+def _row_view(t, B, N, H, W, name="disp_layered"):
+    """Is ``t`` a ROW VIEW: a [B,N,H,W] tensor with ``stride(3) == 0`` (and W > 1) that is not an H/W-expanded view of per-plane
+    scalars — what ``ops.plane_geometry`` returns for ``disp_layered`` / ``padding_mask``, or any tensor with those strides (a
+    batch slice ``view[:B]`` included).  Such a tensor IS constant along x, by construction: the row kernels take it with no
+    ``row_uniform`` promise and no check of the data.  A stride-0 view of another shape raises ``ValueError``."""
+    if not torch.is_tensor(t) or t.dim() != 4 or t.shape[3] <= 1 or t.stride(3) != 0 or (t.stride(2) == 0 and t.shape[2] > 1):
+        return False
+    if tuple(t.shape) != (B, N, H, W):
+        raise ValueError("%s is a row view (stride(3) == 0) of shape %s, expected %s" % (name, tuple(t.shape), (B, N, H, W)))
+    return True
+
+
+def _rows_of(view):
+    """The [B,N,H] rows of a row view (``_row_view``).  A view made by ``ops.plane_geometry`` carries the rows tensor it was
+    expanded from (``_pd_rows``): the consumer then hangs on that tensor's autograd node directly, and its gradient arrives
+    [B,N,H]-sized — nothing is spread over W and summed again, and several consumers add up in [B,N,H].  Any other row view
+    goes through ``_FirstColumn``: the row total comes back as ``g / W`` on every column, a stride-0 gradient."""
+    rows = getattr(view, "_pd_rows", None)
+    if (rows is not None and rows.data_ptr() == view.data_ptr() and tuple(rows.shape) == tuple(view.shape[:3])
+            and rows.stride() == view.stride()[:3]):
+        return rows
+    if view.requires_grad and torch.is_grad_enabled():
+        return _FirstColumn.apply(view)
+    return view.detach()[..., 0]
+
+
+class _RowView(torch.autograd.Function):
+    """rows [B,N,H] -> the [B,N,H,W] view with ``stride(3) == 0`` (the reference's shape of ``outputs["disp_layered"]``, nothing
+    [B,N,H,W]-sized behind it).  Backward: a gradient that is itself constant along x (``stride(3) == 0``: ``_FirstColumn``'s
+    ``g / W`` on every column) gives ``W * g[..., 0]`` without touching W times as many elements; any other gradient — a foreign
+    torch consumer of the view — is summed over x.  The package's own row consumers do not come through here at all
+    (``_rows_of``)."""
+
+    @staticmethod
+    def forward(ctx, rows, W):
+        ctx.W = int(W)
+        ctx.set_materialize_grads(False)
+        return rows.unsqueeze(-1).expand(*rows.shape, int(W))
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        if ctx.W > 1 and g.stride(-1) == 0:
+            return g[..., 0] * float(ctx.W), None
+        return g.sum(-1), None
+
+
+def row_view(rows, W):
+    """``_RowView`` + the ``_pd_rows`` tag ``_rows_of`` reads."""
+    view = _RowView.apply(rows, W) if rows.requires_grad else rows.unsqueeze(-1).expand(*rows.shape, int(W))
+    view._pd_rows = rows
+    return view
+
+
 @functools.lru_cache(maxsize=None)
 def _row_kernels(B, N, H, W, impl):
     """Do the row kernels serve disp mode at this shape under ``impl``?  pd_sweep_uses_rowshift (the per-row flags do not
@@ -571,7 +626,8 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
     being materialised) or a dense ``[B,N,H,W]`` map (xz / yz planes present).  ``row_uniform=True`` promises that a
     dense map is constant along x (true for xy and xz planes: networks/depth_decoder.py:153-181 build them from the
     y-grid only; false once yz planes exist): its first column is then used as ``[B,N,H]`` per-row disparities, which
-    keeps the row-shift kernels applicable.
+    keeps the row-shift kernels applicable.  A ROW VIEW — ``stride(3) == 0``, as ``ops.plane_geometry`` returns it, for the map
+    and / or the mask — says the same through its strides: it takes the row route without the promise (``_row_view``).
 
     Gradient of a dense ``row_uniform`` map.  The reference's autograd hands ``disp_layered`` a dense [B,N,H,W] gradient
     (every column its own share).  Here the row's total ``g[b,n,y]`` comes back SPREAD EVENLY, ``g / W`` on every column, as
@@ -595,30 +651,36 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
             return _finish(SweepCall(src, tgt, logits, sigma if use_mixture_loss else None, shift, None, None, mask,
                                      dists if render_probability else None, C.PD_WARP_DISP, flags | bf, sign), defer, return_mean)
         disp_layered, padding_mask = (t[..., None].expand(B, N, H, W) for t in _rows)   # PD_IMPL_GENERAL & co.
-    if tuple(disp_layered.shape) != (B, N, H, W):
+    view = _row_view(disp_layered, B, N, H, W)   # constant along x by its strides: no promise needed, no data check
+    if not view and tuple(disp_layered.shape) != (B, N, H, W):
         disp_layered = disp_layered.expand(B, N, H, W)
-    per_plane = disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
+    per_plane = not view and disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
     rows = False
     if per_plane:
         plane = _per_plane_view(disp_layered)
-    elif row_uniform:
+    elif view or row_uniform:
         rows = _row_kernels(B, N, H, W, S.SWEEP_IMPL)
-        if rows:   # a LEAF map keeps the exact select gradient (g on column 0, zeros elsewhere); see the docstring
+        if rows and view:
+            plane = _rows_of(disp_layered)
+        elif rows:   # a LEAF map keeps the exact select gradient (g on column 0, zeros elsewhere); see the docstring
             plane = disp_layered[..., 0].contiguous() if disp_layered.is_leaf else _FirstColumn.apply(disp_layered)
         else:
             plane = disp_layered
     else:
         plane = disp_layered
+    mask_view = padding_mask is not None and _row_view(padding_mask, B, N, H, W, "padding_mask")
+    if padding_mask is not None and not mask_view:
+        if padding_mask.dtype != torch.float32:
+            padding_mask = padding_mask.float()
+        if tuple(padding_mask.shape) != (B, N, H, W):
+            padding_mask = padding_mask.expand(B, N, H, W)
+    flags = _flags(use_mixture_loss, automask, dense=not (per_plane or rows), render=render_probability, rows=rows)
+    if padding_mask is not None and (row_uniform or mask_view) and (per_plane or rows) and _row_kernels(B, N, H, W, S.SWEEP_IMPL):
+        # the mask of xy / xz planes is constant along x as well (depth_decoder.py:157, 166): hand over its first column
+        padding_mask = padding_mask.detach()[..., 0] if mask_view else padding_mask[..., 0]
+        flags |= C.PD_MASK_ROWS
     if padding_mask is not None and padding_mask.dtype != torch.float32:
         padding_mask = padding_mask.float()
-    if padding_mask is not None and tuple(padding_mask.shape) != (B, N, H, W):
-        padding_mask = padding_mask.expand(B, N, H, W)
-    flags = _flags(use_mixture_loss, automask, dense=not (per_plane or rows), render=render_probability, rows=rows)
-    if padding_mask is not None and row_uniform and (per_plane or rows):
-        # the mask of xy / xz planes is constant along x as well (depth_decoder.py:157, 166): hand over its first column
-        if _row_kernels(B, N, H, W, S.SWEEP_IMPL):
-            padding_mask = padding_mask[..., 0]
-            flags |= C.PD_MASK_ROWS
     # bf16 logits / sigma: native where the library serves the descriptor; a per-pixel mask is a fact of the call that no
     # descriptor shows, and PD_LOGITS_BF16 is refused with one — fp32 copies there and everywhere else
     per_pixel_mask = padding_mask is not None and not flags & C.PD_MASK_ROWS

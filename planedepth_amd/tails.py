@@ -7,7 +7,7 @@ import os
 from . import _capi as C
 from . import _state as S
 from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, _plane_grad_buffer
-from .sweep import TailLink, _per_plane_view
+from .sweep import TailLink, _per_plane_view, _row_view, _rows_of, row_view
 
 
 def _storage_flag(raw_logits, raw_sigma, mix):
@@ -46,9 +46,10 @@ class _DecoderTail(torch.autograd.Function):
         C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
         if mix:
             C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
-        C.require_gpu_tensor("disp_layered", disp_layered, (B, N, H, W) if flags & C.PD_TAIL_DISP_DENSE else (B, N))
+        C.require_gpu_tensor("disp_layered", disp_layered, (B, N, H, W) if flags & C.PD_TAIL_DISP_DENSE else
+                             (B, N, H) if flags & C.PD_TAIL_DISP_ROWS else (B, N))
         if padding_mask is not None:
-            C.require_gpu_tensor("padding_mask", padding_mask, (B, N, H, W))
+            C.require_gpu_tensor("padding_mask", padding_mask, (B, N, H) if flags & C.PD_TAIL_MASK_ROWS else (B, N, H, W))
         raw_logits, raw_sigma, disp_layered, padding_mask = map(_contig, (raw_logits, raw_sigma, disp_layered, padding_mask))
         dev = raw_logits.device
         new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)  # noqa: E731
@@ -109,7 +110,7 @@ class _DecoderTail(torch.autograd.Function):
         g_raw_sigma = torch.empty_like(raw_sigma) if need_s else None
         g_dl = torch.empty_like(disp_layered) if need_d else None
         ws = None
-        if need_d and not (flags & C.PD_TAIL_DISP_DENSE):
+        if need_d and not (flags & (C.PD_TAIL_DISP_DENSE | C.PD_TAIL_DISP_ROWS)):   # (the row form reduces inside its kernel)
             ws = torch.empty(lib.pd_decoder_tail_bwd_workspace_floats(B, N, H, W), device=raw_logits.device,
                              dtype=torch.float32)
         g_logits, g_sigma, g_disp, g_depth = map(_contig, (g_logits, g_sigma if mix else None, g_disp, g_depth))
@@ -136,6 +137,12 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     (no gradient: nothing in the reference's losses reads them).  ``disp_layered`` may be the decoder's expanded view of
     per-plane scalars or a dense map; ``padding_mask=None`` means all ones (xy planes only).
 
+    Row form.  A map and / or a mask that is a row view — [B,N,H,W] with ``stride(3) == 0``, what ``plane_geometry`` returns
+    (xy + xz planes) — goes in as its [B,N,H] rows (``PD_TAIL_DISP_ROWS`` / ``PD_TAIL_MASK_ROWS``), each tensor in its own form: a
+    dense one next to a row view is legal.  The outputs and the conv outputs' gradients have the dense route's bits; the map's
+    gradient is [B,N,H], summed over x on the device by the workgroup that owns the row (deterministic).  Nothing
+    [B,N,H,W]-sized is read or written for the map and the mask.
+
     ``raw_logits`` / ``raw_sigma`` are fp32, or both bf16 (``torch.autocast``: PD_TAIL_BF16).  ``logits`` / ``sigma`` and the
     conv outputs' gradients then are bf16 too, each element rounded once from the fp32 value; ``disp``, ``depth``, ``pi`` and
     ``probability`` stay fp32 and come from the unrounded fp32 sigma (the fp32 route on the widened inputs).  With bf16,
@@ -144,15 +151,20 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     """
     B, N, H, W = raw_logits.shape
     bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
-    if tuple(disp_layered.shape) != (B, N, H, W):
+    rows = _row_view(disp_layered, B, N, H, W)
+    if not rows and tuple(disp_layered.shape) != (B, N, H, W):
         disp_layered = disp_layered.expand(B, N, H, W)
-    per_plane = disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
-    plane = _per_plane_view(disp_layered) if per_plane else disp_layered
-    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | (0 if per_plane else C.PD_TAIL_DISP_DENSE) | bf16
+    per_plane = not rows and disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
+    plane = _rows_of(disp_layered) if rows else _per_plane_view(disp_layered) if per_plane else disp_layered
+    flags = ((C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | bf16 |
+             (C.PD_TAIL_DISP_ROWS if rows else 0 if per_plane else C.PD_TAIL_DISP_DENSE))
     if padding_mask is not None:
+        if _row_view(padding_mask, B, N, H, W, "padding_mask"):
+            padding_mask = padding_mask.detach()[..., 0]
+            flags |= C.PD_TAIL_MASK_ROWS
         if padding_mask.dtype != torch.float32:
             padding_mask = padding_mask.float()
-        if tuple(padding_mask.shape) != (B, N, H, W):
+        if not flags & C.PD_TAIL_MASK_ROWS and tuple(padding_mask.shape) != (B, N, H, W):
             padding_mask = padding_mask.expand(B, N, H, W)
     # fuse_sweep_backward: the caller's promise that logits / sigma feed (with gradient) exactly ONE plane sweep — the trainer's
     # single-view pred_novel_images — whose backward kernel then applies this tail's backward too (TailLink).  Sweeps are
@@ -273,7 +285,9 @@ def plade_tail(raw_logits, raw_sigma, disp_layered, ray_norm=None, use_mixture_l
     network's expanded view of per-plane scalars or a dense map (ground planes).  Returns (logits [B,N,H,W], dists
     [B,N-1,H,W], sigma | None, disp, depth, layers) where ``layers()`` materialises ``(pi, probability)`` on demand (no
     gradient: nothing in the reference's losses reads them).  bf16 conv outputs (``torch.autocast``) are taken natively under the
-    rule of ``decoder_tail``: ``logits`` / ``sigma`` and the conv outputs' gradients are bf16, ``dists`` and the rest fp32."""
+    rule of ``decoder_tail``: ``logits`` / ``sigma`` and the conv outputs' gradients are bf16, ``dists`` and the rest fp32.
+    This tail has no row form: a row view (``plane_geometry``'s ``disp_layered``, ``stride(3) == 0``) is materialised to the dense
+    map by ``_contig`` — correct, and no faster than a dense map."""
     B, Nm1, H, W = raw_logits.shape
     N = Nm1 + 1
     bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
@@ -341,3 +355,85 @@ def plane_disparities(levels, disp_min, disp_max, width, no_levels=None):
                                         0.1 * 0.58 * width)
     return disp.reshape(B, N, 1, 1), distance
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The decoder's geometry head in row form (networks/depth_decoder.py:148-207, yz_levels == 0)
+# ---------------------------------------------------------------------------------------------------------------------
+class _PlaneGeometry(torch.autograd.Function):
+    """(grid [B,2,H,W], residual [B,N] | None) -> (disp_rows [B,N,H], mask_rows [B,N,H], distance [B,N], norm [B,N,3]); one launch
+    each way (pd_plane_geometry_fwd / _bwd).  Gradients flow into ``residual`` from ``disp_rows`` and ``distance``."""
+
+    @staticmethod
+    def forward(ctx, grid, residual, cfg):
+        lib = C.load()
+        no_levels, xz_levels = cfg[0], cfg[1]
+        B, _, H, W = grid.shape
+        N = no_levels + xz_levels
+        grid, residual = _contig(grid), _contig(residual)
+        dev = grid.device
+        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
+        disp_rows, mask_rows, distance, norm = new(B, N, H), new(B, N, H), new(B, N), new(B, N, 3)
+        with C.on_device(dev), _timed("plane_geometry_fwd"):
+            C.check(lib.pd_plane_geometry_fwd(B, no_levels, xz_levels, H, W, 0, *cfg[2:], C.ptr(residual), C.ptr(grid),
+                                              C.ptr(disp_rows), C.ptr(mask_rows), C.ptr(distance), C.ptr(norm),
+                                              C.stream_handle(dev)), "pd_plane_geometry_fwd")
+        ctx.save_for_backward(grid, residual, disp_rows)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(mask_rows, norm)
+        ctx.set_materialize_grads(False)
+        return disp_rows, mask_rows, distance, norm
+
+    @staticmethod
+    def backward(ctx, g_rows, _g_mask, g_distance, _g_norm):
+        lib = C.load()
+        grid, residual, disp_rows = ctx.saved_tensors
+        if residual is None or not ctx.needs_input_grad[1] or (g_rows is None and g_distance is None):
+            return None, None, None
+        B, _, H, W = grid.shape
+        g_rows, g_distance = _contig(g_rows), _contig(g_distance)
+        g_residual = torch.empty_like(residual)
+        with C.on_device(grid.device), _timed("plane_geometry_bwd"):
+            C.check(lib.pd_plane_geometry_bwd(B, ctx.cfg[0], ctx.cfg[1], H, W, 0, *ctx.cfg[2:], C.ptr(residual), C.ptr(grid),
+                                              C.ptr(disp_rows), C.ptr(g_rows), C.ptr(g_distance), C.ptr(g_residual),
+                                              C.stream_handle(grid.device)), "pd_plane_geometry_bwd")
+        return None, g_residual, None
+
+
+def plane_geometry(grid, residual, *, no_levels, xz_levels, disp_min, disp_max, xz_min, xz_max, check_contract=None):
+    """The geometry head of ``DepthDecoder.forward`` for xy + xz planes (networks/depth_decoder.py:148-207, ``yz_levels == 0``) as
+    one autograd node: ``grid`` = ``inputs["grid"]`` [B,2,H,W], ``residual`` = ``sigmoid(residualconv) - 0.5`` as [B,N] or
+    [B,N,1,1] (N = no_levels + xz_levels; ``None`` without ``--plane_residual``).  Returns ``(disp_layered, padding_mask,
+    distance [B,N], norm [B,N,3])``: ``disp_layered`` and ``padding_mask`` (float 0 / 1) have the reference's shape [B,N,H,W]
+    and are ROW VIEWS — ``stride(3) == 0`` over [B,N,H] row tensors; nothing [B,N,H,W]-sized exists behind them.
+    ``decoder_tail``, ``plane_sweep_disp``, ``post_process_disp`` and the trainer path recognise such a view by its strides and
+    take their row forms with no ``row_uniform`` promise.
+
+    Gradients reach ``residual`` through ``disp_layered`` and ``distance``.  The package's row consumers hang on the rows
+    tensor's node directly (their gradient is [B,N,H]); a foreign torch consumer of the view gets the right gradient as well
+    (``_RowView``: summed over x; a gradient that is itself constant along x is not touched W times).
+
+    The y channel of ``grid`` is taken to be constant along x and the x extent of a row is taken from its first and last column:
+    true for every grid datasets/pair_transforms.py makes.  ``check_contract=True`` (default: the environment's
+    ``PD_CHECK_CONTRACT``) verifies the y channel on the data (one reduction and a host sync) and raises ``ValueError``; a
+    sheared or rotated grid must keep the reference's dense lines."""
+    C.require_gpu_tensor("grid", grid)
+    if grid.dim() != 4 or grid.shape[1] != 2:
+        raise ValueError("grid must be [B,2,H,W], got %s" % (tuple(grid.shape),))
+    B, _, H, W = grid.shape
+    no_levels, xz_levels = int(no_levels), int(xz_levels)
+    N = no_levels + xz_levels
+    if residual is not None:
+        C.require_gpu_tensor("residual", residual)
+        if tuple(residual.shape) not in ((B, N), (B, N, 1, 1)):
+            raise ValueError("residual must be [B,N] or [B,N,1,1] with N = no_levels + xz_levels = %d, got %s"
+                             % (N, tuple(residual.shape)))
+        residual = residual.reshape(B, N)
+    if check_contract is None:
+        check_contract = bool(os.environ.get("PD_CHECK_CONTRACT"))
+    if check_contract and xz_levels > 0 and not bool((grid[:, 1] == grid[:, 1, :, :1]).all()):
+        raise ValueError("plane_geometry takes a grid whose y channel is constant along x, but this one is not (a sheared or "
+                         "rotated grid must keep the reference's dense geometry)")
+    cfg = (no_levels, xz_levels, float(disp_min), float(disp_max), float(xz_min), float(xz_max))
+    disp_rows, mask_rows, distance, norm = _PlaneGeometry.apply(grid, residual, cfg)
+    return row_view(disp_rows, W), row_view(mask_rows, W), distance, norm

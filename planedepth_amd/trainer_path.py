@@ -87,9 +87,13 @@ def pred_novel_images(self, inputs, outputs):
         pm, dl = outputs.get("padding_mask"), outputs.get("disp_layered")   # (homography_warp does not read disp_layered)
         if padding_mask is None and pm is not None and not bool((pm == 1).all()):
             raise ValueError("opt.xz_levels == opt.yz_levels == 0 promises an all-ones padding_mask, but it has zeros")
-        if row_uniform and dl is not None and dl.dim() == 4 and dl.shape[-1] > 1 and not bool((dl == dl[..., :1]).all()):
+        # (a row view — stride(3) == 0, ops.plane_geometry's — is constant along x by construction: nothing to check, and the
+        # sweep takes its row route from the strides, with or without the promise)
+        if (row_uniform and dl is not None and dl.dim() == 4 and dl.shape[-1] > 1 and dl.stride(3) != 0
+                and not bool((dl == dl[..., :1]).all())):
             raise ValueError("opt.yz_levels == 0 promises disparities that are constant along x, but disp_layered is not")
-        if row_uniform and pm is not None and pm.dim() == 4 and pm.shape[-1] > 1 and not bool((pm == pm[..., :1]).all()):
+        if (row_uniform and pm is not None and pm.dim() == 4 and pm.shape[-1] > 1 and pm.stride(3) != 0
+                and not bool((pm == pm[..., :1]).all())):
             raise ValueError("opt.yz_levels == 0 promises a padding_mask that is constant along x, but it is not")
     # Several target views (trainer.py:532; mono training: ["r", -1, 1]) sweep the same logits / sigma: they are issued as
     # ONE autograd node whose backward kernels add their gradients in place (ops._MultiPlaneSweep) instead of one node
@@ -272,7 +276,8 @@ def generate_post_process_disp(self, inputs):
         check = True
     if check is None:
         check = not getattr(self, "_pd_pp_contract_checked", False)
-    if check and row_uniform and dl.dim() == 4 and dl.shape[-1] > 1 and not bool((dl == dl[..., :1]).all()):
+    if (check and row_uniform and dl.dim() == 4 and dl.shape[-1] > 1 and dl.stride(3) != 0   # (a row view needs no check)
+            and not bool((dl == dl[..., :1]).all())):
         raise ValueError("opt.yz_levels == 0 promises disparities that are constant along x, but disp_layered is not")
     try:
         self._pd_pp_contract_checked = True
