@@ -83,7 +83,7 @@ enum pd_sweep_flags {
                          zeroed once for many calls): the kernels add into it, and the entry point then issues no memset
                          launch of its own (4-5 us per call next to a 0.1 ms kernel).  Ignored by the other entry points */
   ,
-  PD_BWD_PLANE_ZEROED = 1024 /* pd_plane_sweep_bwd / _bwd_tail, PD_WARP_DISP with one disparity per plane: the caller hands `g_plane`
+  PD_BWD_PLANE_ZEROED = 1024 /* pd_plane_sweep_bwd / _bwd_tail / _bwd_tail_rows, PD_WARP_DISP with one disparity per plane: the caller hands `g_plane`
                          [B,N] over holding zeros (e.g. a slice of a buffer it zeroed once for many calls).  Where
                          pd_sweep_bwd_plane_adds(d) == 1 (the row-stream backward) every row workgroup then ADDS its share with
                          atomics and the entry point launches no reduction kernel of its own (4-5 us + a launch gap per call next
@@ -244,6 +244,30 @@ int pd_plane_sweep_bwd_tail(const pd_sweep_desc* d, const float* src, const floa
                             const float* g_rgb_rec, const float* g_ph_map, const float* g_ph_mean, const float* raw_sigma,
                             const float* tail_stash, const float* disp, const float* g_disp, const float* g_depth,
                             float* g_raw_logits, float* g_raw_sigma, float* g_plane, float* workspace, pd_stream_t stream);
+
+/*
+ * pd_plane_sweep_bwd_tail for the row form of xy + xz planes (networks/depth_decoder.py:153-181: disparity and padding mask
+ * are constant along x): `plane` is [B,N] or, PD_DISP_ROWS, [B,N,H]; `mask_rows` is the [B,N,H] float 0 / 1 mask that BOTH
+ * pd_decoder_tail_fwd (PD_TAIL_MASK_ROWS) and the sweep (PD_MASK_ROWS) were given — required with PD_MASK_ROWS, NULL without it.
+ * All four combinations are served; with neither flag the call is pd_plane_sweep_bwd_tail's.  The results are what
+ * pd_plane_sweep_bwd + pd_decoder_tail_bwd (PD_TAIL_DISP_ROWS / PD_TAIL_MASK_ROWS) produce: with m = the mask,
+ * P = m softmax(logits) / sigma / sum(m pi / sigma) (tail_stash holds the log-sum-exp over the MASKED logits, where a masked plane
+ * enters with logit 0, and sum(m pi / sigma)); at an unmasked element the formulas of pd_plane_sweep_bwd_tail hold as they stand.
+ * At a masked (b, n, y) g_raw_logits, g_raw_sigma and the tail's share of g_plane are exact zeros by selection — whatever
+ * `plane` holds there, a non-finite value included.  g_plane has the shape of `plane`: with PD_DISP_ROWS the row workgroup
+ * that owns (b, y) writes the warp's + the tail's share of [B,N,H] directly (no workspace, no reduction launch); else as in
+ * pd_plane_sweep_bwd_tail (PD_BWD_PLANE_ZEROED honoured).
+ * Served where pd_sweep_bwd_tail_rows_fuses(d) == 1: PD_WARP_DISP, PD_MIXTURE, sign = +-1, fp32 storage, no PD_DISP_DENSE, no
+ * PD_RENDER_PROB, even W, the row-stream backward's plain LDS layout (+ 4 N bytes for a row form); PD_ERR_UNSUPPORTED otherwise and
+ * for PD_LOGITS_BF16.  pd_sweep_bwd_tail_fuses keeps answering for pd_plane_sweep_bwd_tail alone (0 for the row flags).
+ */
+int pd_sweep_bwd_tail_rows_fuses(const pd_sweep_desc* d);
+int pd_plane_sweep_bwd_tail_rows(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits,
+                                 const float* sigma, const float* plane, const float* mask_rows, const float* rgb_rec,
+                                 const float* stash, const float* g_rgb_rec, const float* g_ph_map, const float* g_ph_mean,
+                                 const float* raw_sigma, const float* tail_stash, const float* disp, const float* g_disp,
+                                 const float* g_depth, float* g_raw_logits, float* g_raw_sigma, float* g_plane,
+                                 float* workspace, pd_stream_t stream);
 
 /*
  * The per-plane tensors the reference stores in `outputs` and the fused path never needs (trainer.py:582-602):

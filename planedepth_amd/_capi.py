@@ -76,6 +76,8 @@ SIGNATURES = {
     "pd_plane_sweep_layers": (_I, [_D] + [_P] * 14),
     "pd_sweep_bwd_tail_fuses": (_I, [_D]),
     "pd_plane_sweep_bwd_tail": (_I, [_D] + [_P] * 20),
+    "pd_sweep_bwd_tail_rows_fuses": (_I, [_D]),
+    "pd_plane_sweep_bwd_tail_rows": (_I, [_D] + [_P] * 21),
     "pd_uniform_gather_pair": (_I, [_D] + [_P] * 9),
     "pd_uniform_fwd_pair": (_I, [_D] + [_P] * 3 + [ctypes.POINTER(SweepView)] * 2 + [_P]),
     "pd_uniform_bwd_pair": (_I, [_D] + [_P] * 3 + [ctypes.POINTER(SweepView)] * 2 + [_P] * 3),

@@ -473,6 +473,7 @@ SweepRoute pd::sweep_route(const pd_sweep_desc* d, const CallFacts& f) {
   r.accumulates = !r.rows;   // the row kernels' owner-computes ring stores have no read-modify-write form; the plane-uniform
                              // and gather stores do, and the atomic scatter accumulates by nature
   r.tail_fuses = r.rows && stream_ok && rowstream_bwd_tail_applicable(d, f.per_pixel_mask);
+  r.tail_rows_fuses = r.rows && stream_ok && rowstream_bwd_tail_rows_applicable(d, f.per_pixel_mask);
   r.fwd_err = r.bwd_err = PD_ERR_UNSUPPORTED;
 
   if (r.rows) {
@@ -488,7 +489,8 @@ SweepRoute pd::sweep_route(const pd_sweep_desc* d, const CallFacts& f) {
     }
     // default: lanes own aligned source slots, waves stream along plane rows (pd_plane_sweep_rowstream.hip); else the
     // target-ordered row-shift backward, which needs less LDS
-    r.bwd = f.tail ? (r.tail_fuses ? BwdFamily::RowStreamTail : BwdFamily::Unsupported)
+    r.bwd = f.tail_rows ? (r.tail_rows_fuses ? BwdFamily::RowStreamTailRows : BwdFamily::Unsupported)
+            : f.tail ? (r.tail_fuses ? BwdFamily::RowStreamTail : BwdFamily::Unsupported)
             : (stream_ok && rowstream_bwd_applicable(d, f.per_pixel_mask)) ? BwdFamily::RowStream : BwdFamily::RowShift;
     if (bf16 && r.bwd == BwdFamily::RowShift) {   // (validate() refused it)
       r.bwd = BwdFamily::Unsupported; r.bwd_err = PD_ERR_ARG;
@@ -497,13 +499,14 @@ SweepRoute pd::sweep_route(const pd_sweep_desc* d, const CallFacts& f) {
   } else {
     r.fwd = uniform ? FwdFamily::Uniform : FwdFamily::General;
     // one homography per plane: two passes, no atomics (pd_plane_sweep_gather.hip) where somebody wants g_logits / g_sigma
-    r.bwd = (f.tail || (!uniform && impl == PD_IMPL_TILE)) ? BwdFamily::Unsupported : uniform ? BwdFamily::Uniform
+    r.bwd = (f.tail || f.tail_rows || (!uniform && impl == PD_IMPL_TILE)) ? BwdFamily::Unsupported : uniform ? BwdFamily::Uniform
             : (r.gather_fits && f.wants_grads) ? BwdFamily::Gather : BwdFamily::Scatter;
   }
   if (r.bwd == BwdFamily::Unsupported && !r.bwd_why)
-    r.bwd_why = f.tail ? "pd_plane_sweep_bwd_tail: not served for this descriptor (pd_sweep_bwd_tail_fuses)"
+    r.bwd_why = f.tail_rows ? "pd_plane_sweep_bwd_tail_rows: not served for this descriptor (pd_sweep_bwd_tail_rows_fuses)"
+                : f.tail ? "pd_plane_sweep_bwd_tail: not served for this descriptor (pd_sweep_bwd_tail_fuses)"
                        : "PD_IMPL_TILE (the owned-tile backward) was removed: it was slower than the default kernels";
-  const bool streams = r.bwd == BwdFamily::RowStream || r.bwd == BwdFamily::RowStreamTail;
+  const bool streams = r.bwd == BwdFamily::RowStream || r.bwd == BwdFamily::RowStreamTail || r.bwd == BwdFamily::RowStreamTailRows;
   r.plane_adds = streams && !(d->flags & (PD_DISP_ROWS | PD_DISP_DENSE));
   // both kernels that read bf16 run (hence: row kernels, not PD_IMPL_ROWS1); PD_IMPL_UNIFORM_DIRECT is a homography cross-check
   r.serves_bf16 = bf16 && !(d->flags & PD_HOMO_UNIFORM) && impl != PD_IMPL_UNIFORM_DIRECT &&
@@ -529,6 +532,8 @@ extern "C" int pd_sweep_bwd_accumulates(const pd_sweep_desc* d) { return (d && q
 extern "C" int pd_sweep_bwd_plane_adds(const pd_sweep_desc* d) { return (d && query_route(d).plane_adds) ? 1 : 0; }
 
 extern "C" int pd_sweep_bwd_tail_fuses(const pd_sweep_desc* d) { return (d && query_route(d).tail_fuses) ? 1 : 0; }
+
+extern "C" int pd_sweep_bwd_tail_rows_fuses(const pd_sweep_desc* d) { return (d && query_route(d).tail_rows_fuses) ? 1 : 0; }
 
 extern "C" size_t pd_sweep_stash_floats(const pd_sweep_desc* d) {
   if (!d) return 0;
@@ -600,7 +605,11 @@ extern "C" int pd_plane_sweep_fwd(const pd_sweep_desc* d, const float* src, cons
   return check_launch("sweep_fwd_kernel");
 }
 
-struct TailIn { const float* raw_sigma; const float* stash; const float* disp; const float* g_disp; const float* g_depth; };
+struct TailIn {
+  const float* raw_sigma; const float* stash; const float* disp; const float* g_disp; const float* g_depth;
+  const char* entry;   // the entry point's name, for messages
+  bool rows;           // pd_plane_sweep_bwd_tail_rows
+};
 
 static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits,
                           const float* sigma, const float* plane, const float* plane_aux, const float* inv_K3,
@@ -622,12 +631,13 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   CallFacts f = assumed_facts();
   f.per_pixel_mask = ak.has_mask != 0;
   f.wants_grads = g_logits || g_sigma;
-  f.tail = tail != nullptr;
+  f.tail = tail != nullptr && !tail->rows;
+  f.tail_rows = tail != nullptr && tail->rows;
   const SweepRoute r = sweep_route(d, f);
   PD_REQUIRE(!accumulate || r.accumulates, "PD_BWD_ACCUMULATE is not served for this descriptor (pd_sweep_bwd_accumulates)");
   if (d->flags & PD_LOGITS_BF16) {
     if (tail) {
-      set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_bwd_tail");
+      set_error("PD_LOGITS_BF16: not served by %s", tail->entry);
       return PD_ERR_UNSUPPORTED;
     }
     PD_REQUIRE(!((reinterpret_cast<uintptr_t>(g_logits) | reinterpret_cast<uintptr_t>(g_sigma)) & 3),
@@ -641,8 +651,9 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   if (r.rows) PD_REQUIRE(workspace, "the row-shift backward needs workspace (pd_sweep_bwd_workspace_floats)");
   switch (r.bwd) {
     case BwdFamily::Unsupported: set_error("%s", r.bwd_why); return r.bwd_err;
-    case BwdFamily::RowStreamTail:   // pd_plane_sweep_bwd_tail: the row-stream backward with the decoder tail's backward riding along
-      PD_REQUIRE(g_logits && g_sigma, "pd_plane_sweep_bwd_tail writes both g_raw_logits and g_raw_sigma");
+    case BwdFamily::RowStreamTail:   // pd_plane_sweep_bwd_tail(_rows): the row-stream backward with the decoder tail's backward riding along
+    case BwdFamily::RowStreamTailRows:
+      PD_REQUIRE(g_logits && g_sigma, "%s writes both g_raw_logits and g_raw_sigma", tail->entry);
       o.tail_raw_sigma = tail->raw_sigma; o.tail_stash = tail->stash; o.tail_disp = tail->disp;
       o.tail_g_disp = tail->g_disp; o.tail_g_depth = tail->g_depth;
       return rowstream_bwd(d, ak, o, stream);
@@ -706,8 +717,26 @@ extern "C" int pd_plane_sweep_bwd_tail(const pd_sweep_desc* d, const float* src,
     return PD_ERR_UNSUPPORTED;
   }
   PD_REQUIRE(raw_sigma && tail_stash && disp, "raw_sigma / tail_stash / disp must not be NULL");
-  const TailIn t = {raw_sigma, tail_stash, disp, g_disp, g_depth};
+  const TailIn t = {raw_sigma, tail_stash, disp, g_disp, g_depth, "pd_plane_sweep_bwd_tail", false};
   return sweep_bwd_impl(d, src, tgt, logits, sigma, plane, nullptr, nullptr, nullptr, nullptr, rgb_rec, stash, g_rgb_rec,
+                        g_ph_map, g_ph_mean, g_raw_logits, g_raw_sigma, g_plane, nullptr, workspace, stream, &t);
+}
+
+extern "C" int pd_plane_sweep_bwd_tail_rows(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits,
+                                            const float* sigma, const float* plane, const float* mask_rows,
+                                            const float* rgb_rec, const float* stash, const float* g_rgb_rec,
+                                            const float* g_ph_map, const float* g_ph_mean, const float* raw_sigma,
+                                            const float* tail_stash, const float* disp, const float* g_disp,
+                                            const float* g_depth, float* g_raw_logits, float* g_raw_sigma, float* g_plane,
+                                            float* workspace, pd_stream_t stream) {
+  if (d && (d->flags & PD_LOGITS_BF16)) {
+    set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_bwd_tail_rows");
+    return PD_ERR_UNSUPPORTED;
+  }
+  PD_REQUIRE(raw_sigma && tail_stash && disp, "raw_sigma / tail_stash / disp must not be NULL");
+  PD_REQUIRE(!d || (d->flags & PD_MASK_ROWS) || !mask_rows, "mask_rows [B,N,H] goes with PD_MASK_ROWS (no other mask form is served)");
+  const TailIn t = {raw_sigma, tail_stash, disp, g_disp, g_depth, "pd_plane_sweep_bwd_tail_rows", true};
+  return sweep_bwd_impl(d, src, tgt, logits, sigma, plane, nullptr, nullptr, mask_rows, nullptr, rgb_rec, stash, g_rgb_rec,
                         g_ph_map, g_ph_mean, g_raw_logits, g_raw_sigma, g_plane, nullptr, workspace, stream, &t);
 }
 

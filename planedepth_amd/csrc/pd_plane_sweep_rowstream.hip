@@ -70,6 +70,11 @@ namespace pd {
 #define PD_STREAM_OCC 4  // launch bound (1024 threads): the allocator's cap is 128 VGPRs; the kernel uses 76 = 6 waves per SIMD
 #endif
 
+// TAIL forms of the kernel: the fused decoder tail's backward rides along (pd_plane_sweep_bwd_tail / _bwd_tail_rows).
+// kTailPlane is the form of one disparity per plane and no mask; kTailRows adds what PD_DISP_ROWS / PD_MASK_ROWS need (a
+// per-plane "in view on this row" flag) under its own instantiation, so that kTailPlane's code is what it was without it.
+constexpr int kTailNone = 0, kTailPlane = 1, kTailRows = 2;
+
 constexpr int kSlots = 2;               // source slots per lane
 constexpr int kSeg = kWave * kSlots;    // slots per wave iteration
 constexpr int kStreamThreadsMax = 1024;
@@ -99,7 +104,8 @@ struct StreamLds {
   float* hand;    // [nwaves][2] carries that leave a wave's range in the middle of a row
   int* special;   // [1]  any plane with a negative shift or an irregular one (the epilogue has work)
   float4* tail;   // TAIL: [CW] per SOURCE pixel (lse of the decoder's logits, 1 / sum pi/sigma, disp, d loss / d disp)
-  float* dpl;     // TAIL: [N]  the planes' disparities (unsigned, unclamped: the decoder's disp_layered)
+  float* dpl;     // TAIL: [N]  the planes' disparities on this row (unsigned, unclamped: the decoder's disp_layered)
+  int* mrow;      // kTailRows: [N]  0: the row's padding mask is 0 for the plane (the tail's terms are exact zeros there), else 1
   int* live;      // [N]  dead items: first live segment | (one past the last live segment) << 16
   // bf16 storage only (every gradient element rounded once, from fp32): slots that still take an addend after their item
   // keep their fp32 pair here instead of being stored — (l0, l1, s0, s1)
@@ -260,7 +266,7 @@ __device__ __forceinline__ void stream_store(const SweepArgs& a, const BwdOut& o
 
 // One regular (plane, segment) iteration.  carry_*: right-tap contribution of the previous segment's last slot (wave
 // uniform); returns this segment's in the same variables.
-template <class T, bool MIX, int NROWS, bool PK, bool TAIL>
+template <class T, bool MIX, int NROWS, bool PK, int TAIL>
 __device__ __forceinline__ void stream_compute(const StreamGroup<T, NROWS>& gq, const SweepArgs& a, const BwdOut& o,
                                                const StreamRow& r, const StreamLds& L, int n, int seg, int k, float sd,
                                                int lane, unsigned lane8, float lane2f, int HW, float Wm1, float rcpWm1,
@@ -321,11 +327,18 @@ __device__ __forceinline__ void stream_compute(const StreamGroup<T, NROWS>& gq, 
     const int own = (NROWS == 2 && r.yA != r.y) ? NROWS - 1 : 0;
     const float dn = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(L.dpl[n])));
     const float* rs = o.tail_raw_sigma + ((long)r.b * a.N + n) * HW + (long)r.y * a.W + xs0;
-    const TailTerm t0 = tail_term(L.tail[xs0 + 2], g.l[own][0], g.s[own][0], dn, rs);
-    const TailTerm t1 = tail_term(L.tail[xs0 + 3], g.l[own][1], g.s[own][1], dn, rs + 1);
-    out_l0 += t0.t; out_l1 += t1.t;
-    out_s0 = (out_s0 - t0.tos) * t0.fs; out_s1 = (out_s1 - t1.tos) * t1.fs;
-    if (want_plane) gacc += a.sign * (t0.gdl + t1.gdl);   // (the row's sum is scaled by d ix / d disp = sign at the end: sign^2 = 1)
+    // kTailRows: a plane whose padding mask is 0 on this row (wave-uniform) has P = 0 at every element of the row: the conv
+    // outputs' gradients and the tail's disparity share are zeros BY SELECTION, whatever the plane's disparity holds there (the
+    // sweep's own shares are zeros already: stage_shift put the plane out of view)
+    if (TAIL == kTailRows && __builtin_amdgcn_readfirstlane(L.mrow[n]) == 0) {
+      out_l0 = out_l1 = out_s0 = out_s1 = 0.0f;
+    } else {
+      const TailTerm t0 = tail_term(L.tail[xs0 + 2], g.l[own][0], g.s[own][0], dn, rs);
+      const TailTerm t1 = tail_term(L.tail[xs0 + 3], g.l[own][1], g.s[own][1], dn, rs + 1);
+      out_l0 += t0.t; out_l1 += t1.t;
+      out_s0 = (out_s0 - t0.tos) * t0.fs; out_s1 = (out_s1 - t1.tos) * t1.fs;
+      if (want_plane) gacc += a.sign * (t0.gdl + t1.gdl);   // (the row's sum is scaled by d ix / d disp = sign at the end: sign^2 = 1)
+    }
   }
   stream_store<T>(a, o, r, n, seg, lane, lane8, HW, gl_bytes, gs_bytes, MIX, out_l0, out_l1, out_s0, out_s1, defer);
 }
@@ -334,7 +347,7 @@ __device__ __forceinline__ void stream_compute(const StreamGroup<T, NROWS>& gq, 
 // floor(ix); contributions go to the gradient rows with atomics, the disparity-gradient term is returned.
 // Used for irregular planes (rows zero-filled up front) and for the virtual slots of the epilogue.  LDS_DST (bf16 storage):
 // the contributions go with LDS atomics to the fp32 row (or pair) dl / ds, indexed by column, instead.
-template <class T, bool MIX, int NROWS, bool PK, bool TAIL, bool LDS_DST = false>
+template <class T, bool MIX, int NROWS, bool PK, int TAIL, bool LDS_DST = false>
 __device__ __forceinline__ float stream_general_slot(   // (as a call: 123 VGPRs + scratch — measured, NOTEBOOK.md 3.6.4)
     const SweepArgs& a, const BwdOut& o, const StreamRow& r,
                                                      const StreamLds& L, int n, int xs, int k, float sd, bool on, int HW,
@@ -398,7 +411,7 @@ __device__ __forceinline__ float stream_general_slot(   // (as a call: 123 VGPRs
 
 // Stage target row r.y of image r.b for its workgroup: per-target-pixel context (cell = pixel + 2, zero-gradient guard cells),
 // the (vertically blended) source colour row and, TAIL, the decoder tail's per-source-pixel terms.
-template <bool MIX, int NROWS, bool PK, bool TAIL>
+template <bool MIX, int NROWS, bool PK, int TAIL>
 __device__ __forceinline__ void stream_stage_ctx(const SweepArgs& a, const BwdOut& o, const StreamRow& r, const StreamLds& L, int HW) {
   const int W = a.W;
   const float* srcb = a.src + (long)r.b * 3 * HW;
@@ -438,7 +451,7 @@ __device__ __forceinline__ void stream_stage_ctx(const SweepArgs& a, const BwdOu
 }
 
 // One plane's staged shift (stream_body's form) + its live segment range (dead items).  Returns "special".
-template <bool TAIL>
+template <int TAIL>
 __device__ __forceinline__ int stage_shift(const SweepArgs& a, const StreamLds& L, int i, float plane_i, bool masked, int nseg) {
   const int W = a.W;
   const float lim = (float)(W + 2), tol = irregular_tol(W);
@@ -450,6 +463,7 @@ __device__ __forceinline__ int stage_shift(const SweepArgs& a, const StreamLds& 
   const int irr = (inview && (fr < tol || fr > 1.0f - tol)) ? 1 : 0;
   L.shift[i] = make_int2(__float_as_int(sd), k * 2 + irr);
   if (TAIL) L.dpl[i] = plane_i;
+  if (TAIL == kTailRows) L.mrow[i] = masked ? 0 : 1;
   L.red[i] = 0.0f;
   // Slot xs serves the targets xs - k (left tap) and xs - 1 - k (right tap).  k >= 0: none of segment s is inside the row when
   // s * kSeg + kSeg - 1 < k; k < 0: when s * kSeg - 1 - k >= W.  Irregular planes keep every segment (their general path decides).
@@ -462,7 +476,7 @@ __device__ __forceinline__ int stage_shift(const SweepArgs& a, const StreamLds& 
   return (irr || (k < 0 && inview)) ? 1 : 0;
 }
 
-template <class T, bool MIX, int NROWS, bool PK, bool TAIL>
+template <class T, bool MIX, int NROWS, bool PK, int TAIL>
 __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o, int b, int y, const RowSel& row, const StreamLds& L) {
   constexpr int D = (NROWS == 1) ? PD_STREAM_D1 : PD_STREAM_D2;
   constexpr bool BF = sizeof(T) == 2;   // bf16 storage (never with TAIL)
@@ -525,6 +539,8 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   special = __builtin_amdgcn_readfirstlane(*L.special);
 
   if (special && !BF) {   // irregular planes: their gradient rows are accumulated with atomics, so they start from zero
+    // (kTailRows: a plane that is masked on this row is staged out of view, which is never irregular — every plane that gets
+    // here is in view, its tail term is owed in full)
     for (int n2 = 0; n2 < N; ++n2) {
       if (!(L.shift[n2].y & 1)) continue;
       for (int x = threadIdx.x; x < W; x += blockDim.x) {
@@ -704,9 +720,10 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   }
 }
 
-// (TAIL: the tail's terms take the kernel from 77 to 93 VGPRs, which costs the third resident workgroup; bounded at six waves per
-// SIMD it keeps it for twelve spilled dwords outside the loop: 0.175 against 0.196 ms, next to 0.174 + 0.208 ms for the two kernels)
-template <class T, bool MIX, bool PK, bool TAIL>
+// (TAIL: left to itself the allocator took the tail's terms to 93 VGPRs, which costs the third resident workgroup.  Bounded at six
+// waves per SIMD both tail forms, kTailPlane and kTailRows, build to 80 VGPRs and 60 bytes of scratch, spilled outside the loop, and
+// keep it: kTailPlane 0.175 against 0.196 ms, next to 0.174 + 0.208 ms for the two kernels)
+template <class T, bool MIX, bool PK, int TAIL>
 __global__ __launch_bounds__(kStreamThreadsMax, (TAIL || sizeof(T) == 2) ? 6 : PD_STREAM_OCC) void rowstream_bwd_kernel(SweepArgs a, BwdOut o) {
   extern __shared__ float4 lds4[];
   StreamLds L;
@@ -722,6 +739,7 @@ __global__ __launch_bounds__(kStreamThreadsMax, (TAIL || sizeof(T) == 2) ? 6 : P
   L.special = reinterpret_cast<int*>(L.hand + 2 * (blockDim.x >> 6));
   L.dpl = reinterpret_cast<float*>(L.special + 4);
   L.live = reinterpret_cast<int*>(L.dpl + a.N);
+  L.mrow = L.live + a.N;   // (rowstream_lds_bytes: kTailRows; never with bf16 storage, whose arrays start at the same place)
   L.CWr = nseg * kSeg;
   if (sizeof(T) == 2) {   // (rowstream_lds_bytes: bf16)
     L.fix = reinterpret_cast<float*>(L.live + a.N);
@@ -746,15 +764,16 @@ __global__ __launch_bounds__(kStreamThreadsMax, (TAIL || sizeof(T) == 2) ? 6 : P
 // it buys a workgroup per CU (192 x 640: 42 KB, three workgroups either way; 384 x 1280: 83 KB = ONE workgroup plain,
 // 72 KB = two packed).
 // bf16 storage (PD_LOGITS_BF16) adds the parked pairs and two fp32 rows for the irregular planes: 5 KB at W = 640.
-static size_t rowstream_lds_bytes(const pd_sweep_desc* d, int nwaves, bool packed, bool tail = false) {
+static size_t rowstream_lds_bytes(const pd_sweep_desc* d, int nwaves, bool packed, int tail = kTailNone) {
   const size_t CW = (size_t)ceil_div(d->W, kSeg) * kSeg + 4;
   const size_t bf16 = (d->flags & PD_LOGITS_BF16) ? (size_t)d->N * 5 * sizeof(float) + (size_t)nwaves * 4 * sizeof(float) +
                                                        (CW - 4) * 2 * sizeof(float) : 0;
   return CW * (packed ? 3 * sizeof(float4) + sizeof(float2) : (tail ? 5 : 4) * sizeof(float4)) +
-         (size_t)d->N * (sizeof(float2) + 3 * sizeof(float)) + (size_t)nwaves * 2 * sizeof(float) + 32 + bf16;
+         (size_t)d->N * (sizeof(float2) + 3 * sizeof(float) + (tail == kTailRows ? sizeof(int) : 0)) +
+         (size_t)nwaves * 2 * sizeof(float) + 32 + bf16;
 }
 struct StreamShape { int nwaves; bool packed; size_t lds; };
-static StreamShape rowstream_shape(const pd_sweep_desc* d, bool tail = false) {
+static StreamShape rowstream_shape(const pd_sweep_desc* d, int tail = kTailNone) {
   const size_t kCuLds = device_lds_bytes();
   // workgroups per CU by LDS (at most three: 24 waves per CU at the kernel's 77 VGPRs); waves per workgroup to fill them:
   // three workgroups of 8, two of 12, one of 16
@@ -777,7 +796,7 @@ bool rowstream_bwd_applicable(const pd_sweep_desc* d, bool per_pixel_mask) {
 
 size_t rowstream_bwd_workspace_floats(const pd_sweep_desc* d) { return (size_t)d->B * d->H * d->N; }
 
-template <bool MIX, bool PK, bool TAIL, class T = float>
+template <bool MIX, bool PK, int TAIL, class T = float>
 static int rowstream_launch(const SweepArgs& a, const BwdOut& o, dim3 grid, dim3 block, size_t shmem, hipStream_t stream) {
   static LdsGrant granted;   // per instantiation and device: the attribute is set once (and checked), not per launch
   const int rc = grant_dynamic_lds((const void*)rowstream_bwd_kernel<T, MIX, PK, TAIL>, shmem, &granted, "rowstream_bwd_kernel");
@@ -790,25 +809,35 @@ static int rowstream_launch(const SweepArgs& a, const BwdOut& o, dim3 grid, dim3
 // mixture, one disparity per plane, unit sign.
 bool rowstream_bwd_tail_applicable(const pd_sweep_desc* d, bool per_pixel_mask) {
   return rowstream_bwd_applicable(d, per_pixel_mask) && (d->flags & PD_MIXTURE) && !(d->flags & (PD_DISP_ROWS | PD_MASK_ROWS)) &&
-         (d->sign == 1.0f || d->sign == -1.0f) && rowstream_shape(d, true).lds <= device_lds_bytes();
+         (d->sign == 1.0f || d->sign == -1.0f) && rowstream_shape(d, kTailPlane).lds <= device_lds_bytes();
+}
+
+// pd_plane_sweep_bwd_tail_rows: the same for per-row disparities (PD_DISP_ROWS) and / or a per-row mask (PD_MASK_ROWS) — the
+// existing predicate without its exclusion of the two flags, with the row form's LDS (one more int per plane).  A descriptor
+// with neither flag is served by the per-plane form's kernel.
+static int tail_form(const pd_sweep_desc* d) { return (d->flags & (PD_DISP_ROWS | PD_MASK_ROWS)) ? kTailRows : kTailPlane; }
+bool rowstream_bwd_tail_rows_applicable(const pd_sweep_desc* d, bool per_pixel_mask) {
+  return rowstream_bwd_applicable(d, per_pixel_mask) && (d->flags & PD_MIXTURE) && !(d->flags & PD_LOGITS_BF16) &&
+         (d->sign == 1.0f || d->sign == -1.0f) && rowstream_shape(d, tail_form(d)).lds <= device_lds_bytes();
 }
 
 int rowstream_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, hipStream_t stream) {
-  const bool tail = o.tail_stash != nullptr;
+  const int tail = o.tail_stash == nullptr ? kTailNone : tail_form(d);
   const bool mix = (d->flags & PD_MIXTURE) != 0;
   const StreamShape sh = rowstream_shape(d, tail);
   const dim3 grid(d->H, d->B), block(sh.nwaves * kWave);
   int rc;
   if (d->flags & PD_LOGITS_BF16) {   // (pd_sweep_native_bf16: never with the tail)
-    if (mix) rc = sh.packed ? rowstream_launch<true, true, false, Bf16>(a, o, grid, block, sh.lds, stream)
-                            : rowstream_launch<true, false, false, Bf16>(a, o, grid, block, sh.lds, stream);
-    else     rc = sh.packed ? rowstream_launch<false, true, false, Bf16>(a, o, grid, block, sh.lds, stream)
-                            : rowstream_launch<false, false, false, Bf16>(a, o, grid, block, sh.lds, stream);
-  } else if (tail) rc = rowstream_launch<true, false, true>(a, o, grid, block, sh.lds, stream);
-  else if (mix) rc = sh.packed ? rowstream_launch<true, true, false>(a, o, grid, block, sh.lds, stream)
-                               : rowstream_launch<true, false, false>(a, o, grid, block, sh.lds, stream);
-  else          rc = sh.packed ? rowstream_launch<false, true, false>(a, o, grid, block, sh.lds, stream)
-                               : rowstream_launch<false, false, false>(a, o, grid, block, sh.lds, stream);
+    if (mix) rc = sh.packed ? rowstream_launch<true, true, kTailNone, Bf16>(a, o, grid, block, sh.lds, stream)
+                            : rowstream_launch<true, false, kTailNone, Bf16>(a, o, grid, block, sh.lds, stream);
+    else     rc = sh.packed ? rowstream_launch<false, true, kTailNone, Bf16>(a, o, grid, block, sh.lds, stream)
+                            : rowstream_launch<false, false, kTailNone, Bf16>(a, o, grid, block, sh.lds, stream);
+  } else if (tail == kTailRows) rc = rowstream_launch<true, false, kTailRows>(a, o, grid, block, sh.lds, stream);
+  else if (tail) rc = rowstream_launch<true, false, kTailPlane>(a, o, grid, block, sh.lds, stream);
+  else if (mix) rc = sh.packed ? rowstream_launch<true, true, kTailNone>(a, o, grid, block, sh.lds, stream)
+                               : rowstream_launch<true, false, kTailNone>(a, o, grid, block, sh.lds, stream);
+  else          rc = sh.packed ? rowstream_launch<false, true, kTailNone>(a, o, grid, block, sh.lds, stream)
+                               : rowstream_launch<false, false, kTailNone>(a, o, grid, block, sh.lds, stream);
   if (rc) return rc;
   rc = check_launch("rowstream_bwd_kernel");
   if (rc || !o.g_plane || (d->flags & (PD_DISP_ROWS | PD_BWD_PLANE_ZEROED))) return rc;

@@ -49,6 +49,7 @@ struct BwdOut {
   const float* g_ph_mean;  // optional: device scalar, upstream gradient of mean(ph_map)
   // pd_plane_sweep_bwd_tail (row-stream backward only): the fused decoder tail's backward rides along — g_logits / g_sigma
   // receive the gradients of the decoder's CONV outputs (networks/depth_decoder.py:258-291 through pd_decoder_tail_fwd)
+  // (pd_plane_sweep_bwd_tail_rows: the tail's [B,N,H] mask is the sweep's, SweepArgs::mask_rows; its disparities are `plane`)
   const float* tail_raw_sigma = nullptr;  // [B,N,H,W] sigmaconv output (read only where sigma sits on the lower clamp bound)
   const float* tail_stash = nullptr;      // [B,2,H,W] pd_decoder_tail_fwd's stash: log-sum-exp of the logits, sum pi/sigma
   const float* tail_disp = nullptr;       // [B,1,H,W]
@@ -262,12 +263,13 @@ struct CallFacts {
   bool dists_aligned;   // PD_RENDER_PROB: dists is 8-byte aligned
   bool wants_grads;     // backward: g_logits or g_sigma is asked for (else the gather's two passes have nothing to write)
   bool tail;            // pd_plane_sweep_bwd_tail: the decoder tail's backward rides along
+  bool tail_rows;       // pd_plane_sweep_bwd_tail_rows: the same, per-row disparities and / or a per-row mask allowed
 };
 // A capability query has no call at hand: no per-pixel mask, aligned tensors, gradients wanted, no tail.
-inline CallFacts assumed_facts() { return CallFacts{false, true, true, true, false}; }
+inline CallFacts assumed_facts() { return CallFacts{false, true, true, true, false, false}; }
 
 enum class FwdFamily { General, Uniform, RowShift, SegmentStream, Unsupported };
-enum class BwdFamily { Scatter, Gather, Uniform, RowShift, RowStream, RowStreamTail, Unsupported };
+enum class BwdFamily { Scatter, Gather, Uniform, RowShift, RowStream, RowStreamTail, RowStreamTailRows, Unsupported };
 
 struct SweepRoute {
   FwdFamily fwd;
@@ -279,6 +281,7 @@ struct SweepRoute {
   bool accumulates;       // the backward honours PD_BWD_ACCUMULATE (pd_sweep_bwd_accumulates)
   bool plane_adds;        // ... adds the plane gradient into a zeroed block under PD_BWD_PLANE_ZEROED (pd_sweep_bwd_plane_adds)
   bool tail_fuses;        // ... can take the decoder tail along (pd_sweep_bwd_tail_fuses)
+  bool tail_rows_fuses;   // ... also with PD_DISP_ROWS / PD_MASK_ROWS, through pd_plane_sweep_bwd_tail_rows (pd_sweep_bwd_tail_rows_fuses)
   bool serves_bf16;       // d->flags has PD_LOGITS_BF16 and both kernels that read bf16 serve it (pd_sweep_native_bf16 sets the flag)
   bool rowshift_fits, gather_fits;   // the families' own limits whatever `impl` asks for: what pd_sweep_bwd_workspace_floats sizes for
 };
@@ -302,6 +305,7 @@ int fwdstream_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, fl
 // Row-stream backward (pd_plane_sweep_rowstream.hip): lanes own aligned source slots, waves stream along plane rows.
 bool rowstream_bwd_applicable(const pd_sweep_desc* d, bool per_pixel_mask);
 bool rowstream_bwd_tail_applicable(const pd_sweep_desc* d, bool per_pixel_mask);
+bool rowstream_bwd_tail_rows_applicable(const pd_sweep_desc* d, bool per_pixel_mask);
 int rowstream_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, hipStream_t stream);
 size_t rowstream_bwd_workspace_floats(const pd_sweep_desc* d);
 

@@ -99,11 +99,13 @@ def fused_decoder_tail(outputs, dispconv_out, sigmaconv_out=None, *, use_mixture
     Reads ``outputs["disp_layered"]`` and ``outputs["padding_mask"]`` (skipped when ``all_ones_mask`` says the decoder
     built it with ``torch.ones_like``, i.e. xy planes only).
 
-    ``fuse_sweep_backward=True`` (xy planes, mixture loss, one target view): the promise that ``outputs["logits"]`` /
-    ``["sigma"]`` are consumed — as far as gradients go — by the trainer's plane sweep alone.  The sweep's backward kernel
-    then applies this tail's backward on the values it holds anyway and writes the conv outputs' gradients directly
-    (``ops.TailLink``, ``pd_plane_sweep_bwd_tail``); the tail's own backward kernel, which re-reads the [B,N,H,W]-sized
-    gradients the sweep has just written, no longer runs.  NOT detected: another differentiable consumer of ``outputs["sigma"]``
+    ``fuse_sweep_backward=True`` (mixture loss, one target view; xy planes, or xy + xz planes in the row form that
+    ``fused_plane_geometry`` puts into ``outputs``): the promise that ``outputs["logits"]`` / ``["sigma"]`` are consumed — as far
+    as gradients go — by the trainer's plane sweep alone.  The sweep's backward kernel then applies this tail's backward on the
+    values it holds anyway and writes the conv outputs' gradients directly (``ops.TailLink``; ``pd_plane_sweep_bwd_tail``, or
+    ``pd_plane_sweep_bwd_tail_rows`` for row-view disparities / a row-view mask — the views' strides decide, there is no switch);
+    the tail's own backward kernel, which re-reads the [B,N,H,W]-sized gradients the sweep has just written, no longer runs.  A
+    dense ``disp_layered`` or a per-pixel ``padding_mask`` (yz planes) takes no link: two kernels, the same results.  NOT detected: another differentiable consumer of ``outputs["sigma"]``
     (a regulariser) — its gradient would be added, in sigma space, to one already in conv-output space; keep the flag off then.
     With bf16 conv outputs (autocast) the flag is accepted and no link is made: the sweep's fused backward has no bf16 form, so
     the sweep's native bf16 backward and then this tail's run as two kernels, with the results of ``fuse_sweep_backward=False``."""

@@ -222,9 +222,10 @@ def _sweep_backward(saved, cfg, grads, need, into=None, accumulate=False):
 
 
 def _sweep_backward_tail(saved, cfg, grads, need, link):
-    """pd_plane_sweep_bwd_tail: the sweep's backward with the linked decoder tail's backward riding along.  Returns
-    (g_raw_logits, g_raw_sigma, g_plane) — handed to autograd as the gradients of logits / sigma; the tail's node passes them
-    through (TailLink)."""
+    """pd_plane_sweep_bwd_tail — or, with per-row disparities and / or a row mask, pd_plane_sweep_bwd_tail_rows: the sweep's
+    backward with the linked decoder tail's backward riding along.  Returns (g_raw_logits, g_raw_sigma, g_plane) — handed to
+    autograd as the gradients of logits / sigma; the tail's node passes them through (TailLink).  ``g_plane`` has the shape of
+    the disparities ([B,N] or [B,N,H]) and holds the warp's and the tail's share."""
     lib = C.load()
     s = SweepSaved(*saved)
     mode, flags, sign = cfg
@@ -239,12 +240,18 @@ def _sweep_backward_tail(saved, cfg, grads, need, link):
     ws = _workspace(lib, d, dev)
     g_rgb_rec, g_ph_map, gd, gz = map(_contig, (g_rgb_rec, g_ph_map, g_disp, g_depth))
     g_ph_mean = _scalar_grad(g_ph_mean)
+    tail_args = (C.ptr(s.rgb_rec), C.ptr(s.stash), C.ptr(g_rgb_rec), C.ptr(g_ph_map), C.ptr(g_ph_mean), C.ptr(link.raw_sigma),
+                 C.ptr(link.stash), C.ptr(link.disp), C.ptr(gd), C.ptr(gz), C.ptr(gl), C.ptr(gs), C.ptr(g_plane), C.ptr(ws),
+                 C.stream_handle(dev))
+    head = (ctypes.byref(d), C.ptr(s.src), C.ptr(s.tgt), C.ptr(s.logits), C.ptr(s.sigma), C.ptr(s.plane))
     with C.on_device(dev), _timed("bwd"):
-        rc = lib.pd_plane_sweep_bwd_tail(ctypes.byref(d), C.ptr(s.src), C.ptr(s.tgt), C.ptr(s.logits), C.ptr(s.sigma), C.ptr(s.plane),
-                                         C.ptr(s.rgb_rec), C.ptr(s.stash), C.ptr(g_rgb_rec), C.ptr(g_ph_map), C.ptr(g_ph_mean),
-                                         C.ptr(link.raw_sigma), C.ptr(link.stash), C.ptr(link.disp), C.ptr(gd), C.ptr(gz),
-                                         C.ptr(gl), C.ptr(gs), C.ptr(g_plane), C.ptr(ws), C.stream_handle(dev))
-    C.check(rc, "pd_plane_sweep_bwd_tail")
+        if flags & (C.PD_DISP_ROWS | C.PD_MASK_ROWS):   # (plane_sweep_disp checked: the sweep's row mask IS the tail's)
+            name = "pd_plane_sweep_bwd_tail_rows"
+            rc = lib.pd_plane_sweep_bwd_tail_rows(*head, C.ptr(s.padding_mask), *tail_args)
+        else:
+            name = "pd_plane_sweep_bwd_tail"
+            rc = lib.pd_plane_sweep_bwd_tail(*head, *tail_args)
+    C.check(rc, name)
     link.applied = {"disp": g_disp, "depth": g_depth}   # until the tail's node of this pass has consumed it
     link.fused_passes += 1
     return gl, gs, g_plane
@@ -253,17 +260,27 @@ def _sweep_backward_tail(saved, cfg, grads, need, link):
 class TailLink:
     """What ties a fused decoder tail (``decoder_tail(..., fuse_sweep_backward=True)``) to the ONE plane sweep that consumes
     its logits / sigma, so that the sweep's backward kernel can apply the tail's backward as well
-    (``pd_plane_sweep_bwd_tail``: the [B,N,H,W]-sized g_logits / g_sigma are never re-read by a tail kernel).
+    (``pd_plane_sweep_bwd_tail``, ``pd_plane_sweep_bwd_tail_rows`` for row-form disparities / mask: the [B,N,H,W]-sized
+    g_logits / g_sigma are never re-read by a tail kernel).
 
     Autograd runs the sweep's node before the tail's, and the tail's other upstream gradients (d loss / d disp from the
     smoothness term, d / d depth) reach the tail's node only — so ``pred_novel_images`` routes ``outputs["disp"]`` /
     ``["depth"]`` through gradient taps created AFTER the sweep's node: nodes created later run earlier, the taps have
     handed their gradients over by the time the sweep's backward runs.  The tail's own backward then passes g_logits /
     g_sigma through, and runs its kernel only on whatever upstream gradient of disp / depth the sweep did NOT see (none in
-    the trainer's graph; a consumer that took ``disp`` before the tap existed, for example) — correct in any order."""
+    the trainer's graph; a consumer that took ``disp`` before the tap existed, for example) — correct in any order.
 
-    def __init__(self, raw_sigma, stash, disp):
+    The fused kernel takes the tail's disparities and mask from the SWEEP's arguments, and the sweep's plane gradient carries the
+    tail's share.  For the row form ``plane_sweep_disp`` therefore fuses only when its [B,N,H] rows are the tail's memory
+    (``disp_rows`` / ``mask_rows``: the rows tensor behind ``plane_geometry``'s or ``row_view``'s views; a ``row_uniform`` dense
+    copy, an untagged stride-0 view or rows on one side only count as a consumer the fused form does not serve).  Per-plane
+    scalars are not compared — ``_per_plane_view`` may hand the two nodes different views of the decoder's [B,N,1,1] tensor: there
+    the flag's promise includes that the sweep is given the ``disp_layered`` the tail was given, as ``pred_novel_images`` does."""
+
+    def __init__(self, raw_sigma, stash, disp, mask_rows=None):
         self.raw_sigma, self.stash, self.disp = raw_sigma, stash, disp
+        self.mask_rows = mask_rows   # the tail's [B,N,H] padding mask (PD_TAIL_MASK_ROWS) or None: the sweep must have been given the same
+        self.disp_rows = None        # the tail's [B,N,H] disparities (PD_TAIL_DISP_ROWS) or None: likewise
         self.consumers = 0        # sweeps that registered as consumers of this tail's logits / sigma
         self.seen = {}            # "disp" / "depth" -> gradient handed over by its tap (taken by the sweep's backward of the pass)
         self.applied = None       # {"disp": g or None, "depth": g or None}: a sweep's backward has applied the tail's terms in THIS
@@ -607,6 +624,16 @@ def _row_kernels(B, N, H, W, impl):
     return bool(C.load().pd_sweep_uses_rowshift(ctypes.byref(C.SweepDesc(B, N, H, W, C.PD_WARP_DISP, 0, 1.0, impl))))
 
 
+def _same_mask_rows(rows, any_mask, tail_rows):
+    """Does the sweep apply the padding mask the linked tail applied?  Neither has one, or both read the same [B,N,H] memory
+    (``rows``: this call's row mask or None; ``any_mask``: it has a mask of some form; ``tail_rows``: TailLink.mask_rows).  Also
+    asked about the per-row disparities (``any_mask`` False, TailLink.disp_rows)."""
+    if rows is None or tail_rows is None:
+        return rows is None and tail_rows is None and not any_mask
+    return (rows.data_ptr() == tail_rows.data_ptr() and tuple(rows.shape) == tuple(tail_rows.shape)
+            and rows.stride() == tail_rows.stride() and rows.dtype == tail_rows.dtype)
+
+
 def _finish(call, defer, return_mean):
     """The end of plane_sweep_disp / plane_sweep_homography: the SweepCall itself (``defer``: for plane_sweep_multi, several
     target views as one autograd node) or its node's (rgb_rec, ph_map[, ph_map.mean() fused into the kernel])."""
@@ -690,11 +717,16 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
     call = SweepCall(src, tgt, logits, sigma if use_mixture_loss else None, plane, None, None, padding_mask,
                      dists if render_probability else None, C.PD_WARP_DISP, flags, sign)
     # a fused decoder tail that asked for it (decoder_tail(..., fuse_sweep_backward=True)) gets its backward applied by this
-    # sweep's backward kernel — where the library serves that form for this descriptor (mixture, one disparity per plane, ...:
-    # pd_sweep_bwd_tail_fuses) and the call has no padding mask and fp32 storage
+    # sweep's backward kernel — where the library serves that form for this descriptor (mixture, one disparity per plane or per
+    # row, ...: pd_sweep_bwd_tail_fuses, or pd_sweep_bwd_tail_rows_fuses for PD_DISP_ROWS / PD_MASK_ROWS), the call has fp32
+    # storage and its padding mask is the tail's: none, or the same [B,N,H] rows.  Anything else — a per-pixel mask here, a mask
+    # on one side only — is a consumer the fused form does not serve
     link = getattr(logits, "_pd_tail_link", None)
-    if (link is not None and not bf and padding_mask is None and getattr(sigma, "_pd_tail_link", None) is link
-            and lib.pd_sweep_bwd_tail_fuses(ctypes.byref(_desc(B, N, H, W, C.PD_WARP_DISP, flags, sign)))):
+    fuses = lib.pd_sweep_bwd_tail_rows_fuses if flags & (C.PD_DISP_ROWS | C.PD_MASK_ROWS) else lib.pd_sweep_bwd_tail_fuses
+    if (link is not None and not bf and getattr(sigma, "_pd_tail_link", None) is link
+            and _same_mask_rows(padding_mask if flags & C.PD_MASK_ROWS else None, padding_mask is not None, link.mask_rows)
+            and _same_mask_rows(plane if rows else None, False, link.disp_rows)
+            and fuses(ctypes.byref(_desc(B, N, H, W, C.PD_WARP_DISP, flags, sign)))):
         link.consumers += 1
         call = call._replace(link=link)
     elif link is not None:

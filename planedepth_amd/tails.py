@@ -66,6 +66,8 @@ class _DecoderTail(torch.autograd.Function):
         ctx.set_materialize_grads(False)   # an output nobody differentiates (depth, usually) arrives as None, not as a zero tensor
         if link is not None:
             link.raw_sigma, link.stash, link.disp = raw_sigma, stash, disp.detach()
+            link.mask_rows = padding_mask   # ([B,N,H], contiguous, or None: decoder_tail links no other mask form)
+            link.disp_rows = disp_layered if flags & C.PD_TAIL_DISP_ROWS else None
         if logits is None:       # no mask: the logits ARE the conv output (reference: logits * ones)
             logits = raw_logits.view_as(raw_logits)
         if sigma is None:
@@ -148,6 +150,10 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     ``probability`` stay fp32 and come from the unrounded fp32 sigma (the fp32 route on the widened inputs).  With bf16,
     ``fuse_sweep_backward`` takes no tail link: the sweep's bf16 backward and this tail's run as two kernels, with the results of
     ``fuse_sweep_backward=False``.
+
+    ``fuse_sweep_backward=True`` links this tail to the one plane sweep that consumes its logits / sigma (``TailLink``) for
+    per-plane scalars AND for the row form — row-view disparities and / or a row-view mask, the reference's default 49 xy + 14 xz
+    planes as ``plane_geometry`` returns them.  A dense map or a per-pixel mask gets no link (two kernels, the same results).
     """
     B, N, H, W = raw_logits.shape
     bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
@@ -173,7 +179,10 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     # the sweep already wrote in conv-output space, without the sigmoid' factor and the clamp gate.  (``logits`` are safe:
     # d logits / d raw_logits is the identity here.)  Leave the flag off for such a graph.
     # bf16 conv outputs: no link (the row-stream backward's tail form has no bf16 instantiation); two kernels, the same results.
-    link = TailLink(None, None, None) if (fuse_sweep_backward and use_mixture_loss and padding_mask is None and per_plane
+    # Forms that link: disparities per plane or as rows, no mask or a row mask (pd_plane_sweep_bwd_tail / _bwd_tail_rows); a dense
+    # map or a per-pixel mask does not.
+    link = TailLink(None, None, None) if (fuse_sweep_backward and use_mixture_loss and (per_plane or rows) and
+                                           (padding_mask is None or flags & C.PD_TAIL_MASK_ROWS)
                                            and not bf16 and torch.is_grad_enabled()) else None
     logits, sigma, disp, depth, stash = _DecoderTail.apply(raw_logits, raw_sigma if use_mixture_loss else None, plane,
                                                            padding_mask, flags, link)
