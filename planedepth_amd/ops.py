@@ -3,7 +3,7 @@ and ``bench.py`` use.  The operators live in ``sweep`` (the fused plane sweep: a
 ``tails`` (decoder / PladeNet tails), ``losses`` (SSIM, mixture NLL, masked photometric, smoothness, perceptual feature distance), ``postprocess``
 (self-distillation warps, batch doubling, crop grid), ``metrics`` (depth evaluation), ``geometry`` (backproject / project /
 homography grids, grid_sample) and ``_buffers`` (descriptors, pre-zeroed pools); the switches tests flip between calls (``ops.SWEEP_IMPL = ...``) are attributes
-of ``_state`` that this module forwards both ways.
+of ``_state`` that this module forwards both ways.  ``planeform``: the forms of ``disp_layered`` / ``padding_mask`` (per plane, rows, dense) they all read.
 
 Every function launches hand-written HIP kernels through ctypes on torch's current stream.  PyTorch is used for device
 memory, streams and autograd plumbing only; there is no eager / CPU implementation behind these ops.
@@ -16,10 +16,11 @@ from . import _state
 from ._buffers import (  # noqa: F401
     _timed, _desc, _contig, _ZERO_POOL, _zero_scalar, _ZERO_BLOCKS,
     _ZERO_BLOCK_FLOATS, _zero_block, _plane_grad_buffer)
+from .planeform import _per_plane_view, _FirstColumn, _row_view, _rows_of, _RowView, row_view  # noqa: F401
 from .sweep import (  # noqa: F401
     SweepCall, SweepSaved, _sweep_forward, _sweep_forward_pair, _sweep_backward_pair, _sweep_backward, _sweep_backward_tail,
     TailLink, _GradTap, tail_taps, _PlaneSweep, _SIDE_FIELDS, _PER_SIDE, _MultiPlaneSweep,
-    plane_sweep_multi, as_f32, _storage_route, _flags, _SIGN, _per_plane_view, _FirstColumn, _row_view, _rows_of, _RowView, row_view, plane_sweep_disp,
+    plane_sweep_multi, as_f32, _storage_route, _flags, _SIGN, plane_sweep_disp,
     homography_matrices, _HomographyMatrices, homography_matrices_fused, plane_sweep_homography, _stereo_rows_sweep, plane_sweep_layers)
 from .tails import (  # noqa: F401
     _PlaneLevels, plane_disparities, _PlaneGeometry, plane_geometry,

@@ -1,31 +1,21 @@
 """Forward-only operators around the batch: the self-distillation post-process (trainer.py:404-466), the batch doubling of
 add_flip_right_inputs (trainer.py:252-276), the dataset's crop grid (datasets/pair_transforms.py:27-56).
 """
-import ctypes
-import os
-
 from . import _capi as C
-from . import _state as S
-from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, _plane_grad_buffer
-from .sweep import _row_view
+from . import planeform as PF
+from ._buffers import torch, _contig
+
+_DISP_FLAG = {PF.PER_PLANE: 0, PF.ROWS: C.PD_PP_DISP_ROWS, PF.DENSE: C.PD_PP_DISP_DENSE}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Post-process warps — forward only, as in the reference (no_grad networks, detached result)
 # ---------------------------------------------------------------------------------------------------------------------
 def _pp_disp(disp_layered, B, N, H, W, row_uniform=False):
-    """(tensor, flags): per-plane [B,N] when the map is an H/W-expanded view; [B,N,H] + PD_PP_DISP_ROWS when it is constant
-    along x — an x-expanded view, or a dense map under the caller's ``row_uniform`` promise (xy and xz planes:
-    networks/depth_decoder.py:153-181; yz planes are not) —; else the dense [B,N,H,W] map.  A row view (``stride(3) == 0``:
-    ``ops.plane_geometry``'s map, or a batch slice of it) is read as rows without the promise; one of another shape raises
-    ``ValueError`` (``_row_view``)."""
-    if not _row_view(disp_layered, B, N, H, W) and tuple(disp_layered.shape) != (B, N, H, W):
-        disp_layered = disp_layered.expand(B, N, H, W)
-    if disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0:
-        return disp_layered[:, :, 0, 0].contiguous(), 0
-    if disp_layered.stride(3) == 0 or row_uniform:
-        return disp_layered[:, :, :, 0].contiguous(), C.PD_PP_DISP_ROWS
-    return disp_layered.contiguous(), C.PD_PP_DISP_DENSE
+    """(tensor, flags) of ``PF.disp_operand``: rows for a row view, under the ``row_uniform`` promise (xy and xz planes:
+    networks/depth_decoder.py:153-181; yz planes are not) and for a [B,N,H,1] map, which the expand over x makes a row view."""
+    form, disp = PF.disp_operand(disp_layered, B, N, H, W, promise=row_uniform or (disp_layered.shape[-1] == 1 and W > 1), grad=False)
+    return disp, _DISP_FLAG[form]
 
 
 def warp_softmax(planes, disp_layered, sign, flip_src=False, row_uniform=False):
@@ -157,5 +147,3 @@ def crop_grid(params, height, width):
         C.check(lib.pd_crop_grid(B, int(height), int(width), C.ptr(params), C.ptr(grid), C.stream_handle(params.device)),
                 "pd_crop_grid")
     return grid
-
-

@@ -10,7 +10,8 @@ from typing import NamedTuple
 
 from . import _capi as C
 from . import _state as S
-from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, _plane_grad_buffer
+from . import planeform as PF
+from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _plane_grad_buffer
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -518,103 +519,15 @@ def plane_sweep_multi(deferred):
     return [tuple(outs[3 * i:3 * i + 3]) for i in range(len(deferred))]
 
 
-def _flags(use_mixture_loss, automask, dense=False, render=False, rows=False):
+_DISP_FLAG = {PF.PER_PLANE: 0, PF.ROWS: C.PD_DISP_ROWS, PF.DENSE: C.PD_DISP_DENSE}
+
+
+def _flags(use_mixture_loss, automask, form=PF.PER_PLANE, render=False):
     return ((C.PD_MIXTURE if use_mixture_loss else 0) | (C.PD_AUTOMASK if automask else 0) |
-            (C.PD_DISP_DENSE if dense else 0) | (C.PD_RENDER_PROB if render else 0) | (C.PD_DISP_ROWS if rows else 0))
+            (C.PD_RENDER_PROB if render else 0) | _DISP_FLAG[form])
 
 
 _SIGN = {"r": 1.0, "l": -1.0}
-
-
-def _per_plane_view(disp_layered):
-    """[B,N] view of an H/W-expanded disparity tensor, taken from the tensor it was expanded FROM when possible.
-
-    ``disp_layered[:, :, 0, 0]`` would be correct but makes autograd materialise a zero [B,N,H,W] gradient and then
-    reduce it again (ExpandBackward): ~0.1 ms per step of pure overhead at 8x49x192x640.  When the view's base is the
-    decoder's [B,N,1,1] tensor (networks/depth_decoder.py:153-156) the gradient is handed to that tensor directly.
-    """
-    B, N = disp_layered.shape[:2]
-    base = disp_layered._base
-    if (base is not None and base.dim() == 4 and tuple(base.shape) == (B, N, 1, 1)
-            and base.storage_offset() == disp_layered.storage_offset()
-            and base.stride()[:2] == disp_layered.stride()[:2]
-            and base.requires_grad == disp_layered.requires_grad):
-        return base.reshape(B, N)
-    return disp_layered[:, :, 0, 0]
-
-
-class _FirstColumn(torch.autograd.Function):
-    """``dense[..., 0]`` of a [B,N,H,W] map that is constant along x by the caller's promise (``row_uniform``: xy and xz
-    planes, networks/depth_decoder.py:153-181) -> contiguous [B,N,H].
-
-    Backward: the row's gradient goes back as ``g / W`` on EVERY column, as an expanded (stride-0) view — whatever built
-    the map from x-independent quantities (the decoder's ``expand`` / its y-grid formula) sums over x and receives exactly
-    ``g``.  A plain ``dense[..., 0]`` hands autograd a SelectBackward that zero-fills a [B,N,H,W] tensor per step to carry one
-    column (248 MB at 8x63x192x640: 0.037 ms next to a 0.38 ms path) and makes that expand-backward read it all."""
-
-    @staticmethod
-    def forward(ctx, dense):
-        ctx.W = dense.shape[-1]
-        return dense[..., 0].contiguous()
-
-    @staticmethod
-    def backward(ctx, g):
-        return (g * (1.0 / ctx.W)).unsqueeze(-1).expand(*g.shape, ctx.W)
-
-
-def _row_view(t, B, N, H, W, name="disp_layered"):
-    """Is ``t`` a ROW VIEW: a [B,N,H,W] tensor with ``stride(3) == 0`` (and W > 1) that is not an H/W-expanded view of per-plane
-    scalars — what ``ops.plane_geometry`` returns for ``disp_layered`` / ``padding_mask``, or any tensor with those strides (a
-    batch slice ``view[:B]`` included).  Such a tensor IS constant along x, by construction: the row kernels take it with no
-    ``row_uniform`` promise and no check of the data.  A stride-0 view of another shape raises ``ValueError``."""
-    if not torch.is_tensor(t) or t.dim() != 4 or t.shape[3] <= 1 or t.stride(3) != 0 or (t.stride(2) == 0 and t.shape[2] > 1):
-        return False
-    if tuple(t.shape) != (B, N, H, W):
-        raise ValueError("%s is a row view (stride(3) == 0) of shape %s, expected %s" % (name, tuple(t.shape), (B, N, H, W)))
-    return True
-
-
-def _rows_of(view):
-    """The [B,N,H] rows of a row view (``_row_view``).  A view made by ``ops.plane_geometry`` carries the rows tensor it was
-    expanded from (``_pd_rows``): the consumer then hangs on that tensor's autograd node directly, and its gradient arrives
-    [B,N,H]-sized — nothing is spread over W and summed again, and several consumers add up in [B,N,H].  Any other row view
-    goes through ``_FirstColumn``: the row total comes back as ``g / W`` on every column, a stride-0 gradient."""
-    rows = getattr(view, "_pd_rows", None)
-    if (rows is not None and rows.data_ptr() == view.data_ptr() and tuple(rows.shape) == tuple(view.shape[:3])
-            and rows.stride() == view.stride()[:3]):
-        return rows
-    if view.requires_grad and torch.is_grad_enabled():
-        return _FirstColumn.apply(view)
-    return view.detach()[..., 0]
-
-
-class _RowView(torch.autograd.Function):
-    """rows [B,N,H] -> the [B,N,H,W] view with ``stride(3) == 0`` (the reference's shape of ``outputs["disp_layered"]``, nothing
-    [B,N,H,W]-sized behind it).  Backward: a gradient that is itself constant along x (``stride(3) == 0``: ``_FirstColumn``'s
-    ``g / W`` on every column) gives ``W * g[..., 0]`` without touching W times as many elements; any other gradient — a foreign
-    torch consumer of the view — is summed over x.  The package's own row consumers do not come through here at all
-    (``_rows_of``)."""
-
-    @staticmethod
-    def forward(ctx, rows, W):
-        ctx.W = int(W)
-        ctx.set_materialize_grads(False)
-        return rows.unsqueeze(-1).expand(*rows.shape, int(W))
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return None, None
-        if ctx.W > 1 and g.stride(-1) == 0:
-            return g[..., 0] * float(ctx.W), None
-        return g.sum(-1), None
-
-
-def row_view(rows, W):
-    """``_RowView`` + the ``_pd_rows`` tag ``_rows_of`` reads."""
-    view = _RowView.apply(rows, W) if rows.requires_grad else rows.unsqueeze(-1).expand(*rows.shape, int(W))
-    view._pd_rows = rows
-    return view
 
 
 @functools.lru_cache(maxsize=None)
@@ -668,46 +581,25 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
     B, N, H, W = logits.shape
     lib = C.load()
     sign = _SIGN.get(target_side, 0.0)  # any other key leaves the grid untouched (trainer.py:546-549)
+    row_kernels = _row_kernels(B, N, H, W, S.SWEEP_IMPL)
     if _rows is not None:
         # internal (the stereo view of homography_warp): per-row shifts [B,N,H] and per-row mask [B,N,H] as they are — no
         # [B,N,H,W] view whose slice-backward would zero-fill and reduce 190 MB per step
-        if _row_kernels(B, N, H, W, S.SWEEP_IMPL):
+        if row_kernels:
             shift, mask = _rows
-            flags = _flags(use_mixture_loss, automask, rows=True, render=render_probability) | C.PD_MASK_ROWS
+            flags = _flags(use_mixture_loss, automask, PF.ROWS, render_probability) | C.PD_MASK_ROWS
             logits, sigma, bf = _storage_route(logits, sigma, use_mixture_loss, _desc(B, N, H, W, C.PD_WARP_DISP, flags, sign))
             return _finish(SweepCall(src, tgt, logits, sigma if use_mixture_loss else None, shift, None, None, mask,
                                      dists if render_probability else None, C.PD_WARP_DISP, flags | bf, sign), defer, return_mean)
         disp_layered, padding_mask = (t[..., None].expand(B, N, H, W) for t in _rows)   # PD_IMPL_GENERAL & co.
-    view = _row_view(disp_layered, B, N, H, W)   # constant along x by its strides: no promise needed, no data check
-    if not view and tuple(disp_layered.shape) != (B, N, H, W):
-        disp_layered = disp_layered.expand(B, N, H, W)
-    per_plane = not view and disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
-    rows = False
-    if per_plane:
-        plane = _per_plane_view(disp_layered)
-    elif view or row_uniform:
-        rows = _row_kernels(B, N, H, W, S.SWEEP_IMPL)
-        if rows and view:
-            plane = _rows_of(disp_layered)
-        elif rows:   # a LEAF map keeps the exact select gradient (g on column 0, zeros elsewhere); see the docstring
-            plane = disp_layered[..., 0].contiguous() if disp_layered.is_leaf else _FirstColumn.apply(disp_layered)
-        else:
-            plane = disp_layered
-    else:
-        plane = disp_layered
-    mask_view = padding_mask is not None and _row_view(padding_mask, B, N, H, W, "padding_mask")
-    if padding_mask is not None and not mask_view:
-        if padding_mask.dtype != torch.float32:
-            padding_mask = padding_mask.float()
-        if tuple(padding_mask.shape) != (B, N, H, W):
-            padding_mask = padding_mask.expand(B, N, H, W)
-    flags = _flags(use_mixture_loss, automask, dense=not (per_plane or rows), render=render_probability, rows=rows)
-    if padding_mask is not None and (row_uniform or mask_view) and (per_plane or rows) and _row_kernels(B, N, H, W, S.SWEEP_IMPL):
+    # rows: a row view (constant along x by its strides: no promise, no data check) or row_uniform, where the row kernels serve
+    form, plane = PF.disp_operand(disp_layered, B, N, H, W, rows=row_kernels, promise=row_uniform)
+    flags = _flags(use_mixture_loss, automask, form, render_probability)
+    if padding_mask is not None:
         # the mask of xy / xz planes is constant along x as well (depth_decoder.py:157, 166): hand over its first column
-        padding_mask = padding_mask.detach()[..., 0] if mask_view else padding_mask[..., 0]
-        flags |= C.PD_MASK_ROWS
-    if padding_mask is not None and padding_mask.dtype != torch.float32:
-        padding_mask = padding_mask.float()
+        mask_form, padding_mask = PF.mask_operand(padding_mask, B, N, H, W, rows=form != PF.DENSE and row_kernels,
+                                                  promise=row_uniform)
+        flags |= C.PD_MASK_ROWS if mask_form == PF.ROWS else 0
     # bf16 logits / sigma: native where the library serves the descriptor; a per-pixel mask is a fact of the call that no
     # descriptor shows, and PD_LOGITS_BF16 is refused with one — fp32 copies there and everywhere else
     per_pixel_mask = padding_mask is not None and not flags & C.PD_MASK_ROWS
@@ -725,7 +617,7 @@ def plane_sweep_disp(src, tgt, logits, sigma, disp_layered, padding_mask=None, *
     fuses = lib.pd_sweep_bwd_tail_rows_fuses if flags & (C.PD_DISP_ROWS | C.PD_MASK_ROWS) else lib.pd_sweep_bwd_tail_fuses
     if (link is not None and not bf and getattr(sigma, "_pd_tail_link", None) is link
             and _same_mask_rows(padding_mask if flags & C.PD_MASK_ROWS else None, padding_mask is not None, link.mask_rows)
-            and _same_mask_rows(plane if rows else None, False, link.disp_rows)
+            and _same_mask_rows(plane if form == PF.ROWS else None, False, link.disp_rows)
             and fuses(ctypes.byref(_desc(B, N, H, W, C.PD_WARP_DISP, flags, sign)))):
         link.consumers += 1
         call = call._replace(link=link)
@@ -818,8 +710,6 @@ def homography_matrices_fused(distance, norm, T, K, inv_K, mode=C.PD_HMAT_PLANES
     return _HomographyMatrices.apply(distance, norm, T, K, inv_K, int(mode), int(rows))
 
 
-
-
 def plane_sweep_homography(src, tgt, logits, sigma, distance, norm, T, K, inv_K, *, use_mixture_loss=True,
                            automask=False, render_probability=False, dists=None, return_mean=False, plane_uniform=False,
                            stereo_rows=False, defer=False):
@@ -905,15 +795,12 @@ def plane_sweep_layers(src, logits, sigma, *, disp_layered=None, padding_mask=No
     with torch.no_grad():
         logits, sigma, _ = _storage_route(logits, sigma, use_mixture_loss, None)   # (the layers kernel reads fp32 only)
         if homography is None:
-            if tuple(disp_layered.shape) != (B, N, H, W):
-                disp_layered = disp_layered.expand(B, N, H, W)
-            per_plane = disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
-            plane = (disp_layered[:, :, 0, 0] if per_plane else disp_layered).contiguous()  # layers: general kernels
+            form, plane = PF.disp_operand(disp_layered, B, N, H, W, grad=False, row_views=False)   # layers: general kernels
             aux = k3 = None
             mode, sign = C.PD_WARP_DISP, _SIGN.get(target_side, 0.0)
-            flags = _flags(use_mixture_loss, False, dense=not per_plane, render=render_probability)
+            flags = _flags(use_mixture_loss, False, form, render_probability)
             if padding_mask is not None:
-                padding_mask = padding_mask.float().expand(B, N, H, W).contiguous()
+                padding_mask = PF.mask_operand(padding_mask, B, N, H, W, row_views=False)[1].contiguous()
         else:
             plane, aux, k3 = (t.contiguous() for t in homography)
             mode, sign, padding_mask = C.PD_WARP_HOMOGRAPHY, 0.0, None
@@ -937,5 +824,3 @@ def plane_sweep_layers(src, logits, sigma, *, disp_layered=None, padding_mask=No
                                            C.ptr(out.get("pi_rec")), C.stream_handle(dev))
         C.check(rc, "pd_plane_sweep_layers")
     return out
-
-

@@ -1,13 +1,14 @@
 """Network tails: DepthDecoder's (networks/depth_decoder.py:258-291) and PladeNet's compositing tail
 (networks/plade_net.py:309-341).
 """
-import ctypes
 import os
 
 from . import _capi as C
-from . import _state as S
-from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, _plane_grad_buffer
-from .sweep import TailLink, _per_plane_view, _row_view, _rows_of, row_view
+from . import planeform as PF
+from ._buffers import torch, _timed, _contig
+from .sweep import TailLink
+
+_DISP_FLAG = {PF.PER_PLANE: 0, PF.ROWS: C.PD_TAIL_DISP_ROWS, PF.DENSE: C.PD_TAIL_DISP_DENSE}
 
 
 def _storage_flag(raw_logits, raw_sigma, mix):
@@ -157,21 +158,11 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     """
     B, N, H, W = raw_logits.shape
     bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
-    rows = _row_view(disp_layered, B, N, H, W)
-    if not rows and tuple(disp_layered.shape) != (B, N, H, W):
-        disp_layered = disp_layered.expand(B, N, H, W)
-    per_plane = not rows and disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
-    plane = _rows_of(disp_layered) if rows else _per_plane_view(disp_layered) if per_plane else disp_layered
-    flags = ((C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | bf16 |
-             (C.PD_TAIL_DISP_ROWS if rows else 0 if per_plane else C.PD_TAIL_DISP_DENSE))
+    form, plane = PF.disp_operand(disp_layered, B, N, H, W)   # (rows from the strides only: this tail takes no promise)
+    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | bf16 | _DISP_FLAG[form]
     if padding_mask is not None:
-        if _row_view(padding_mask, B, N, H, W, "padding_mask"):
-            padding_mask = padding_mask.detach()[..., 0]
-            flags |= C.PD_TAIL_MASK_ROWS
-        if padding_mask.dtype != torch.float32:
-            padding_mask = padding_mask.float()
-        if not flags & C.PD_TAIL_MASK_ROWS and tuple(padding_mask.shape) != (B, N, H, W):
-            padding_mask = padding_mask.expand(B, N, H, W)
+        mask_form, padding_mask = PF.mask_operand(padding_mask, B, N, H, W)
+        flags |= C.PD_TAIL_MASK_ROWS if mask_form == PF.ROWS else 0
     # fuse_sweep_backward: the caller's promise that logits / sigma feed (with gradient) exactly ONE plane sweep — the trainer's
     # single-view pred_novel_images — whose backward kernel then applies this tail's backward too (TailLink).  Sweeps are
     # counted (a second one, or one the fused form does not serve, switches the fusion off); any OTHER differentiable consumer
@@ -181,7 +172,7 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     # bf16 conv outputs: no link (the row-stream backward's tail form has no bf16 instantiation); two kernels, the same results.
     # Forms that link: disparities per plane or as rows, no mask or a row mask (pd_plane_sweep_bwd_tail / _bwd_tail_rows); a dense
     # map or a per-pixel mask does not.
-    link = TailLink(None, None, None) if (fuse_sweep_backward and use_mixture_loss and (per_plane or rows) and
+    link = TailLink(None, None, None) if (fuse_sweep_backward and use_mixture_loss and form != PF.DENSE and
                                            (padding_mask is None or flags & C.PD_TAIL_MASK_ROWS)
                                            and not bf16 and torch.is_grad_enabled()) else None
     logits, sigma, disp, depth, stash = _DecoderTail.apply(raw_logits, raw_sigma if use_mixture_loss else None, plane,
@@ -300,11 +291,8 @@ def plade_tail(raw_logits, raw_sigma, disp_layered, ray_norm=None, use_mixture_l
     B, Nm1, H, W = raw_logits.shape
     N = Nm1 + 1
     bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
-    if tuple(disp_layered.shape) != (B, N, H, W):
-        disp_layered = disp_layered.expand(B, N, H, W)
-    per_plane = disp_layered.stride(2) == 0 and disp_layered.stride(3) == 0
-    plane = _per_plane_view(disp_layered) if per_plane else disp_layered
-    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | (0 if per_plane else C.PD_TAIL_DISP_DENSE) | bf16
+    form, plane = PF.disp_operand(disp_layered, B, N, H, W, row_views=False)
+    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | _DISP_FLAG[form] | bf16
     if ray_norm is None:
         ray_norm = camera_ray_norm(H, W, raw_logits.device)
     logits, dists, sigma, disp, depth, stash = _PladeTail.apply(raw_logits, raw_sigma if use_mixture_loss else None, plane,
@@ -363,7 +351,6 @@ def plane_disparities(levels, disp_min, disp_max, width, no_levels=None):
     disp, distance = _PlaneLevels.apply(levels.reshape(B, N), N if no_levels is None else no_levels, disp_min, disp_max,
                                         0.1 * 0.58 * width)
     return disp.reshape(B, N, 1, 1), distance
-
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -445,4 +432,4 @@ def plane_geometry(grid, residual, *, no_levels, xz_levels, disp_min, disp_max, 
                          "rotated grid must keep the reference's dense geometry)")
     cfg = (no_levels, xz_levels, float(disp_min), float(disp_max), float(xz_min), float(xz_max))
     disp_rows, mask_rows, distance, norm = _PlaneGeometry.apply(grid, residual, cfg)
-    return row_view(disp_rows, W), row_view(mask_rows, W), distance, norm
+    return PF.row_view(disp_rows, W), PF.row_view(mask_rows, W), distance, norm

@@ -51,6 +51,31 @@ def _color_name(opt):
     return "color_aug" if getattr(opt, "match_aug", False) else "color"
 
 
+def _contract_check(self, attr):
+    """Verify the options' promises on the data now?  opt.pd_check_contract (True / False) or PD_CHECK_CONTRACT; else until ``attr`` is set."""
+    check = getattr(self.opt, "pd_check_contract", None)
+    if os.environ.get("PD_CHECK_CONTRACT"):
+        check = True
+    if check is None:
+        check = not getattr(self, attr, False)
+    return check
+
+
+def _contract_checked(self, attr):
+    try:
+        setattr(self, attr, True)
+    except AttributeError:
+        pass
+
+
+def _require_constant_along_x(t, message):
+    """``ValueError(message)`` unless the map ``t`` is constant along x: a row view (``stride(3) == 0``, ``ops.plane_geometry``'s)
+    is by construction, and takes the row routes with or without the promise; anything else is compared with its first column."""
+    if (t is not None and t.dim() == 4 and t.shape[-1] > 1 and t.stride(3) != 0
+            and not bool((t == t[..., :1]).all())):
+        raise ValueError(message)
+
+
 def pred_novel_images(self, inputs, outputs):
     """Generate the warped (reprojected) colour images for a minibatch (reference trainer.py:523-603).
 
@@ -78,31 +103,19 @@ def pred_novel_images(self, inputs, outputs):
     # pose source whose outputs disagree with opt would get silently wrong warps.  They are therefore verified on the
     # data ONCE per trainer object — on its first call (a few reductions and one host sync), the verdict cached on the
     # object; opt.pd_check_contract = True (or PD_CHECK_CONTRACT=1) checks every call, = False never.
-    check = getattr(opt, "pd_check_contract", None)
-    if os.environ.get("PD_CHECK_CONTRACT"):
-        check = True
-    if check is None:
-        check = not getattr(self, "_pd_contract_checked", False)
+    check = _contract_check(self, "_pd_contract_checked")
     if check:
         pm, dl = outputs.get("padding_mask"), outputs.get("disp_layered")   # (homography_warp does not read disp_layered)
         if padding_mask is None and pm is not None and not bool((pm == 1).all()):
             raise ValueError("opt.xz_levels == opt.yz_levels == 0 promises an all-ones padding_mask, but it has zeros")
-        # (a row view — stride(3) == 0, ops.plane_geometry's — is constant along x by construction: nothing to check, and the
-        # sweep takes its row route from the strides, with or without the promise)
-        if (row_uniform and dl is not None and dl.dim() == 4 and dl.shape[-1] > 1 and dl.stride(3) != 0
-                and not bool((dl == dl[..., :1]).all())):
-            raise ValueError("opt.yz_levels == 0 promises disparities that are constant along x, but disp_layered is not")
-        if (row_uniform and pm is not None and pm.dim() == 4 and pm.shape[-1] > 1 and pm.stride(3) != 0
-                and not bool((pm == pm[..., :1]).all())):
-            raise ValueError("opt.yz_levels == 0 promises a padding_mask that is constant along x, but it is not")
+        if row_uniform:
+            _require_constant_along_x(dl, "opt.yz_levels == 0 promises disparities that are constant along x, but disp_layered is not")
+            _require_constant_along_x(pm, "opt.yz_levels == 0 promises a padding_mask that is constant along x, but it is not")
     # Several target views (trainer.py:532; mono training: ["r", -1, 1]) sweep the same logits / sigma: they are issued as
     # ONE autograd node whose backward kernels add their gradients in place (ops._MultiPlaneSweep) instead of one node
     # per view with [B,N,H,W]-sized adds in between.  opt.pd_fuse_sides = False keeps one node per view.
     fuse_sides = len(self.target_sides) > 1 and getattr(opt, "pd_fuse_sides", True)
-    try:
-        self._pd_contract_checked = True     # (set before the per-view checks run: a failing check raises anyway)
-    except AttributeError:
-        pass
+    _contract_checked(self, "_pd_contract_checked")   # (set before the per-view checks run: a failing check raises anyway)
     calls, handles = [], []
     logits = outputs["logits"]
     if len(self.target_sides) > 1:   # bf16 (autocast) logits / sigma: ONE fp32 copy for every view, whose gradients then add
@@ -271,18 +284,9 @@ def generate_post_process_disp(self, inputs):
     # from the options and verified on the data once per trainer object, as pred_novel_images does (opt.pd_check_contract)
     dl = outputs["disp_layered"]
     row_uniform = getattr(opt, "yz_levels", None) == 0
-    check = getattr(opt, "pd_check_contract", None)
-    if os.environ.get("PD_CHECK_CONTRACT"):
-        check = True
-    if check is None:
-        check = not getattr(self, "_pd_pp_contract_checked", False)
-    if (check and row_uniform and dl.dim() == 4 and dl.shape[-1] > 1 and dl.stride(3) != 0   # (a row view needs no check)
-            and not bool((dl == dl[..., :1]).all())):
-        raise ValueError("opt.yz_levels == 0 promises disparities that are constant along x, but disp_layered is not")
-    try:
-        self._pd_pp_contract_checked = True
-    except AttributeError:
-        pass
+    if row_uniform and _contract_check(self, "_pd_pp_contract_checked"):
+        _require_constant_along_x(dl, "opt.yz_levels == 0 promises disparities that are constant along x, but disp_layered is not")
+    _contract_checked(self, "_pd_pp_contract_checked")
     disp_pp, mask_novel = ops.post_process_disp(outputs["logits"], outputs["probability"], outputs["disp"], dl,
                                                 row_uniform=row_uniform)
     return disp_pp.detach(), mask_novel.detach()
