@@ -236,7 +236,8 @@ def _sweep_backward_tail(saved, cfg, grads, need, link):
     _, _, need_plane, _ = need
     g_plane, plane_flag = _plane_grad_buffer(s.plane, B, N, H, W, mode, flags, sign) if need_plane else (None, 0)
     d = _desc(B, N, H, W, mode, flags | plane_flag, sign)
-    g_disp, g_depth = link.seen.pop("disp", None), link.seen.pop("depth", None)   # (taken: state of THIS backward pass only)
+    link.enter_pass()
+    g_disp, g_depth = link.seen.pop("disp", None), link.seen.pop("depth", None)   # (what the taps of THIS backward pass left)
     gl, gs = torch.empty_like(s.logits), torch.empty_like(s.sigma)
     ws = _workspace(lib, d, dev)
     g_rgb_rec, g_ph_map, gd, gz = map(_contig, (g_rgb_rec, g_ph_map, g_disp, g_depth))
@@ -276,18 +277,51 @@ class TailLink:
     (``disp_rows`` / ``mask_rows``: the rows tensor behind ``plane_geometry``'s or ``row_view``'s views; a ``row_uniform`` dense
     copy, an untagged stride-0 view or rows on one side only count as a consumer the fused form does not serve).  Per-plane
     scalars are not compared — ``_per_plane_view`` may hand the two nodes different views of the decoder's [B,N,1,1] tensor: there
-    the flag's promise includes that the sweep is given the ``disp_layered`` the tail was given, as ``pred_novel_images`` does."""
+    the flag's promise includes that the sweep is given the ``disp_layered`` the tail was given, as ``pred_novel_images`` does.
+
+    Per-pass state.  ``seen`` and ``applied`` belong to ONE backward pass — the autograd engine's graph task, ``pass_id`` — and a
+    pass need not run all three of tap, sweep and tail (``torch.autograd.grad`` over a part of a retained graph).  Every backward
+    that touches the link calls ``enter_pass`` first: state of another pass is dropped, and a callback at the end of the pass
+    (the engine's ``queue_callback``) clears what this one leaves, so nothing a pass wrote is ever read by a later one.
+
+    The refused pass.  ``torch.autograd.grad(loss, [logits, sigma])`` makes the engine run the sweep's backward and only CAPTURE
+    at the tail's node: the caller would receive the conv outputs' gradients (sigmoid', the clamp gate, the mask and the disparity
+    share applied) as d loss / d logits, d loss / d sigma.  The sweep cannot tell such a pass from one that runs the tail's node,
+    and the fused kernel has no output-space gradients to return, so the choice made here is to REFUSE: the end-of-pass callback
+    finds ``applied`` never consumed and raises ``PlaneDepthHipError`` naming ``fuse_sweep_backward``; the link is clean afterwards and
+    the graph stays usable.  Build the graph with ``fuse_sweep_backward=False`` for such a pass."""
 
     def __init__(self, raw_sigma, stash, disp, mask_rows=None):
         self.raw_sigma, self.stash, self.disp = raw_sigma, stash, disp
         self.mask_rows = mask_rows   # the tail's [B,N,H] padding mask (PD_TAIL_MASK_ROWS) or None: the sweep must have been given the same
         self.disp_rows = None        # the tail's [B,N,H] disparities (PD_TAIL_DISP_ROWS) or None: likewise
         self.consumers = 0        # sweeps that registered as consumers of this tail's logits / sigma
+        self.pass_id = None       # the backward pass (torch._C._current_graph_task_id()) that ``seen`` / ``applied`` belong to
         self.seen = {}            # "disp" / "depth" -> gradient handed over by its tap (taken by the sweep's backward of the pass)
         self.applied = None       # {"disp": g or None, "depth": g or None}: a sweep's backward has applied the tail's terms in THIS
-                                  # backward pass; the tail's node consumes it and resets it — a second pass over a retained graph
-                                  # (retain_graph=True, a second torch.autograd.grad) starts clean
+                                  # backward pass; the tail's node consumes it and resets it
         self.fused_passes = 0     # backward passes in which the sweep's kernel applied the tail's backward (diagnostics / tests)
+
+    def enter_pass(self):
+        """First thing in every backward that reads or writes ``seen`` / ``applied`` (tap, sweep, tail)."""
+        pass_id = torch._C._current_graph_task_id()   # (-1 outside the engine: no end of a pass to book)
+        if pass_id != self.pass_id:
+            self.pass_id, self.applied = pass_id, None
+            self.seen.clear()
+            if pass_id >= 0:
+                torch.autograd.Variable._execution_engine.queue_callback(lambda: self._end_pass(pass_id))
+
+    def _end_pass(self, pass_id):
+        if pass_id != self.pass_id:
+            return
+        applied, self.applied, self.pass_id = self.applied, None, None
+        self.seen.clear()
+        if applied is not None:   # the sweep applied the tail's backward and the tail's node never ran: see "The refused pass"
+            raise C.PlaneDepthHipError(
+                "fuse_sweep_backward: this backward pass ran the plane sweep's fused backward but not the decoder tail's node "
+                "(torch.autograd.grad with logits / sigma as inputs?), so the gradients it holds at logits / sigma are those of the "
+                "decoder's conv outputs, not d / d logits and d / d sigma.  Build the graph with fuse_sweep_backward=False for such "
+                "a pass.")
 
 
 class _GradTap(torch.autograd.Function):
@@ -300,6 +334,7 @@ class _GradTap(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        ctx.link.enter_pass()
         ctx.link.seen[ctx.which] = g
         return g, None, None
 

@@ -90,7 +90,8 @@ class _DecoderTail(torch.autograd.Function):
         extra = None
         applied = None
         if link is not None:
-            applied, link.applied = link.applied, None   # per-pass state: consumed here (a second backward over the graph)
+            link.enter_pass()                            # (a note of another backward pass is not this pass's: TailLink)
+            applied, link.applied = link.applied, None   # per-pass state: consumed here
             link.seen.clear()
         if applied is not None:
             # the sweep's backward kernel applied this node's backward already (pd_plane_sweep_bwd_tail): g_logits / g_sigma ARE
