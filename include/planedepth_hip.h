@@ -397,6 +397,33 @@ int pd_plade_tail_bwd(int B, int N, int H, int W, int flags, const float* raw_lo
                       pd_stream_t stream);
 
 /*
+ * Inference tails: the two tails above, forward only, for a caller that wants a depth map and not a training step
+ * (evaluate_depth_HR.py:144-168 reads outputs["disp"] and outputs["probability"].amax(1) only).  One pass over the planes;
+ * nothing [B,N,H,W]-sized is written (no logits, sigma or dists).
+ * Inputs, flags, refusals, alignment rules and the choice between 4 pixels and 1 pixel per lane are those of
+ * pd_decoder_tail_fwd (all five PD_TAIL_* flags, row forms included) and pd_plade_tail_fwd (PD_TAIL_MIXTURE,
+ * PD_TAIL_DISP_DENSE, PD_TAIL_BF16; a row flag is refused, N >= 2).  The output pointers listed below count for the alignment
+ * rule like the fp32 ones of fwd (16 bytes each for 4 pixels per lane); under PD_TAIL_BF16 only raw_logits / raw_sigma are bf16.
+ * Outputs, all [B,1,H,W] unless said otherwise; `disp` is required, every other one may be NULL and is skipped then:
+ *   disp, depth   bit-identical to what the matching fwd writes for the same inputs and flags
+ *   confidence    fp32, max_n probability_n: with the mixture the weights (pi / sigma * mask) / sum_N of depth_decoder.py:282-285
+ *                 (pi / sigma / sum_N for PladeNet), without it pi.  A masked plane keeps logit 0 in the softmax, as in the
+ *                 reference.  Within rounding of pd_*_tail_layers' probability, not bit-identical for the decoder tail (the best
+ *                 weight is carried through the online softmax and rescaled when its reference moves).
+ *   plane_index   int32, the plane that attains that maximum; the lowest index among equal maxima (the comparison is strict)
+ *   disp_best     fp32, disp_layered at plane_index
+ *   stash         [B,2,H,W] (decoder) / [B,1,H,W] (PladeNet), bit-identical to fwd's: pd_*_tail_layers serve pi / probability
+ *                 from it on demand
+ * Forward only: there is no backward for these entries; a differentiable caller uses pd_*_tail_fwd / _bwd.
+ */
+int pd_decoder_tail_infer(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
+                          const float* padding_mask, const float* disp_layered, float* disp, float* depth, float* confidence,
+                          int* plane_index, float* disp_best, float* stash, pd_stream_t stream);
+int pd_plade_tail_infer(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
+                        const float* disp_layered, const float* ray_norm, float* disp, float* depth, float* confidence,
+                        int* plane_index, float* disp_best, float* stash, pd_stream_t stream);
+
+/*
  * get_smooth_loss_disp (layers.py:243-256; trainer.py:768):
  *   out[0] = mean_x |d(x)-d(x+1)| exp(-gamma mean_c|I(x)-I(x+1)|) + the same along y.
  * disp [B,1,H,W], img [B,C,H,W]; both may be crops of wider tensors: unit column stride, the other strides (in floats)

@@ -4,6 +4,7 @@ Importing the package does not need a GPU or the built library; calling any oper
 """
 from . import decoder_tail, layers, metrics, ops, synthetic, trainer_path  # noqa: F401
 from .decoder_tail import fused_decoder_tail  # noqa: F401
+from .predict import predict  # noqa: F401
 from .layers import (SSIM, BackprojectDepth, HomographyWarp, Project3D, disp_to_depth,  # noqa: F401
                      get_smooth_loss_disp, multimodal_loss)
 from .trainer_path import (add_flip_right_inputs, compute_depth_losses, compute_losses, compute_reprojection_loss,  # noqa: F401

@@ -15,23 +15,9 @@
 // PD_TAIL_BF16: raw_logits / raw_sigma, logits / sigma and their gradients hold bf16 (storage type ST = Bf16; the rule of
 // pd_decoder_tail.hip: exact widening, the fp32 arithmetic in the same order, one rounding per bf16 output element); dists and
 // its gradient, the disparities and the per-pixel maps stay fp32.
-#include "pd_tail_common.h"
+#include "pd_plade_tail.h"
 
 namespace pd {
-
-struct PladeArgs {
-  int N, HW, W;
-  int mix, dense;
-  const float* raw_logits;   // [B,N-1,H,W]
-  const float* raw_sigma;    // [B,N,H,W]
-  const float* dl;           // [B,N] or [B,N,H,W]
-  const float* ray;          // [H*W]
-};
-
-template <int PX>
-__device__ __forceinline__ Px<PX> plade_disp(const PladeArgs& a, int b, int n, long pix) {
-  return a.dense ? ldv<PX>(a.dl + ((long)b * a.N + n) * a.HW + pix) : splat<PX>(a.dl[b * a.N + n]);
-}
 
 template <class ST, bool MIX, int PX>
 __global__ __launch_bounds__(kBlock) void plade_fwd_kernel(PladeArgs a, float* __restrict__ logits, float* __restrict__ dists,
@@ -235,39 +221,6 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
     for (int i = threadIdx.x; i < N; i += kBlock) dst[i] = red[i];
   }
 }
-
-static int plade_validate(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
-                          const float* dl, const float* ray) {
-  PD_REQUIRE(B > 0 && B <= 65535 && N >= 2 && H > 0 && W > 0, "bad shape (alpha compositing needs N >= 2 planes)");
-  PD_REQUIRE((long)H * W < (1L << 31), "image too large");
-  PD_REQUIRE((flags & ~(PD_TAIL_MIXTURE | PD_TAIL_DISP_DENSE | PD_TAIL_BF16)) == 0, "unknown flags");
-  PD_REQUIRE(raw_logits && dl && ray, "NULL pointer");
-  PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || raw_sigma, "mixture needs raw_sigma");
-  return 0;
-}
-
-static PladeArgs plade_args(int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma, const float* dl,
-                            const float* ray) {
-  PladeArgs a;
-  a.N = N; a.HW = H * W; a.W = W;
-  a.mix = (flags & PD_TAIL_MIXTURE) != 0;
-  a.dense = (flags & PD_TAIL_DISP_DENSE) != 0;
-  a.raw_logits = raw_logits; a.raw_sigma = raw_sigma; a.dl = dl; a.ray = ray;
-  return a;
-}
-
-#define PD_PLADE_DISPATCH_T(KERNEL, T, px, mix, grid, shmem, stream, ...)                                   \
-  do {                                                                                                       \
-    if ((px) == 4) { if (mix) KERNEL<T, true, 4><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);              \
-                     else     KERNEL<T, false, 4><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__); }           \
-    else           { if (mix) KERNEL<T, true, 1><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__);              \
-                     else     KERNEL<T, false, 1><<<grid, kBlock, shmem, stream>>>(__VA_ARGS__); }           \
-  } while (0)
-#define PD_PLADE_DISPATCH(KERNEL, bf16, px, mix, grid, shmem, stream, ...)                                  \
-  do {                                                                                                       \
-    if (bf16) PD_PLADE_DISPATCH_T(KERNEL, Bf16, px, mix, grid, shmem, stream, __VA_ARGS__);                  \
-    else      PD_PLADE_DISPATCH_T(KERNEL, float, px, mix, grid, shmem, stream, __VA_ARGS__);                 \
-  } while (0)
 
 }  // namespace pd
 

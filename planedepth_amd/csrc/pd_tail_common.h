@@ -65,7 +65,7 @@ __device__ __forceinline__ Px<PX> splat(float x) {
 // 4 pixels per thread when every row of 4 is whole and aligned to its access in every tensor involved: `ptrs` hold fp32 (16
 // bytes), `storage` the tensors that PD_TAIL_BF16 turns into bf16 (8 bytes then, 16 without the flag).  The decoder tail's row
 // forms ([B,N,H] operands, read as scalars and not listed here) additionally ask for W % 4 == 0, so that the 4 pixels share a
-// row (pd_decoder_tail.hip: tail_px_rows).
+// row (pd_decoder_tail.h: tail_px_rows).
 static inline int tail_px(int H, int W, std::initializer_list<const void*> ptrs, std::initializer_list<const void*> storage,
                           bool bf16) {
   if (((long)H * W) % 4 != 0) return 1;

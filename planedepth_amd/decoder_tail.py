@@ -182,3 +182,46 @@ def fused_plade_tail(outputs, conv0_out, conv_sigma_out=None, *, use_mixture_los
     outputs["disp"] = disp
     outputs["depth"] = depth
     return outputs
+
+
+def _fill_inference(outputs, res, shape, device):
+    outputs["disp"] = res.disp
+    outputs["depth"] = res.depth
+    outputs["confidence"] = res.confidence
+    outputs["plane_index"] = res.plane_index
+    outputs["disp_best"] = res.disp_best
+    outputs["probability"] = LazyLayers(shape, lambda: res.layers(False, True)[1], device, torch.float32)
+    return outputs
+
+
+_INFERENCE_WANT = ("depth", "confidence", "plane_index", "disp_best", "layers")
+
+
+def fused_decoder_tail_inference(outputs, dispconv_out, sigmaconv_out=None, *, use_mixture_loss=True, all_ones_mask=False):
+    """``fused_decoder_tail`` for a network that only predicts (``planedepth_amd.predict``, the reference's
+    evaluate_depth_HR.py): fills ``outputs["disp"]``, ``["depth"]``, ``["confidence"]`` (``max_n probability_n``, fp32 [B,1,H,W]:
+    what evaluate_depth_HR.py:168 reduces ``probability`` to), ``["plane_index"]`` (int32, the plane that attains it;
+    depth_decoder.py:286), ``["disp_best"]`` (``disp_layered`` at that plane) and ``["probability"]`` — a ``LazyLayers``, so
+    ``output["probability"].amax(1)`` keeps working unchanged and the [B,N,H,W] tensor exists only if something touches it.
+    One forward-only kernel (``ops.decoder_tail_inference``); ``disp`` / ``depth`` have ``fused_decoder_tail``'s bits.
+
+    NOT set: ``outputs["logits"]``, ``["sigma"]`` and ``["pi"]`` — writing those [B,N,H,W] tensors is what this call saves.  A
+    caller that wants them (the plane sweep, the losses, the self-distillation post-process) uses ``fused_decoder_tail``, under
+    ``torch.no_grad()`` where no gradient is needed.  Call it under ``torch.no_grad()``: conv outputs that require grad raise
+    ``ValueError`` otherwise."""
+    mask = None if all_ones_mask else outputs["padding_mask"]
+    res = ops.decoder_tail_inference(dispconv_out, sigmaconv_out, mask, outputs["disp_layered"],
+                                     use_mixture_loss=use_mixture_loss, want=_INFERENCE_WANT)
+    return _fill_inference(outputs, res, dispconv_out.shape, dispconv_out.device)
+
+
+def fused_plade_tail_inference(outputs, conv0_out, conv_sigma_out=None, *, use_mixture_loss=True):
+    """``fused_plade_tail`` for a network that only predicts: the keys of ``fused_decoder_tail_inference`` from one forward-only
+    kernel (``ops.plade_tail_inference``), with ``fused_plade_tail``'s bits in ``disp`` / ``depth``.
+
+    NOT set: ``outputs["logits"]``, ``["dists"]``, ``["sigma"]`` and ``["pi"]``; a caller that wants them uses ``fused_plade_tail``
+    (under ``torch.no_grad()`` where no gradient is needed)."""
+    B, Nm1, H, W = conv0_out.shape
+    res = ops.plade_tail_inference(conv0_out, conv_sigma_out, outputs["disp_layered"], use_mixture_loss=use_mixture_loss,
+                                   want=_INFERENCE_WANT)
+    return _fill_inference(outputs, res, (B, Nm1 + 1, H, W), conv0_out.device)

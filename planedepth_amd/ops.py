@@ -25,7 +25,7 @@ from .sweep import (  # noqa: F401
 from .tails import (  # noqa: F401
     _PlaneLevels, plane_disparities, _PlaneGeometry, plane_geometry,
     _DecoderTail, decoder_tail, _PladeTail, _RAY_NORM, camera_ray_norm, _camera_ray_norm,
-    plade_tail)
+    plade_tail, InferenceTail, decoder_tail_inference, plade_tail_inference)
 from .losses import (  # noqa: F401
     _SSIM, ssim, _ReprojLoss, reprojection_loss, _MixtureNLL, multimodal_loss,
     _MaskedPhotometric, masked_photometric, _row_strided, _SmoothLoss, smooth_loss_disp,

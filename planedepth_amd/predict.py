@@ -1,0 +1,57 @@
+"""From images to depth maps: the prediction loop of the reference's ``evaluate_depth_HR.py`` (lines 139-168) on the device — the
+producer of what ``metrics.eval_depth_errors`` and ``planedepth_amd.evaluate`` consume.
+
+``model(images, grids)`` is the reference's ``depth_decoder(encoder(x), grids)`` or ``PladeNet`` and returns the outputs dict.  With
+the inference tail inside (``decoder_tail.fused_decoder_tail_inference`` / ``fused_plade_tail_inference``) nothing plane-sized is
+written on the way to ``outputs["disp"]`` and ``outputs["confidence"]``; a model that still carries the training tail works too
+(its confidence is taken from ``outputs["probability"].amax(1)``, which materialises the [B,N,H,W] tensor).
+"""
+import collections
+
+import torch
+
+from . import _capi as C
+from . import ops
+
+Prediction = collections.namedtuple("Prediction", "raw_disp disp depth confidence mean_confidence")
+
+
+def eval_grid(batch, height, width, device):
+    """``inputs["grid"]`` of evaluate_depth_HR.py:139-152: ``linspace(-1, 1)`` over the width and the height, meshgrid "xy",
+    stacked (x, y) and expanded over the batch — [batch,2,height,width], built on the host as the reference builds it."""
+    grid = torch.stack(torch.meshgrid(torch.linspace(-1, 1, width), torch.linspace(-1, 1, height), indexing="xy"), dim=0)
+    return grid.to(device)[None].expand(batch, -1, -1, -1)
+
+
+def predict(model, images, *, post_process=False, autocast=False):
+    """Disparity, depth and confidence of ``images`` [M,3,h,w] (fp32, on the GPU) under ``torch.no_grad()``, and under
+    ``torch.autocast("cuda", torch.bfloat16)`` when ``autocast``.  With ``post_process`` the batch is ``[images ; mirrored images]``
+    (``ops.cat_flip``: two forward passes per image, evaluate_depth_HR.py:148-150).  Returns the named tuple
+
+    * ``raw_disp`` [M,h,w], [2M,h,w] with ``post_process``: ``outputs["disp"][:, 0]`` — what ``metrics.eval_depth_errors(...,
+      post_process=...)`` takes;
+    * ``disp`` [M,1,h,w]: ``outputs["disp"]``, or with ``post_process`` ``0.5f * (d[:M] + d[M:].flip(-1))`` — the live part of
+      ``batch_post_process_disparity`` (contract A1 of ``metrics``);
+    * ``depth`` = ``float32(0.1 * 0.58 * w) / disp``;
+    * ``confidence`` [M or 2M,1,h,w]: ``max_n probability_n`` of every pass;
+    * ``mean_confidence`` [M or 2M]: its mean over the image, the reference's ``probabilities_max`` (:168).
+
+    The averages and the mean are plain torch on [.,1,h,w] tensors."""
+    C.require_gpu_tensor("images", images)
+    if images.dim() != 4:
+        raise ValueError("images must be [M,C,h,w], got %s" % (tuple(images.shape),))
+    M, _, h, w = images.shape
+    with torch.no_grad():
+        batch = ops.cat_flip(images, images) if post_process else images
+        grids = eval_grid(batch.shape[0], h, w, images.device)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(autocast)):
+            outputs = model(batch, grids)
+        d = outputs["disp"]
+        confidence = outputs.get("confidence")
+        if confidence is None:   # a training tail: probability is a [B,N,H,W] tensor (or the lazy stand-in for one)
+            confidence = outputs["probability"].amax(1, keepdim=True)
+        raw_disp = d[:, 0]
+        disp = 0.5 * (d[:M] + d[M:].flip(-1)) if post_process else d
+        depth = disp.new_full((), 0.1 * 0.58 * w) / disp   # (a true division: ``scalar / tensor`` is reciprocal-times-scalar)
+        mean_confidence = confidence[:, 0].mean(-1).mean(-1)
+    return Prediction(raw_disp, disp, depth, confidence, mean_confidence)

@@ -1,6 +1,7 @@
 """Network tails: DepthDecoder's (networks/depth_decoder.py:258-291) and PladeNet's compositing tail
 (networks/plade_net.py:309-341).
 """
+import collections
 import os
 
 from . import _capi as C
@@ -218,7 +219,7 @@ class _PladeTail(torch.autograd.Function):
         logits, dists = new(B, N, H, W, dtype=st), new(B, N - 1, H, W)
         sigma = new(B, N, H, W, dtype=st) if mix else None
         disp, depth, stash = new(B, 1, H, W), new(B, 1, H, W), new(B, 1, H, W)
-        with C.on_device(dev):
+        with C.on_device(dev), _timed("plade_fwd"):
             C.check(lib.pd_plade_tail_fwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(disp_layered),
                                           C.ptr(ray_norm), C.ptr(logits), C.ptr(dists), C.ptr(sigma), C.ptr(disp), C.ptr(depth),
                                           C.ptr(stash), C.stream_handle(dev)), "pd_plade_tail_fwd")
@@ -310,6 +311,139 @@ def plade_tail(raw_logits, raw_sigma, disp_layered, ray_norm=None, use_mixture_l
         return pi, prob
 
     return logits, dists, (sigma if use_mixture_loss else None), disp, depth, layers
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Inference tails: forward only, nothing [B,N,H,W]-sized written (pd_decoder_tail_infer / pd_plade_tail_infer)
+# ---------------------------------------------------------------------------------------------------------------------
+InferenceTail = collections.namedtuple("InferenceTail", "disp depth confidence plane_index disp_best layers")
+_INFER_WANT = ("depth", "confidence", "plane_index", "disp_best", "layers")
+
+
+def _infer_want(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for w in want:
+        if w not in _INFER_WANT:
+            raise ValueError("want: unknown output %r (disp is always returned; the optional ones are %s)"
+                             % (w, ", ".join(_INFER_WANT)))
+    return want
+
+
+def _infer_no_grad(differentiable, **tensors):
+    """The inference tails build no autograd node: an input that asks for a gradient is a caller's mistake, not a silent detach."""
+    if torch.is_grad_enabled():
+        for name, t in tensors.items():
+            if torch.is_tensor(t) and t.requires_grad:
+                raise ValueError("%s requires grad, but %s_inference is forward-only: call it under torch.no_grad(), or use "
+                                 "ops.%s, the differentiable operator" % (name, differentiable, differentiable))
+
+
+def _infer_outputs(B, H, W, dev, want, stash_channels):
+    new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)  # noqa: E731
+    return (new(B, 1, H, W),
+            new(B, 1, H, W) if "depth" in want else None,
+            new(B, 1, H, W) if "confidence" in want else None,
+            new(B, 1, H, W, dtype=torch.int32) if "plane_index" in want else None,
+            new(B, 1, H, W) if "disp_best" in want else None,
+            new(B, stash_channels, H, W) if "layers" in want else None)
+
+
+def decoder_tail_inference(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_loss=True,
+                           want=("depth", "confidence")):
+    """``decoder_tail`` for inference: ``disp`` and, as ``want`` names them, ``depth``, ``confidence`` (``max_n probability_n``,
+    fp32 [B,1,H,W]), ``plane_index`` (int32: the plane that attains it, the lowest index among equal maxima — the
+    ``candidates_idx`` of depth_decoder.py:286), ``disp_best`` (``disp_layered`` at that plane) and ``layers`` (the stash is then
+    kept and ``layers()`` materialises ``(pi, probability)`` on demand, as ``decoder_tail``'s does).  Returns the named tuple
+    ``(disp, depth, confidence, plane_index, disp_best, layers)``; what was not asked for is ``None``.
+
+    One forward-only kernel (``pd_decoder_tail_infer``) that writes nothing [B,N,H,W]-sized — no ``logits``, no ``sigma`` — where
+    ``decoder_tail`` under ``no_grad`` writes both.  ``disp`` / ``depth`` have ``decoder_tail``'s bits.  Inputs, their forms (per
+    plane, row views recognised by their strides, dense) and dtypes (fp32, or both conv outputs bf16) are ``decoder_tail``'s.
+    The results carry no autograd node: with gradients enabled an input that requires grad raises ``ValueError`` —
+    ``decoder_tail`` is the differentiable operator."""
+    want = _infer_want(want)
+    B, N, H, W = raw_logits.shape
+    bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
+    _infer_no_grad("decoder_tail", raw_logits=raw_logits, raw_sigma=raw_sigma if use_mixture_loss else None,
+                   padding_mask=padding_mask, disp_layered=disp_layered)
+    st = raw_logits.dtype
+    C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
+    with torch.no_grad():
+        form, plane = PF.disp_operand(disp_layered, B, N, H, W, grad=False)
+        flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | bf16 | _DISP_FLAG[form]
+        if padding_mask is not None:
+            mask_form, padding_mask = PF.mask_operand(padding_mask, B, N, H, W)
+            flags |= C.PD_TAIL_MASK_ROWS if mask_form == PF.ROWS else 0
+            C.require_gpu_tensor("padding_mask", padding_mask, (B, N, H) if flags & C.PD_TAIL_MASK_ROWS else (B, N, H, W))
+        if use_mixture_loss:
+            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
+        C.require_gpu_tensor("disp_layered", plane, (B, N, H, W) if form == PF.DENSE else (B, N, H) if form == PF.ROWS else (B, N))
+        rl, rs, pm, dl = map(_contig, (raw_logits.detach(), raw_sigma.detach() if use_mixture_loss else None, padding_mask, plane))
+        dev = rl.device
+        disp, depth, conf, index, best, stash = _infer_outputs(B, H, W, dev, want, 2)
+        lib = C.load()
+        with C.on_device(dev), _timed("tail_infer"):
+            C.check(lib.pd_decoder_tail_infer(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pm), C.ptr(dl), C.ptr(disp),
+                                              C.ptr(depth), C.ptr(conf), C.ptr(index), C.ptr(best), C.ptr(stash),
+                                              C.stream_handle(dev)), "pd_decoder_tail_infer")
+
+    def layers(want_pi=True, want_probability=True):
+        with torch.no_grad():
+            pi = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_pi else None
+            prob = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_probability else None
+            with C.on_device(dev):
+                C.check(lib.pd_decoder_tail_layers(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pm), C.ptr(stash),
+                                                   C.ptr(pi), C.ptr(prob), C.stream_handle(dev)), "pd_decoder_tail_layers")
+        return pi, prob
+
+    layers.stash = stash   # (what pd_*_tail_fwd would have written: kept for layers(), readable for a caller that wants it)
+    return InferenceTail(disp, depth, conf, index, best, layers if stash is not None else None)
+
+
+def plade_tail_inference(raw_logits, raw_sigma, disp_layered, ray_norm=None, use_mixture_loss=True,
+                         want=("depth", "confidence")):
+    """``plade_tail`` for inference, with ``decoder_tail_inference``'s outputs and rules: one forward-only kernel
+    (``pd_plade_tail_infer``) that writes none of ``logits``, ``dists`` and ``sigma``.  ``raw_logits`` [B,N-1,H,W], ``raw_sigma``
+    [B,N,H,W] (mixture only), ``disp_layered`` per plane or dense (a row view is materialised: this tail has no row form).
+    ``confidence`` is ``layers()``'s ``probability.amax(1)``; ``plade_tail`` is the differentiable operator."""
+    want = _infer_want(want)
+    B, Nm1, H, W = raw_logits.shape
+    N = Nm1 + 1
+    bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
+    _infer_no_grad("plade_tail", raw_logits=raw_logits, raw_sigma=raw_sigma if use_mixture_loss else None,
+                   disp_layered=disp_layered, ray_norm=ray_norm)
+    st = raw_logits.dtype
+    C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
+    with torch.no_grad():
+        form, plane = PF.disp_operand(disp_layered, B, N, H, W, grad=False, row_views=False)
+        flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | _DISP_FLAG[form] | bf16
+        if ray_norm is None:
+            ray_norm = camera_ray_norm(H, W, raw_logits.device)
+        if use_mixture_loss:
+            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
+        C.require_gpu_tensor("disp_layered", plane, (B, N, H, W) if form == PF.DENSE else (B, N))
+        C.require_gpu_tensor("ray_norm", ray_norm, (H, W))
+        rl, rs, dl, ray = map(_contig, (raw_logits.detach(), raw_sigma.detach() if use_mixture_loss else None, plane,
+                                        ray_norm.detach()))
+        dev = rl.device
+        disp, depth, conf, index, best, stash = _infer_outputs(B, H, W, dev, want, 1)
+        lib = C.load()
+        with C.on_device(dev), _timed("plade_infer"):
+            C.check(lib.pd_plade_tail_infer(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(dl), C.ptr(ray), C.ptr(disp),
+                                            C.ptr(depth), C.ptr(conf), C.ptr(index), C.ptr(best), C.ptr(stash),
+                                            C.stream_handle(dev)), "pd_plade_tail_infer")
+
+    def layers(want_pi=True, want_probability=True):
+        with torch.no_grad():
+            pi = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_pi else None
+            prob = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_probability else None
+            with C.on_device(dev):
+                C.check(lib.pd_plade_tail_layers(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(dl), C.ptr(ray), C.ptr(stash),
+                                                 C.ptr(pi), C.ptr(prob), C.stream_handle(dev)), "pd_plade_tail_layers")
+        return pi, prob
+
+    layers.stash = stash   # (what pd_*_tail_fwd would have written: kept for layers(), readable for a caller that wants it)
+    return InferenceTail(disp, depth, conf, index, best, layers if stash is not None else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
