@@ -33,9 +33,7 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __r
                                                           float* __restrict__ stash) {
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
   if (pix >= a.HW) return;
-  const long base = (long)b * a.N * a.HW + pix;
-  const int H = RF ? a.HW / a.W : 0, y = RF ? pix / a.W : 0;   // row form: the lane's row (W % PX == 0 there)
-  const long rbase = (long)b * a.N * H;
+  const TailLane ln = tail_lane<RF>(a, b, pix);
   float m[PX], Z[PX], Sw[PX], Sd[PX];  // running reference, sum e^(l-m), sum of weights, sum w*d
 #pragma unroll
   for (int j = 0; j < PX; ++j) { m[j] = -INFINITY; Z[j] = Sw[j] = Sd[j] = 0.0f; }
@@ -44,46 +42,22 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(TailArgs a, float* __r
   constexpr int kUnroll = sizeof(ST) == sizeof(float) ? 2 : 1;
 #pragma unroll kUnroll
   for (int n = 0; n < a.N; ++n) {
-    const long i = base + (long)n * a.HW;
-    const Px<PX> mk = !HASMASK ? splat<PX>(1.0f) : (RF & kRowMask) ? ld_row<PX>(a.mask + rbase, n, H, y) : ldv<PX>(a.mask + i);
-    const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
-    const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
-    const Px<PX> dv = (RF & kRowDisp) ? ld_row<PX>(a.dl + rbase, n, H, y)
-                                      : a.dense ? ldv<PX>(a.dl + i) : splat<PX>(a.dl[b * a.N + n]);
+    const long i = ln.base + (long)n * a.HW;
+    TailOperands<PX> q;
+    tail_operands<ST, MIX, HASMASK, PX, RF>(a, ln, n, i, q);
     Px<PX> lo, so;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
-      const float l = rl.v[j] * mk.v[j];                           // depth_decoder.py:259
-      lo.v[j] = l;
-      float inv = 1.0f;
-      if (MIX) {
-        const float sg = clamp_sigma(sigmoid_f(rs.v[j]));          // :278-279
-        so.v[j] = sg;
-        inv = mk.v[j] / sg;                                        // :282-283 (mask applied to the weights)
-      }
-      if (l > m[j]) {  // move the reference to the new maximum
-        const float sc = __expf(m[j] - l);
-        Z[j] *= sc; Sw[j] *= sc; Sd[j] *= sc;
-        m[j] = l;
-      }
-      const float e = __expf(l - m[j]);
-      const float w = e * inv;
-      Z[j] += e;
-      Sw[j] += w;
-      Sd[j] += w * dv.v[j];
+      float none, w;   // (no best weight here)
+      tail_softmax_step<MIX, false>(q.rl.v[j], q.rs.v[j], q.mk.v[j], q.dv.v[j], m[j], Z[j], Sw[j], Sd[j], none, lo.v[j], so.v[j], w);
     }
     if (HASMASK) stv<PX>(elems<ST>(logits) + i, lo);
     if (MIX) stv<PX>(elems<ST>(sigma) + i, so);
   }
   Px<PX> o_disp, o_depth, o_lse, o_sn;
 #pragma unroll
-  for (int j = 0; j < PX; ++j) {
-    const float dsp = Sd[j] / Sw[j];                                // :284-285, 289 (the softmax normaliser cancels)
-    o_disp.v[j] = dsp;
-    o_depth.v[j] = 0.1f * 0.58f * (float)a.W / dsp;                 // :291
-    o_lse.v[j] = m[j] + __logf(Z[j]);                               // log-sum-exp of the masked logits
-    o_sn.v[j] = Sw[j] / Z[j];                                       // sum_N pi * mask / sigma
-  }
+  for (int j = 0; j < PX; ++j)
+    tail_softmax_finish(m[j], Z[j], Sw[j], Sd[j], tail_depth_scale(a.W), o_disp.v[j], o_depth.v[j], o_lse.v[j], o_sn.v[j]);
   stv<PX>(disp + (long)b * a.HW + pix, o_disp);
   stv<PX>(depth + (long)b * a.HW + pix, o_depth);
   stv<PX>(stash + ((long)b * 2 + 0) * a.HW + pix, o_lse);
@@ -96,23 +70,20 @@ __global__ __launch_bounds__(kBlock) void tail_layers_kernel(TailArgs a, const f
                                                              float* __restrict__ pi, float* __restrict__ prob) {
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
   if (pix >= a.HW) return;
-  const long base = (long)b * a.N * a.HW + pix;
   const Px<PX> lse = ldv<PX>(stash + ((long)b * 2 + 0) * a.HW + pix);
   const Px<PX> sn = ldv<PX>(stash + ((long)b * 2 + 1) * a.HW + pix);
-  const int H = RF ? a.HW / a.W : 0, y = RF ? pix / a.W : 0;
-  const long rbase = (long)b * a.N * H;
+  const TailLane ln = tail_lane<RF>(a, b, pix);
 #pragma unroll 2
   for (int n = 0; n < a.N; ++n) {
-    const long i = base + (long)n * a.HW;
-    const Px<PX> mk = !HASMASK ? splat<PX>(1.0f) : (RF & kRowMask) ? ld_row<PX>(a.mask + rbase, n, H, y) : ldv<PX>(a.mask + i);
-    const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
-    const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
+    const long i = ln.base + (long)n * a.HW;
+    TailOperands<PX> q;
+    tail_operands<ST, MIX, HASMASK, PX, RF, false>(a, ln, n, i, q);   // (no disparity here)
     Px<PX> op, oq;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
-      const float p = __expf(rl.v[j] * mk.v[j] - lse.v[j]);
+      const float p = __expf(q.rl.v[j] * q.mk.v[j] - lse.v[j]);
       op.v[j] = p;
-      oq.v[j] = MIX ? p * mk.v[j] / clamp_sigma(sigmoid_f(rs.v[j])) / sn.v[j] : p;
+      oq.v[j] = MIX ? p * q.mk.v[j] / clamp_sigma(sigmoid_f(q.rs.v[j])) / sn.v[j] : p;
     }
     if (pi) stv<PX>(pi + i, op);
     if (prob) stv<PX>(prob + i, oq);
@@ -123,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void tail_layers_kernel(TailArgs a, const f
 // (+ the depth term): d disp / d w_n = (d_n - disp) / S, and since sum_k pi_k (d loss / d pi_k) = gD/S * sum_k w_k
 // (d_k - disp) = 0 exactly, the softmax backward needs no second reduction:
 //   g_logits_n += gD (d_n - disp) P_n;   g_sigma_n -= gD (d_n - disp) P_n / sigma_n;   g_d_n = gD P_n.
-// One pixel of one plane (shared by the pixel-linear and the row-owned kernel: the same expressions in the same order).
+// One pixel of one plane.
 template <bool MIX>
 __device__ __forceinline__ void tail_bwd_px(float rl, float rs, float mk, float dv, float gl, float gs, float lse, float sn,
                                             float dsp, float gD, float& o_l, float& o_s, float& o_d) {
@@ -141,72 +112,71 @@ __device__ __forceinline__ void tail_bwd_px(float rl, float rs, float mk, float 
   o_d = gD * P;
 }
 
-// Pixel-linear form: per-plane or dense disparities (RF: 0, or kRowMask for a [B,N,H] mask).
+// What the backward keeps per pixel over the planes: the stash, disp and the upstream gradient of disp.  An inactive lane
+// (it only takes part in the reductions) gets values that are never used.
+template <int PX>
+struct TailBwdPixel {
+  Px<PX> lse, sn, dsp, gD;
+};
+template <int PX>
+__device__ __forceinline__ TailBwdPixel<PX> tail_bwd_pixel(const TailArgs& a, bool active, int b, int pix,
+                                                           const float* __restrict__ stash, const float* __restrict__ disp,
+                                                           const float* __restrict__ g_disp, const float* __restrict__ g_depth) {
+  TailBwdPixel<PX> q = {splat<PX>(0.0f), splat<PX>(1.0f), splat<PX>(1.0f), splat<PX>(0.0f)};
+  if (active) {
+    q.lse = ldv<PX>(stash + ((long)b * 2 + 0) * a.HW + pix);
+    q.sn = ldv<PX>(stash + ((long)b * 2 + 1) * a.HW + pix);
+    q.dsp = ldv<PX>(disp + (long)b * a.HW + pix);
+    q.gD = tail_upstream<PX>(g_disp, g_depth, (long)b * a.HW + pix, q.dsp, tail_depth_scale(a.W));
+  }
+  return q;
+}
+// One plane at an active lane: loads, tail_bwd_px per pixel, stores.  Adds the lane's disparity gradients to gd.  Each
+// gradient pointer may be NULL; g_dl is written here in the dense form only (tested as the kernels always tested it: with another
+// form of the test the compiler stopped contracting gd += gD * P into an fma, and the per-plane gradient's last bit moved).
 template <class ST, bool MIX, bool HASMASK, int PX, int RF>
-__global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const float* __restrict__ stash,
-                                                          const float* __restrict__ disp,
-                                                          const float* __restrict__ g_logits,
-                                                          const float* __restrict__ g_sigma,
-                                                          const float* __restrict__ g_disp,
-                                                          const float* __restrict__ g_depth,
-                                                          float* __restrict__ g_raw_logits,
-                                                          float* __restrict__ g_raw_sigma, float* __restrict__ g_dl,
-                                                          float* __restrict__ partials) {
+__device__ __forceinline__ void tail_bwd_plane(const TailArgs& a, const TailLane& ln, int n, const TailBwdPixel<PX>& q,
+                                               const float* __restrict__ g_logits, const float* __restrict__ g_sigma,
+                                               float* __restrict__ g_raw_logits, float* __restrict__ g_raw_sigma,
+                                               float* __restrict__ g_dl, float& gd) {
+  const long i = ln.base + (long)n * a.HW;
+  TailOperands<PX> o;
+    tail_operands<ST, MIX, HASMASK, PX, RF>(a, ln, n, i, o);
+  const Px<PX> gl = g_logits ? ldv<PX>(elems<ST>(g_logits) + i) : splat<PX>(0.0f);
+  const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(elems<ST>(g_sigma) + i) : splat<PX>(0.0f);
+  Px<PX> o_l, o_s, o_d;
+#pragma unroll
+  for (int j = 0; j < PX; ++j) {
+    tail_bwd_px<MIX>(o.rl.v[j], o.rs.v[j], o.mk.v[j], o.dv.v[j], gl.v[j], gs.v[j], q.lse.v[j], q.sn.v[j], q.dsp.v[j], q.gD.v[j],
+                     o_l.v[j], o_s.v[j], o_d.v[j]);
+    gd += o_d.v[j];
+  }
+  if (g_raw_logits) stv<PX>(elems<ST>(g_raw_logits) + i, o_l);
+  if (MIX && g_raw_sigma) stv<PX>(elems<ST>(g_raw_sigma) + i, o_s);
+  if (!(RF & kRowDisp) && g_dl && a.dense) stv<PX>(g_dl + i, o_d);
+}
+
+// Pixel-linear form: per-plane or dense disparities (RF: 0, or kRowMask for a [B,N,H] mask).  The per-plane form's gradient
+// goes through LDS-atomic block partials and reduce_partials.
+template <class ST, bool MIX, bool HASMASK, int PX, int RF>
+__global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const float* __restrict__ stash, const float* __restrict__ disp,
+                                                          const float* __restrict__ g_logits, const float* __restrict__ g_sigma,
+                                                          const float* __restrict__ g_disp, const float* __restrict__ g_depth,
+                                                          float* __restrict__ g_raw_logits, float* __restrict__ g_raw_sigma,
+                                                          float* __restrict__ g_dl, float* __restrict__ partials) {
   extern __shared__ float red[];  // [N] block sums of the per-plane disparity gradient
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
   const bool reduce = (g_dl != nullptr) && !a.dense;
-  if (reduce) {
-    for (int i = threadIdx.x; i < a.N; i += kBlock) red[i] = 0.0f;
-    __syncthreads();
-  }
+  if (reduce) block_partials_zero(red, a.N);
   const bool active = pix < a.HW;
-  const long base = (long)b * a.N * a.HW + (active ? pix : 0);
-  const int H = RF ? a.HW / a.W : 0, y = RF ? (active ? pix : 0) / a.W : 0;
-  const long rbase = (long)b * a.N * H;
-  Px<PX> lse = splat<PX>(0.0f), sn = splat<PX>(1.0f), dsp = splat<PX>(1.0f), gD = splat<PX>(0.0f);
-  if (active) {
-    lse = ldv<PX>(stash + ((long)b * 2 + 0) * a.HW + pix);
-    sn = ldv<PX>(stash + ((long)b * 2 + 1) * a.HW + pix);
-    dsp = ldv<PX>(disp + (long)b * a.HW + pix);
-    if (g_disp) gD = ldv<PX>(g_disp + (long)b * a.HW + pix);
-    if (g_depth) {
-      const Px<PX> gz = ldv<PX>(g_depth + (long)b * a.HW + pix);
-#pragma unroll
-      for (int j = 0; j < PX; ++j) gD.v[j] -= gz.v[j] * (0.1f * 0.58f * (float)a.W) / (dsp.v[j] * dsp.v[j]);
-    }
-  }
-  const int lane = threadIdx.x & (kWave - 1);
+  const TailLane ln = tail_lane<RF>(a, b, active ? pix : 0);
+  const TailBwdPixel<PX> q = tail_bwd_pixel<PX>(a, active, b, pix, stash, disp, g_disp, g_depth);
   for (int n = 0; n < a.N; ++n) {
-    const long i = base + (long)n * a.HW;
     float gd = 0.0f;
-    if (active) {
-      const Px<PX> mk = !HASMASK ? splat<PX>(1.0f) : (RF & kRowMask) ? ld_row<PX>(a.mask + rbase, n, H, y) : ldv<PX>(a.mask + i);
-      const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
-      const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
-      const Px<PX> dv = a.dense ? ldv<PX>(a.dl + i) : splat<PX>(a.dl[b * a.N + n]);
-      const Px<PX> gl = g_logits ? ldv<PX>(elems<ST>(g_logits) + i) : splat<PX>(0.0f);
-      const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(elems<ST>(g_sigma) + i) : splat<PX>(0.0f);
-      Px<PX> o_l, o_s, o_d;
-#pragma unroll
-      for (int j = 0; j < PX; ++j) {
-        tail_bwd_px<MIX>(rl.v[j], rs.v[j], mk.v[j], dv.v[j], gl.v[j], gs.v[j], lse.v[j], sn.v[j], dsp.v[j], gD.v[j], o_l.v[j],
-                         o_s.v[j], o_d.v[j]);
-        gd += o_d.v[j];
-      }
-      if (g_raw_logits) stv<PX>(elems<ST>(g_raw_logits) + i, o_l);
-      if (MIX && g_raw_sigma) stv<PX>(elems<ST>(g_raw_sigma) + i, o_s);
-      if (g_dl && a.dense) stv<PX>(g_dl + i, o_d);
-    }
-    if (reduce) {
-      const float v = wave_sum_hi(gd);
-      if (lane == kWave - 1) lds_add(&red[n], v);
-    }
+    if (active) tail_bwd_plane<ST, MIX, HASMASK, PX, RF>(a, ln, n, q, g_logits, g_sigma, g_raw_logits, g_raw_sigma, g_dl, gd);
+    if (reduce) block_partials_add(red, n, gd);
   }
-  if (reduce) {
-    __syncthreads();
-    float* dst = partials + ((long)b * gridDim.x + blockIdx.x) * a.N;
-    for (int i = threadIdx.x; i < a.N; i += kBlock) dst[i] = red[i];
-  }
+  if (reduce) block_partials_store(red, partials, b, a.N);
 }
 
 // Row-owned form (PD_TAIL_DISP_ROWS; RF holds kRowDisp): workgroup (y, b) walks row y of image b in steps of blockDim.x * PX
@@ -214,12 +184,9 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_kernel(TailArgs a, const floa
 // (red[wave][n]: plain read-add-write by one lane, no atomics), and plane n's thread adds the waves' in wave order.
 template <class ST, bool MIX, bool HASMASK, int PX, int RF>
 __global__ __launch_bounds__(kBlock) void tail_bwd_rows_kernel(TailArgs a, const float* __restrict__ stash,
-                                                               const float* __restrict__ disp,
-                                                               const float* __restrict__ g_logits,
-                                                               const float* __restrict__ g_sigma,
-                                                               const float* __restrict__ g_disp,
-                                                               const float* __restrict__ g_depth,
-                                                               float* __restrict__ g_raw_logits,
+                                                               const float* __restrict__ disp, const float* __restrict__ g_logits,
+                                                               const float* __restrict__ g_sigma, const float* __restrict__ g_disp,
+                                                               const float* __restrict__ g_depth, float* __restrict__ g_raw_logits,
                                                                float* __restrict__ g_raw_sigma, float* __restrict__ g_dl) {
   extern __shared__ float red[];  // [waves][N]
   const int y = blockIdx.x, b = blockIdx.y, H = gridDim.x;
@@ -233,39 +200,11 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_rows_kernel(TailArgs a, const
     const int x = x0 + threadIdx.x * PX;
     const bool active = x < a.W;
     const int pix = y * a.W + (active ? x : 0);
-    const long base = (long)b * a.N * a.HW + pix;
-    Px<PX> lse = splat<PX>(0.0f), sn = splat<PX>(1.0f), dsp = splat<PX>(1.0f), gD = splat<PX>(0.0f);
-    if (active) {
-      lse = ldv<PX>(stash + ((long)b * 2 + 0) * a.HW + pix);
-      sn = ldv<PX>(stash + ((long)b * 2 + 1) * a.HW + pix);
-      dsp = ldv<PX>(disp + (long)b * a.HW + pix);
-      if (g_disp) gD = ldv<PX>(g_disp + (long)b * a.HW + pix);
-      if (g_depth) {
-        const Px<PX> gz = ldv<PX>(g_depth + (long)b * a.HW + pix);
-#pragma unroll
-        for (int j = 0; j < PX; ++j) gD.v[j] -= gz.v[j] * (0.1f * 0.58f * (float)a.W) / (dsp.v[j] * dsp.v[j]);
-      }
-    }
+    const TailLane ln = {b, H, y, (long)b * a.N * a.HW + pix, rbase};
+    const TailBwdPixel<PX> q = tail_bwd_pixel<PX>(a, active, b, pix, stash, disp, g_disp, g_depth);
     for (int n = 0; n < a.N; ++n) {
-      const long i = base + (long)n * a.HW;
       float gd = 0.0f;
-      if (active) {
-        const Px<PX> mk = !HASMASK ? splat<PX>(1.0f) : (RF & kRowMask) ? ld_row<PX>(a.mask + rbase, n, H, y) : ldv<PX>(a.mask + i);
-        const Px<PX> rl = ldv<PX>(elems<ST>(a.raw_logits) + i);
-        const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + i) : splat<PX>(0.0f);
-        const Px<PX> dv = ld_row<PX>(a.dl + rbase, n, H, y);
-        const Px<PX> gl = g_logits ? ldv<PX>(elems<ST>(g_logits) + i) : splat<PX>(0.0f);
-        const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(elems<ST>(g_sigma) + i) : splat<PX>(0.0f);
-        Px<PX> o_l, o_s, o_d;
-#pragma unroll
-        for (int j = 0; j < PX; ++j) {
-          tail_bwd_px<MIX>(rl.v[j], rs.v[j], mk.v[j], dv.v[j], gl.v[j], gs.v[j], lse.v[j], sn.v[j], dsp.v[j], gD.v[j], o_l.v[j],
-                           o_s.v[j], o_d.v[j]);
-          gd += o_d.v[j];
-        }
-        if (g_raw_logits) stv<PX>(elems<ST>(g_raw_logits) + i, o_l);
-        if (MIX && g_raw_sigma) stv<PX>(elems<ST>(g_raw_sigma) + i, o_s);
-      }
+      if (active) tail_bwd_plane<ST, MIX, HASMASK, PX, RF>(a, ln, n, q, g_logits, g_sigma, g_raw_logits, g_raw_sigma, g_dl, gd);
       if (g_dl) {
         const float v = wave_sum_hi(gd);
         if (lane == kWave - 1) red[wave * a.N + n] += v;
@@ -299,22 +238,11 @@ extern "C" int pd_decoder_tail_fwd(int B, int N, int H, int W, int flags, const 
   PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || sigma, "mixture needs the sigma output");
   PD_REQUIRE(!padding_mask || logits, "a padding mask needs the logits output");
   const TailArgs a = tail_args(N, H, W, flags, raw_logits, raw_sigma, padding_mask, disp_layered);
-  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
   const int rf = tail_rf(flags, padding_mask);
-  const int px = tail_px_rows(tail_px(H, W, {(rf & kRowMask) ? nullptr : padding_mask, a.dense ? disp_layered : nullptr, disp,
-                                             depth, stash},
-                                      {raw_logits, raw_sigma, logits, sigma}, bf16), rf, W);
-  dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  const bool hasmask = padding_mask != nullptr;
-#define PD_TAIL_FWD(RF) \
-  PD_TAIL_DISPATCH(tail_fwd_kernel, RF, bf16, px, a.mix, hasmask, grid, kBlock, 0, (hipStream_t)stream, a, logits, sigma, disp, depth, stash)
-  switch (rf) {
-    case 0: PD_TAIL_FWD(0); break;
-    case kRowDisp: PD_TAIL_FWD(kRowDisp); break;
-    case kRowMask: PD_TAIL_FWD(kRowMask); break;
-    default: PD_TAIL_FWD(kRowDisp | kRowMask); break;
-  }
-#undef PD_TAIL_FWD
+  const TailLaunch t = tail_launch(B, H, W, flags, rf, {(rf & kRowMask) ? nullptr : padding_mask, a.dense ? disp_layered : nullptr,
+                                                        disp, depth, stash}, {raw_logits, raw_sigma, logits, sigma});
+  PD_TAIL_DISPATCH_RF(tail_fwd_kernel, rf, t.bf16, t.px, a.mix, padding_mask != nullptr, t.grid, kBlock, 0, (hipStream_t)stream, a,
+                      logits, sigma, disp, depth, stash);
   return check_launch("tail_fwd_kernel");
 }
 
@@ -324,24 +252,17 @@ extern "C" int pd_decoder_tail_layers(int B, int N, int H, int W, int flags, con
   if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, padding_mask, raw_logits)) return rc;
   PD_REQUIRE(stash && (pi || probability), "NULL pointer");
   const TailArgs a = tail_args(N, H, W, flags, raw_logits, raw_sigma, padding_mask, nullptr);
-  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
   const int rf = tail_rf(flags, padding_mask) & kRowMask;   // (disp_layered is not read here)
-  const int px = tail_px_rows(tail_px(H, W, {rf ? nullptr : padding_mask, stash, pi, probability}, {raw_logits, raw_sigma}, bf16),
-                              rf, W);
-  dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  const bool hasmask = padding_mask != nullptr;
-  if (rf) PD_TAIL_DISPATCH(tail_layers_kernel, kRowMask, bf16, px, a.mix, hasmask, grid, kBlock, 0, (hipStream_t)stream, a, stash,
-                           pi, probability);
-  else    PD_TAIL_DISPATCH(tail_layers_kernel, 0, bf16, px, a.mix, hasmask, grid, kBlock, 0, (hipStream_t)stream, a, stash, pi,
-                           probability);
+  const TailLaunch t = tail_launch(B, H, W, flags, rf, {rf ? nullptr : padding_mask, stash, pi, probability}, {raw_logits, raw_sigma});
+  PD_TAIL_DISPATCH_MASK(tail_layers_kernel, 0, rf, t.bf16, t.px, a.mix, padding_mask != nullptr, t.grid, kBlock, 0,
+                        (hipStream_t)stream, a, stash, pi, probability);
   return check_launch("tail_layers_kernel");
 }
 
-extern "C" int pd_decoder_tail_bwd(int B, int N, int H, int W, int flags, const float* raw_logits,
-                                   const float* raw_sigma, const float* padding_mask, const float* disp_layered,
-                                   const float* stash, const float* disp, const float* g_logits, const float* g_sigma,
-                                   const float* g_disp, const float* g_depth, float* g_raw_logits, float* g_raw_sigma,
-                                   float* g_disp_layered, float* workspace, pd_stream_t stream) {
+extern "C" int pd_decoder_tail_bwd(int B, int N, int H, int W, int flags, const float* raw_logits, const float* raw_sigma,
+                                   const float* padding_mask, const float* disp_layered, const float* stash, const float* disp,
+                                   const float* g_logits, const float* g_sigma, const float* g_disp, const float* g_depth,
+                                   float* g_raw_logits, float* g_raw_sigma, float* g_disp_layered, float* workspace, pd_stream_t stream) {
   if (int rc = tail_validate(B, N, H, W, flags, raw_logits, raw_sigma, padding_mask, disp_layered)) return rc;
   PD_REQUIRE(stash && disp, "NULL pointer");
   PD_REQUIRE(g_raw_logits || g_raw_sigma || g_disp_layered, "no gradient requested");
@@ -350,35 +271,22 @@ extern "C" int pd_decoder_tail_bwd(int B, int N, int H, int W, int flags, const 
   const bool reduce = g_disp_layered && !a.dense && !(rf & kRowDisp);
   PD_REQUIRE(!reduce || workspace, "per-plane disparity gradient needs the workspace");
   PD_REQUIRE((size_t)N * sizeof(float) <= 64 * 1024 / ((rf & kRowDisp) ? kBlock / kWave : 1), "too many planes");
-  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
   const bool hasmask = padding_mask != nullptr;
-  const int px = tail_px_rows(tail_px(H, W, {(rf & kRowMask) ? nullptr : padding_mask, a.dense ? disp_layered : nullptr, stash, disp,
-                                             g_disp, g_depth, a.dense ? g_disp_layered : nullptr},
-                                      {raw_logits, raw_sigma, g_logits, g_sigma, g_raw_logits, g_raw_sigma}, bf16), rf, W);
+  const TailLaunch t = tail_launch(B, H, W, flags, rf, {(rf & kRowMask) ? nullptr : padding_mask, a.dense ? disp_layered : nullptr,
+                                                        stash, disp, g_disp, g_depth, a.dense ? g_disp_layered : nullptr},
+                                   {raw_logits, raw_sigma, g_logits, g_sigma, g_raw_logits, g_raw_sigma});
   if (rf & kRowDisp) {   // row-owned: workgroup (y, b), as many waves as the row has work for
-    const int waves = ceil_div(ceil_div(W, px), kWave);
+    const int waves = ceil_div(ceil_div(W, t.px), kWave);
     const int threads = kWave * (waves < kBlock / kWave ? waves : kBlock / kWave);
-    dim3 grid(H, B);
     const size_t shmem = g_disp_layered ? (size_t)(threads / kWave) * N * sizeof(float) : 0;
-    if (rf & kRowMask)
-      PD_TAIL_DISPATCH(tail_bwd_rows_kernel, kRowDisp | kRowMask, bf16, px, a.mix, hasmask, grid, threads, shmem, (hipStream_t)stream,
-                       a, stash, disp, g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered);
-    else
-      PD_TAIL_DISPATCH(tail_bwd_rows_kernel, kRowDisp, bf16, px, a.mix, hasmask, grid, threads, shmem, (hipStream_t)stream, a, stash,
-                       disp, g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered);
+    PD_TAIL_DISPATCH_MASK(tail_bwd_rows_kernel, kRowDisp, rf, t.bf16, t.px, a.mix, hasmask, dim3(H, B), threads, shmem,
+                          (hipStream_t)stream, a, stash, disp, g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma,
+                          g_disp_layered);
     return check_launch("tail_bwd_rows_kernel");
   }
-  dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
   const size_t shmem = reduce ? (size_t)N * sizeof(float) : 0;
-  if (rf & kRowMask)
-    PD_TAIL_DISPATCH(tail_bwd_kernel, kRowMask, bf16, px, a.mix, hasmask, grid, kBlock, shmem, (hipStream_t)stream, a, stash, disp,
-                     g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
-  else
-    PD_TAIL_DISPATCH(tail_bwd_kernel, 0, bf16, px, a.mix, hasmask, grid, kBlock, shmem, (hipStream_t)stream, a, stash, disp,
-                     g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
+  PD_TAIL_DISPATCH_MASK(tail_bwd_kernel, 0, rf, t.bf16, t.px, a.mix, hasmask, t.grid, kBlock, shmem, (hipStream_t)stream, a, stash,
+                        disp, g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
   if (int rc = check_launch("tail_bwd_kernel")) return rc;
-  if (reduce) {
-    return reduce_partials(workspace, g_disp_layered, (int)grid.x, N, B, (hipStream_t)stream);
-  }
-  return 0;
+  return reduce ? reduce_partials(workspace, g_disp_layered, (int)t.grid.x, N, B, (hipStream_t)stream) : 0;
 }

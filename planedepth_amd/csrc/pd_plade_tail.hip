@@ -26,7 +26,7 @@ __global__ __launch_bounds__(kBlock) void plade_fwd_kernel(PladeArgs a, float* _
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
   if (pix >= a.HW) return;
   const int N = a.N;
-  const float c = 0.1f * 0.58f * (float)a.W;
+  const float c = tail_depth_scale(a.W);
   const Px<PX> r = ldv<PX>(a.ray + pix);
   float T[PX], Sw[PX], Sd[PX], zc[PX];
   Px<PX> dv = plade_disp<PX>(a, b, 0, pix);
@@ -34,47 +34,30 @@ __global__ __launch_bounds__(kBlock) void plade_fwd_kernel(PladeArgs a, float* _
   for (int j = 0; j < PX; ++j) { T[j] = 1.0f; Sw[j] = Sd[j] = 0.0f; zc[j] = c / dv.v[j]; }
   for (int n = 0; n < N; ++n) {
     const bool last = (n == N - 1);
-    const Px<PX> dn = last ? dv : plade_disp<PX>(a, b, n + 1, pix);       // disparity of the NEXT plane
-    const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(elems<ST>(a.raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix);
-    const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
+    // (the operands are loaded here, not through plade_operands: with the shared loader the one-pixel bf16 mixture kernel took
+    // one more register)
+    PladeOperands<PX> q;
+    q.dn = last ? dv : plade_disp<PX>(a, b, n + 1, pix);       // disparity of the NEXT plane
+    q.rl = last ? splat<PX>(0.0f) : ldv<PX>(elems<ST>(a.raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix);
+    q.rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
     Px<PX> o_l, o_t, o_s;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
-      float alpha = 1.0f, zn = zc[j];
-      o_l.v[j] = 1.0f;                                                     // :322 the appended ones channel
-      if (!last) {
-        zn = c / dn.v[j];                                                  // :311
-        const float dist = (zn - zc[j]) * r.v[j];                          // :312-315
-        o_t.v[j] = dist;
-        o_l.v[j] = rl.v[j];
-        alpha = 1.0f - __expf(-fmaxf(rl.v[j], 0.0f) * dist);               // :317
-      }
-      const float p = alpha * T[j];                                        // :320
-      T[j] *= (1.0f - alpha) + 1e-10f;
-      if (MIX) {
-        const float sg = clamp_sigma(sigmoid_f(rs.v[j]));                  // :327-328
-        o_s.v[j] = sg;
-        const float u = p / sg;                                            // :331
-        Sw[j] += u;
-        Sd[j] += u * dv.v[j];
-      } else {
-        Sd[j] += p * dv.v[j];
-      }
-      zc[j] = zn;
+      const PladeStep s = plade_step(last, c, q.dn.v[j], q.rl.v[j], r.v[j], zc[j], T[j]);
+      o_l.v[j] = last ? 1.0f : q.rl.v[j];                                  // :322 the appended ones channel
+      o_t.v[j] = s.dist;
+      T[j] *= plade_keep(s.alpha);
+      plade_accumulate<MIX>(s.p, q.rs.v[j], dv.v[j], Sw[j], Sd[j], o_s.v[j]);
+      zc[j] = s.zn;
     }
     stv<PX>(elems<ST>(logits) + ((long)b * N + n) * a.HW + pix, o_l);
     if (!last) stv<PX>(dists + ((long)b * (N - 1) + n) * a.HW + pix, o_t);
     if (MIX) stv<PX>(elems<ST>(sigma) + ((long)b * N + n) * a.HW + pix, o_s);
-    dv = dn;
+    dv = q.dn;
   }
   Px<PX> o_disp, o_depth, o_sw;
 #pragma unroll
-  for (int j = 0; j < PX; ++j) {
-    const float dsp = MIX ? Sd[j] / Sw[j] : Sd[j];                         // :332-333, 338
-    o_disp.v[j] = dsp;
-    o_depth.v[j] = c / dsp;                                                // :340
-    o_sw.v[j] = MIX ? Sw[j] : 1.0f;
-  }
+  for (int j = 0; j < PX; ++j) plade_finish<MIX>(Sw[j], Sd[j], c, o_disp.v[j], o_depth.v[j], o_sw.v[j]);
   stv<PX>(disp + (long)b * a.HW + pix, o_disp);
   stv<PX>(depth + (long)b * a.HW + pix, o_depth);
   stv<PX>(stash + (long)b * a.HW + pix, o_sw);
@@ -87,34 +70,27 @@ __global__ __launch_bounds__(kBlock) void plade_layers_kernel(PladeArgs a, const
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
   if (pix >= a.HW) return;
   const int N = a.N;
-  const float c = 0.1f * 0.58f * (float)a.W;
+  const float c = tail_depth_scale(a.W);
   const Px<PX> r = ldv<PX>(a.ray + pix), sw = ldv<PX>(stash + (long)b * a.HW + pix);
   float T[PX], zc[PX];
   Px<PX> dv = plade_disp<PX>(a, b, 0, pix);
 #pragma unroll
   for (int j = 0; j < PX; ++j) { T[j] = 1.0f; zc[j] = c / dv.v[j]; }
   for (int n = 0; n < N; ++n) {
-    const bool last = (n == N - 1);
-    const Px<PX> dn = last ? dv : plade_disp<PX>(a, b, n + 1, pix);
-    const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(elems<ST>(a.raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix);
-    const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
+    PladeOperands<PX> q;
+    plade_operands<ST, MIX, PX>(a, b, n, pix, dv, q);
     Px<PX> op, oq;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
-      float alpha = 1.0f, zn = zc[j];
-      if (!last) {
-        zn = c / dn.v[j];
-        alpha = 1.0f - __expf(-fmaxf(rl.v[j], 0.0f) * ((zn - zc[j]) * r.v[j]));
-      }
-      const float p = alpha * T[j];
-      T[j] *= (1.0f - alpha) + 1e-10f;
-      op.v[j] = p;
-      oq.v[j] = MIX ? p / clamp_sigma(sigmoid_f(rs.v[j])) / sw.v[j] : p;
-      zc[j] = zn;
+      const PladeStep s = plade_step(n == N - 1, c, q.dn.v[j], q.rl.v[j], r.v[j], zc[j], T[j]);
+      T[j] *= plade_keep(s.alpha);
+      op.v[j] = s.p;
+      oq.v[j] = MIX ? s.p / clamp_sigma(sigmoid_f(q.rs.v[j])) / sw.v[j] : s.p;
+      zc[j] = s.zn;
     }
     if (pi) stv<PX>(pi + ((long)b * N + n) * a.HW + pix, op);
     if (prob) stv<PX>(prob + ((long)b * N + n) * a.HW + pix, oq);
-    dv = dn;
+    dv = q.dn;
   }
 }
 
@@ -129,53 +105,38 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
   const int pix = (blockIdx.x * kBlock + threadIdx.x) * PX, b = blockIdx.y;
   const int N = a.N;
   const bool reduce = (g_dl != nullptr) && !a.dense;
-  if (reduce) {
-    for (int i = threadIdx.x; i < N; i += kBlock) red[i] = 0.0f;
-    __syncthreads();
-  }
+  if (reduce) block_partials_zero(red, N);
   const bool active = pix < a.HW;
   const long px0 = active ? pix : 0;
-  const float c = 0.1f * 0.58f * (float)a.W;
+  const float c = tail_depth_scale(a.W);
   Px<PX> r = splat<PX>(0.0f), sw = splat<PX>(1.0f), dsp = splat<PX>(1.0f), gD = splat<PX>(0.0f);
   if (active) {
     r = ldv<PX>(a.ray + pix);
     sw = ldv<PX>(stash + (long)b * a.HW + pix);
     dsp = ldv<PX>(disp + (long)b * a.HW + pix);
-    if (g_disp) gD = ldv<PX>(g_disp + (long)b * a.HW + pix);
-    if (g_depth) {
-      const Px<PX> gz = ldv<PX>(g_depth + (long)b * a.HW + pix);
-#pragma unroll
-      for (int j = 0; j < PX; ++j) gD.v[j] -= gz.v[j] * c / (dsp.v[j] * dsp.v[j]);
-    }
+    gD = tail_upstream<PX>(g_disp, g_depth, (long)b * a.HW + pix, dsp, c);
   }
   float T[PX], zc[PX], prefix[PX], gprev[PX];
   Px<PX> dv = plade_disp<PX>(a, b, 0, px0);
 #pragma unroll
   for (int j = 0; j < PX; ++j) { T[j] = 1.0f; zc[j] = c / dv.v[j]; prefix[j] = 0.0f; gprev[j] = 0.0f; }
-  const int lane = threadIdx.x & (kWave - 1);
   for (int n = 0; n < N; ++n) {
     const bool last = (n == N - 1);
     float gd_sum = 0.0f;
     if (active) {
-      const Px<PX> dn = last ? dv : plade_disp<PX>(a, b, n + 1, px0);
-      const Px<PX> rl = last ? splat<PX>(0.0f) : ldv<PX>(elems<ST>(a.raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix);
-      const Px<PX> rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
+      PladeOperands<PX> q;
+    plade_operands<ST, MIX, PX>(a, b, n, px0, dv, q);
       const Px<PX> gl = (g_logits && !last) ? ldv<PX>(elems<ST>(g_logits) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
       const Px<PX> gt = (g_dists && !last) ? ldv<PX>(g_dists + ((long)b * (N - 1) + n) * a.HW + pix) : splat<PX>(0.0f);
       const Px<PX> gs = (MIX && g_sigma) ? ldv<PX>(elems<ST>(g_sigma) + ((long)b * N + n) * a.HW + pix) : splat<PX>(0.0f);
       Px<PX> o_l, o_s, o_d;
 #pragma unroll
       for (int j = 0; j < PX; ++j) {
-        float alpha = 1.0f, zn = zc[j], dist = 0.0f;
-        if (!last) {
-          zn = c / dn.v[j];
-          dist = (zn - zc[j]) * r.v[j];
-          alpha = 1.0f - __expf(-fmaxf(rl.v[j], 0.0f) * dist);
-        }
-        const float p = alpha * T[j];
+        const PladeStep s = plade_step(last, c, q.dn.v[j], q.rl.v[j], r.v[j], zc[j], T[j]);
+        const float alpha = s.alpha, dist = s.dist, p = s.p, rl = q.rl.v[j];
         float g_p, gd_direct, rtot;
         if (MIX) {
-          const float sgu = sigmoid_f(rs.v[j]), sg = clamp_sigma(sgu);
+          const float sgu = sigmoid_f(q.rs.v[j]), sg = clamp_sigma(sgu);
           const float u = p / sg;
           const float g_u = gD.v[j] * (dv.v[j] - dsp.v[j]) / sw.v[j];      // d disp / d u_n = (d_n - disp) / S
           g_p = g_u / sg;
@@ -189,13 +150,13 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
           rtot = gD.v[j] * dsp.v[j];
         }
         prefix[j] += g_p * p;
-        const float keep = (1.0f - alpha) + 1e-10f;
+        const float keep = plade_keep(alpha);
         float g_dist = 0.0f;
         if (!last) {
           const float g_alpha = g_p * T[j] - (rtot - prefix[j]) / keep;
           const float da = 1.0f - alpha;                                   // exp(-relu(l) dist)
-          o_l.v[j] = gl.v[j] + ((rl.v[j] > 0.0f) ? g_alpha * dist * da : 0.0f);
-          g_dist = gt.v[j] + g_alpha * fmaxf(rl.v[j], 0.0f) * da;
+          o_l.v[j] = gl.v[j] + ((rl > 0.0f) ? g_alpha * dist * da : 0.0f);
+          g_dist = gt.v[j] + g_alpha * fmaxf(rl, 0.0f) * da;
         }
         // depth layer n is the far end of distance n-1 and the near end of distance n
         const float g_z = r.v[j] * (gprev[j] - g_dist);
@@ -203,23 +164,16 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
         gd_sum += o_d.v[j];
         T[j] *= keep;
         gprev[j] = g_dist;
-        zc[j] = zn;
+        zc[j] = s.zn;
       }
       if (g_raw_logits && !last) stv<PX>(elems<ST>(g_raw_logits) + ((long)b * (N - 1) + n) * a.HW + pix, o_l);
       if (MIX && g_raw_sigma) stv<PX>(elems<ST>(g_raw_sigma) + ((long)b * N + n) * a.HW + pix, o_s);
       if (g_dl && a.dense) stv<PX>(g_dl + ((long)b * N + n) * a.HW + pix, o_d);
-      dv = dn;
+      dv = q.dn;
     }
-    if (reduce) {
-      const float v = wave_sum_hi(gd_sum);
-      if (lane == kWave - 1) lds_add(&red[n], v);
-    }
+    if (reduce) block_partials_add(red, n, gd_sum);
   }
-  if (reduce) {
-    __syncthreads();
-    float* dst = partials + ((long)b * gridDim.x + blockIdx.x) * N;
-    for (int i = threadIdx.x; i < N; i += kBlock) dst[i] = red[i];
-  }
+  if (reduce) block_partials_store(red, partials, b, N);
 }
 
 }  // namespace pd
@@ -233,11 +187,9 @@ extern "C" int pd_plade_tail_fwd(int B, int N, int H, int W, int flags, const fl
   PD_REQUIRE(logits && dists && disp && depth && stash, "NULL output");
   PD_REQUIRE(!(flags & PD_TAIL_MIXTURE) || sigma, "mixture needs the sigma output");
   const PladeArgs a = plade_args(N, H, W, flags, raw_logits, raw_sigma, disp_layered, ray_norm);
-  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
-  const int px = tail_px(H, W, {a.dense ? disp_layered : nullptr, ray_norm, dists, disp, depth, stash},
-                         {raw_logits, raw_sigma, logits, sigma}, bf16);
-  dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  PD_PLADE_DISPATCH(plade_fwd_kernel, bf16, px, a.mix, grid, 0, (hipStream_t)stream, a, logits, dists, sigma, disp, depth, stash);
+  const TailLaunch t = tail_launch(B, H, W, flags, 0, {a.dense ? disp_layered : nullptr, ray_norm, dists, disp, depth, stash},
+                                   {raw_logits, raw_sigma, logits, sigma});
+  PD_PLADE_DISPATCH(plade_fwd_kernel, t.bf16, t.px, a.mix, t.grid, 0, (hipStream_t)stream, a, logits, dists, sigma, disp, depth, stash);
   return check_launch("plade_fwd_kernel");
 }
 
@@ -247,10 +199,9 @@ extern "C" int pd_plade_tail_layers(int B, int N, int H, int W, int flags, const
   if (int rc = plade_validate(B, N, H, W, flags, raw_logits, raw_sigma, disp_layered, ray_norm)) return rc;
   PD_REQUIRE(stash && (pi || probability), "NULL pointer");
   const PladeArgs a = plade_args(N, H, W, flags, raw_logits, raw_sigma, disp_layered, ray_norm);
-  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
-  const int px = tail_px(H, W, {a.dense ? disp_layered : nullptr, ray_norm, stash, pi, probability}, {raw_logits, raw_sigma}, bf16);
-  dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
-  PD_PLADE_DISPATCH(plade_layers_kernel, bf16, px, a.mix, grid, 0, (hipStream_t)stream, a, stash, pi, probability);
+  const TailLaunch t = tail_launch(B, H, W, flags, 0, {a.dense ? disp_layered : nullptr, ray_norm, stash, pi, probability},
+                                   {raw_logits, raw_sigma});
+  PD_PLADE_DISPATCH(plade_layers_kernel, t.bf16, t.px, a.mix, t.grid, 0, (hipStream_t)stream, a, stash, pi, probability);
   return check_launch("plade_layers_kernel");
 }
 
@@ -266,17 +217,12 @@ extern "C" int pd_plade_tail_bwd(int B, int N, int H, int W, int flags, const fl
   const bool reduce = g_disp_layered && !a.dense;
   PD_REQUIRE(!reduce || workspace, "per-plane disparity gradient needs the workspace (pd_decoder_tail_bwd_workspace_floats)");
   PD_REQUIRE((size_t)N * sizeof(float) <= 64 * 1024, "too many planes");
-  const bool bf16 = (flags & PD_TAIL_BF16) != 0;
-  const int px = tail_px(H, W, {a.dense ? disp_layered : nullptr, ray_norm, stash, disp, g_dists, g_disp, g_depth,
-                                a.dense ? g_disp_layered : nullptr},
-                         {raw_logits, raw_sigma, g_logits, g_sigma, g_raw_logits, g_raw_sigma}, bf16);
-  dim3 grid(ceil_div(ceil_div(H * W, px), kBlock), B);
+  const TailLaunch t = tail_launch(B, H, W, flags, 0, {a.dense ? disp_layered : nullptr, ray_norm, stash, disp, g_dists, g_disp,
+                                                       g_depth, a.dense ? g_disp_layered : nullptr},
+                                   {raw_logits, raw_sigma, g_logits, g_sigma, g_raw_logits, g_raw_sigma});
   const size_t shmem = reduce ? (size_t)N * sizeof(float) : 0;
-  PD_PLADE_DISPATCH(plade_bwd_kernel, bf16, px, a.mix, grid, shmem, (hipStream_t)stream, a, stash, disp, g_logits, g_dists, g_sigma,
-                    g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
+  PD_PLADE_DISPATCH(plade_bwd_kernel, t.bf16, t.px, a.mix, t.grid, shmem, (hipStream_t)stream, a, stash, disp, g_logits, g_dists,
+                    g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_disp_layered, workspace);
   if (int rc = check_launch("plade_bwd_kernel")) return rc;
-  if (reduce) {
-    return reduce_partials(workspace, g_disp_layered, (int)grid.x, N, B, (hipStream_t)stream);
-  }
-  return 0;
+  return reduce ? reduce_partials(workspace, g_disp_layered, (int)t.grid.x, N, B, (hipStream_t)stream) : 0;
 }

@@ -32,6 +32,96 @@ def _storage_grad(name, g, dtype):
         raise TypeError("%s must be %s, got %s" % (name, dtype, g.dtype))
     return g
 
+
+def _decoder_operands(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_loss, grad=True):
+    """(flags, form, raw_sigma | None, padding_mask, plane) of a decoder tail, training or inference: the storage flag from the conv
+    outputs' dtype, ``disp_layered`` and ``padding_mask`` each in its own form (rows from the strides only: this tail takes no
+    promise).  ``grad=False``: a forward-only caller, whose ``plane`` is contiguous and carries no autograd path."""
+    B, N, H, W = raw_logits.shape
+    form, plane = PF.disp_operand(disp_layered, B, N, H, W, grad=grad)
+    flags = _storage_flag(raw_logits, raw_sigma, use_mixture_loss) | _DISP_FLAG[form] | (C.PD_TAIL_MIXTURE if use_mixture_loss else 0)
+    if padding_mask is not None:
+        mask_form, padding_mask = PF.mask_operand(padding_mask, B, N, H, W)
+        flags |= C.PD_TAIL_MASK_ROWS if mask_form == PF.ROWS else 0
+    return flags, form, (raw_sigma if use_mixture_loss else None), padding_mask, plane
+
+
+def _plade_operands(raw_logits, raw_sigma, disp_layered, ray_norm, use_mixture_loss, grad=True):
+    """(flags, raw_sigma | None, plane, ray_norm) of a PladeNet tail, training or inference (no row form: ``row_views=False``)."""
+    B, Nm1, H, W = raw_logits.shape
+    form, plane = PF.disp_operand(disp_layered, B, Nm1 + 1, H, W, grad=grad, row_views=False)
+    flags = _storage_flag(raw_logits, raw_sigma, use_mixture_loss) | _DISP_FLAG[form] | (C.PD_TAIL_MIXTURE if use_mixture_loss else 0)
+    if ray_norm is None:
+        ray_norm = camera_ray_norm(H, W, raw_logits.device)
+    return flags, (raw_sigma if use_mixture_loss else None), plane, ray_norm
+
+
+def _checked(flags, N, raw_logits, raw_sigma, disp_layered, name, fourth):
+    """A tail's operands as its entry points take them: on the GPU, in the shapes ``flags`` announce, contiguous.  ``fourth`` is the
+    decoder tail's ``padding_mask`` (may be None) or the PladeNet tail's ``ray_norm``, as ``name`` says."""
+    B, _, H, W = raw_logits.shape
+    st = raw_logits.dtype   # storage type of logits / sigma and their gradients (_storage_flag checked it: PD_TAIL_BF16)
+    C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
+    if flags & C.PD_TAIL_MIXTURE:
+        C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
+    C.require_gpu_tensor("disp_layered", disp_layered, (B, N, H, W) if flags & C.PD_TAIL_DISP_DENSE else
+                         (B, N, H) if flags & C.PD_TAIL_DISP_ROWS else (B, N))
+    if fourth is not None:
+        C.require_gpu_tensor(name, fourth, (H, W) if name == "ray_norm" else
+                             (B, N, H) if flags & C.PD_TAIL_MASK_ROWS else (B, N, H, W))
+    return tuple(map(_contig, (raw_logits, raw_sigma, disp_layered, fourth)))
+
+
+def _layers_of(entry, N, flags, operands, stash):
+    """The ``layers(want_pi=True, want_probability=True)`` of a tail, training or inference: ``(pi, probability)``, fp32 [B,N,H,W]
+    (with bf16 conv outputs too), materialised on demand from the stash by ``entry`` (pd_decoder_tail_layers /
+    pd_plade_tail_layers) — no gradient: nothing in the reference's losses reads them.  ``operands``: the entry point's inputs
+    in its order, ``raw_logits`` first; they are detached and made contiguous when ``layers`` is called.  ``layers.stash`` is what
+    pd_*_tail_fwd wrote (the inference kernels write the same bits)."""
+    B, _, H, W = operands[0].shape
+    dev = operands[0].device
+
+    def layers(want_pi=True, want_probability=True):
+        lib = C.load()
+        with torch.no_grad():
+            pi = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_pi else None
+            prob = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_probability else None
+            ins = [None if t is None else _contig(t.detach()) for t in operands]
+            with C.on_device(dev):
+                C.check(getattr(lib, entry)(B, N, H, W, flags, *map(C.ptr, ins), C.ptr(stash), C.ptr(pi), C.ptr(prob),
+                                            C.stream_handle(dev)), entry)
+        return pi, prob
+
+    layers.stash = stash
+    return layers
+
+
+def _needs(ctx):
+    """Which of (raw_logits, raw_sigma, disp_layered) a tail's backward owes a gradient (raw_sigma: with the mixture only)."""
+    return ctx.needs_input_grad[0], ctx.needs_input_grad[1] and bool(ctx.flags & C.PD_TAIL_MIXTURE), ctx.needs_input_grad[2]
+
+
+def _grad_buffers(lib, needs, raw_logits, raw_sigma, disp_layered, N, own_reduction):
+    """What a tail's backward writes: (g_raw_logits, g_raw_sigma, g_disp_layered, workspace), each None where ``needs`` does not
+    want it.  The workspace serves the per-plane form's reduction only: ``own_reduction`` = the dense form (nothing to reduce) or
+    the row form (reduced inside its kernel)."""
+    need_l, need_s, need_d = needs
+    B, _, H, W = raw_logits.shape
+    ws = None
+    if need_d and not own_reduction:
+        ws = torch.empty(lib.pd_decoder_tail_bwd_workspace_floats(B, N, H, W), device=raw_logits.device, dtype=torch.float32)
+    return (torch.empty_like(raw_logits) if need_l else None, torch.empty_like(raw_sigma) if need_s else None,
+            torch.empty_like(disp_layered) if need_d else None, ws)
+
+
+def _upstream(mix, dtype, g_logits, g_sigma, *fp32):
+    """A tail's upstream gradients, contiguous: g_logits / g_sigma in the storage dtype (g_sigma only with the mixture), then
+    the fp32 ones."""
+    g = tuple(map(_contig, (g_logits, g_sigma if mix else None) + fp32))
+    _storage_grad("g_logits", g[0], dtype)
+    _storage_grad("g_sigma", g[1], dtype)
+    return g
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Decoder tail (SURVEY.md 8f rank 1)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -44,15 +134,9 @@ class _DecoderTail(torch.autograd.Function):
         B, N, H, W = raw_logits.shape
         mix = bool(flags & C.PD_TAIL_MIXTURE)
         ctx.link = link
-        st = raw_logits.dtype   # storage type of logits / sigma and their gradients (decoder_tail checked it: PD_TAIL_BF16)
-        C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
-        if mix:
-            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
-        C.require_gpu_tensor("disp_layered", disp_layered, (B, N, H, W) if flags & C.PD_TAIL_DISP_DENSE else
-                             (B, N, H) if flags & C.PD_TAIL_DISP_ROWS else (B, N))
-        if padding_mask is not None:
-            C.require_gpu_tensor("padding_mask", padding_mask, (B, N, H) if flags & C.PD_TAIL_MASK_ROWS else (B, N, H, W))
-        raw_logits, raw_sigma, disp_layered, padding_mask = map(_contig, (raw_logits, raw_sigma, disp_layered, padding_mask))
+        st = raw_logits.dtype
+        raw_logits, raw_sigma, disp_layered, padding_mask = _checked(flags, N, raw_logits, raw_sigma, disp_layered, "padding_mask",
+                                                                       padding_mask)
         dev = raw_logits.device
         new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)  # noqa: E731
         logits = new(B, N, H, W, dtype=st) if padding_mask is not None else None
@@ -84,8 +168,8 @@ class _DecoderTail(torch.autograd.Function):
         B, N, H, W = raw_logits.shape
         flags = ctx.flags
         mix = bool(flags & C.PD_TAIL_MIXTURE)
-        need_l, need_s, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and mix, ctx.needs_input_grad[2]
-        if not (need_l or need_s or need_d):
+        need_l, need_s, need_d = needs = _needs(ctx)
+        if not any(needs):
             return None, None, None, None, None, None
         link = ctx.link
         extra = None
@@ -111,16 +195,9 @@ class _DecoderTail(torch.autograd.Function):
                 return (g_logits if need_l else None), (g_sigma if need_s else None), None, None, None, None
             extra = (g_logits, g_sigma)
             g_logits, g_sigma, g_disp, g_depth = None, None, r_disp, r_depth
-        g_raw_logits = torch.empty_like(raw_logits) if need_l else None
-        g_raw_sigma = torch.empty_like(raw_sigma) if need_s else None
-        g_dl = torch.empty_like(disp_layered) if need_d else None
-        ws = None
-        if need_d and not (flags & (C.PD_TAIL_DISP_DENSE | C.PD_TAIL_DISP_ROWS)):   # (the row form reduces inside its kernel)
-            ws = torch.empty(lib.pd_decoder_tail_bwd_workspace_floats(B, N, H, W), device=raw_logits.device,
-                             dtype=torch.float32)
-        g_logits, g_sigma, g_disp, g_depth = map(_contig, (g_logits, g_sigma if mix else None, g_disp, g_depth))
-        _storage_grad("g_logits", g_logits, raw_logits.dtype)
-        _storage_grad("g_sigma", g_sigma, raw_logits.dtype)
+        g_raw_logits, g_raw_sigma, g_dl, ws = _grad_buffers(lib, needs, raw_logits, raw_sigma, disp_layered, N,
+                                                            flags & (C.PD_TAIL_DISP_DENSE | C.PD_TAIL_DISP_ROWS))
+        g_logits, g_sigma, g_disp, g_depth = _upstream(mix, raw_logits.dtype, g_logits, g_sigma, g_disp, g_depth)
         with C.on_device(raw_logits.device), _timed("tail_bwd"):
             C.check(lib.pd_decoder_tail_bwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(padding_mask),
                                             C.ptr(disp_layered), C.ptr(stash), C.ptr(disp), C.ptr(g_logits),
@@ -158,13 +235,8 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     per-plane scalars AND for the row form — row-view disparities and / or a row-view mask, the reference's default 49 xy + 14 xz
     planes as ``plane_geometry`` returns them.  A dense map or a per-pixel mask gets no link (two kernels, the same results).
     """
-    B, N, H, W = raw_logits.shape
-    bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
-    form, plane = PF.disp_operand(disp_layered, B, N, H, W)   # (rows from the strides only: this tail takes no promise)
-    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | bf16 | _DISP_FLAG[form]
-    if padding_mask is not None:
-        mask_form, padding_mask = PF.mask_operand(padding_mask, B, N, H, W)
-        flags |= C.PD_TAIL_MASK_ROWS if mask_form == PF.ROWS else 0
+    flags, form, raw_sigma, padding_mask, plane = _decoder_operands(raw_logits, raw_sigma, padding_mask, disp_layered,
+                                                                    use_mixture_loss)
     # fuse_sweep_backward: the caller's promise that logits / sigma feed (with gradient) exactly ONE plane sweep — the trainer's
     # single-view pred_novel_images — whose backward kernel then applies this tail's backward too (TailLink).  Sweeps are
     # counted (a second one, or one the fused form does not serve, switches the fusion off); any OTHER differentiable consumer
@@ -176,25 +248,13 @@ def decoder_tail(raw_logits, raw_sigma, padding_mask, disp_layered, use_mixture_
     # map or a per-pixel mask does not.
     link = TailLink(None, None, None) if (fuse_sweep_backward and use_mixture_loss and form != PF.DENSE and
                                            (padding_mask is None or flags & C.PD_TAIL_MASK_ROWS)
-                                           and not bf16 and torch.is_grad_enabled()) else None
-    logits, sigma, disp, depth, stash = _DecoderTail.apply(raw_logits, raw_sigma if use_mixture_loss else None, plane,
-                                                           padding_mask, flags, link)
+                                           and not flags & C.PD_TAIL_BF16 and torch.is_grad_enabled()) else None
+    logits, sigma, disp, depth, stash = _DecoderTail.apply(raw_logits, raw_sigma, plane, padding_mask, flags, link)
     if link is not None:
         logits._pd_tail_link = link
         sigma._pd_tail_link = link
 
-    def layers(want_pi=True, want_probability=True):
-        lib = C.load()
-        with torch.no_grad():
-            pi = torch.empty_like(raw_logits, dtype=torch.float32) if want_pi else None     # (fp32 with bf16 conv outputs too)
-            prob = torch.empty_like(raw_logits, dtype=torch.float32) if want_probability else None
-            rl, rs, pm = map(_contig, (raw_logits.detach(), raw_sigma.detach() if use_mixture_loss else None, padding_mask))
-            with C.on_device(raw_logits.device):
-                C.check(lib.pd_decoder_tail_layers(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pm), C.ptr(stash),
-                                                   C.ptr(pi), C.ptr(prob), C.stream_handle(raw_logits.device)),
-                        "pd_decoder_tail_layers")
-        return pi, prob
-
+    layers = _layers_of("pd_decoder_tail_layers", raw_logits.shape[1], flags, (raw_logits, raw_sigma, padding_mask), stash)
     return logits, (sigma if use_mixture_loss else None), disp, depth, layers
 
 
@@ -207,13 +267,8 @@ class _PladeTail(torch.autograd.Function):
         B, Nm1, H, W = raw_logits.shape
         N = Nm1 + 1
         mix = bool(flags & C.PD_TAIL_MIXTURE)
-        st = raw_logits.dtype   # storage type of logits / sigma and their gradients (plade_tail checked it: PD_TAIL_BF16)
-        C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
-        if mix:
-            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
-        C.require_gpu_tensor("disp_layered", disp_layered, (B, N, H, W) if flags & C.PD_TAIL_DISP_DENSE else (B, N))
-        C.require_gpu_tensor("ray_norm", ray_norm, (H, W))
-        raw_logits, raw_sigma, disp_layered, ray_norm = map(_contig, (raw_logits, raw_sigma, disp_layered, ray_norm))
+        st = raw_logits.dtype
+        raw_logits, raw_sigma, disp_layered, ray_norm = _checked(flags, N, raw_logits, raw_sigma, disp_layered, "ray_norm", ray_norm)
         dev = raw_logits.device
         new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=dev, dtype=dtype)  # noqa: E731
         logits, dists = new(B, N, H, W, dtype=st), new(B, N - 1, H, W)
@@ -238,19 +293,13 @@ class _PladeTail(torch.autograd.Function):
         B, Nm1, H, W = raw_logits.shape
         N = Nm1 + 1
         flags = ctx.flags
-        mix = bool(flags & C.PD_TAIL_MIXTURE)
-        need_l, need_s, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and mix, ctx.needs_input_grad[2]
-        if not (need_l or need_s or need_d):
+        needs = _needs(ctx)
+        if not any(needs):
             return None, None, None, None, None, None
-        g_raw_logits = torch.empty_like(raw_logits) if need_l else None
-        g_raw_sigma = torch.empty_like(raw_sigma) if need_s else None
-        g_dl = torch.empty_like(disp_layered) if need_d else None
-        ws = None
-        if need_d and not (flags & C.PD_TAIL_DISP_DENSE):
-            ws = torch.empty(lib.pd_decoder_tail_bwd_workspace_floats(B, N, H, W), device=raw_logits.device, dtype=torch.float32)
-        g_logits, g_dists, g_sigma, g_disp, g_depth = map(_contig, (g_logits, g_dists, g_sigma if mix else None, g_disp, g_depth))
-        _storage_grad("g_logits", g_logits, raw_logits.dtype)
-        _storage_grad("g_sigma", g_sigma, raw_logits.dtype)
+        g_raw_logits, g_raw_sigma, g_dl, ws = _grad_buffers(lib, needs, raw_logits, raw_sigma, disp_layered, N,
+                                                            flags & C.PD_TAIL_DISP_DENSE)
+        g_logits, g_sigma, g_dists, g_disp, g_depth = _upstream(bool(flags & C.PD_TAIL_MIXTURE), raw_logits.dtype, g_logits,
+                                                                g_sigma, g_dists, g_disp, g_depth)
         with C.on_device(raw_logits.device):
             C.check(lib.pd_plade_tail_bwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(disp_layered),
                                           C.ptr(ray_norm), C.ptr(stash), C.ptr(disp), C.ptr(g_logits), C.ptr(g_dists),
@@ -290,26 +339,10 @@ def plade_tail(raw_logits, raw_sigma, disp_layered, ray_norm=None, use_mixture_l
     rule of ``decoder_tail``: ``logits`` / ``sigma`` and the conv outputs' gradients are bf16, ``dists`` and the rest fp32.
     This tail has no row form: a row view (``plane_geometry``'s ``disp_layered``, ``stride(3) == 0``) is materialised to the dense
     map by ``_contig`` — correct, and no faster than a dense map."""
-    B, Nm1, H, W = raw_logits.shape
-    N = Nm1 + 1
-    bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
-    form, plane = PF.disp_operand(disp_layered, B, N, H, W, row_views=False)
-    flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | _DISP_FLAG[form] | bf16
-    if ray_norm is None:
-        ray_norm = camera_ray_norm(H, W, raw_logits.device)
-    logits, dists, sigma, disp, depth, stash = _PladeTail.apply(raw_logits, raw_sigma if use_mixture_loss else None, plane,
-                                                               ray_norm, flags)
+    flags, raw_sigma, plane, ray_norm = _plade_operands(raw_logits, raw_sigma, disp_layered, ray_norm, use_mixture_loss)
+    logits, dists, sigma, disp, depth, stash = _PladeTail.apply(raw_logits, raw_sigma, plane, ray_norm, flags)
 
-    def layers(want_pi=True, want_probability=True):
-        lib = C.load()
-        rl, rs, pl = _contig(raw_logits.detach()), _contig(raw_sigma.detach()) if use_mixture_loss else None, _contig(plane.detach())
-        pi = torch.empty(B, N, H, W, device=rl.device, dtype=torch.float32) if want_pi else None
-        prob = torch.empty(B, N, H, W, device=rl.device, dtype=torch.float32) if want_probability else None
-        with C.on_device(rl.device):
-            C.check(lib.pd_plade_tail_layers(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pl), C.ptr(ray_norm), C.ptr(stash),
-                                             C.ptr(pi), C.ptr(prob), C.stream_handle(rl.device)), "pd_plade_tail_layers")
-        return pi, prob
-
+    layers = _layers_of("pd_plade_tail_layers", raw_logits.shape[1] + 1, flags, (raw_logits, raw_sigma, plane, ray_norm), stash)
     return logits, dists, (sigma if use_mixture_loss else None), disp, depth, layers
 
 
@@ -363,22 +396,14 @@ def decoder_tail_inference(raw_logits, raw_sigma, padding_mask, disp_layered, us
     ``decoder_tail`` is the differentiable operator."""
     want = _infer_want(want)
     B, N, H, W = raw_logits.shape
-    bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
+    _storage_flag(raw_logits, raw_sigma, use_mixture_loss)   # (a wrong dtype is reported before anything else)
     _infer_no_grad("decoder_tail", raw_logits=raw_logits, raw_sigma=raw_sigma if use_mixture_loss else None,
                    padding_mask=padding_mask, disp_layered=disp_layered)
-    st = raw_logits.dtype
-    C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
     with torch.no_grad():
-        form, plane = PF.disp_operand(disp_layered, B, N, H, W, grad=False)
-        flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | bf16 | _DISP_FLAG[form]
-        if padding_mask is not None:
-            mask_form, padding_mask = PF.mask_operand(padding_mask, B, N, H, W)
-            flags |= C.PD_TAIL_MASK_ROWS if mask_form == PF.ROWS else 0
-            C.require_gpu_tensor("padding_mask", padding_mask, (B, N, H) if flags & C.PD_TAIL_MASK_ROWS else (B, N, H, W))
-        if use_mixture_loss:
-            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
-        C.require_gpu_tensor("disp_layered", plane, (B, N, H, W) if form == PF.DENSE else (B, N, H) if form == PF.ROWS else (B, N))
-        rl, rs, pm, dl = map(_contig, (raw_logits.detach(), raw_sigma.detach() if use_mixture_loss else None, padding_mask, plane))
+        flags, _, raw_sigma, padding_mask, plane = _decoder_operands(raw_logits, raw_sigma, padding_mask, disp_layered,
+                                                                     use_mixture_loss, grad=False)
+        rl, rs, dl, pm = _checked(flags, N, raw_logits.detach(), None if raw_sigma is None else raw_sigma.detach(), plane,
+                                  "padding_mask", padding_mask)
         dev = rl.device
         disp, depth, conf, index, best, stash = _infer_outputs(B, H, W, dev, want, 2)
         lib = C.load()
@@ -386,18 +411,8 @@ def decoder_tail_inference(raw_logits, raw_sigma, padding_mask, disp_layered, us
             C.check(lib.pd_decoder_tail_infer(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pm), C.ptr(dl), C.ptr(disp),
                                               C.ptr(depth), C.ptr(conf), C.ptr(index), C.ptr(best), C.ptr(stash),
                                               C.stream_handle(dev)), "pd_decoder_tail_infer")
-
-    def layers(want_pi=True, want_probability=True):
-        with torch.no_grad():
-            pi = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_pi else None
-            prob = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_probability else None
-            with C.on_device(dev):
-                C.check(lib.pd_decoder_tail_layers(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pm), C.ptr(stash),
-                                                   C.ptr(pi), C.ptr(prob), C.stream_handle(dev)), "pd_decoder_tail_layers")
-        return pi, prob
-
-    layers.stash = stash   # (what pd_*_tail_fwd would have written: kept for layers(), readable for a caller that wants it)
-    return InferenceTail(disp, depth, conf, index, best, layers if stash is not None else None)
+    layers = _layers_of("pd_decoder_tail_layers", N, flags, (rl, rs, pm), stash) if stash is not None else None
+    return InferenceTail(disp, depth, conf, index, best, layers)
 
 
 def plade_tail_inference(raw_logits, raw_sigma, disp_layered, ray_norm=None, use_mixture_loss=True,
@@ -409,22 +424,14 @@ def plade_tail_inference(raw_logits, raw_sigma, disp_layered, ray_norm=None, use
     want = _infer_want(want)
     B, Nm1, H, W = raw_logits.shape
     N = Nm1 + 1
-    bf16 = _storage_flag(raw_logits, raw_sigma, use_mixture_loss)
+    _storage_flag(raw_logits, raw_sigma, use_mixture_loss)   # (a wrong dtype is reported before anything else)
     _infer_no_grad("plade_tail", raw_logits=raw_logits, raw_sigma=raw_sigma if use_mixture_loss else None,
                    disp_layered=disp_layered, ray_norm=ray_norm)
-    st = raw_logits.dtype
-    C.require_gpu_tensor("raw_logits", raw_logits, dtype=st)
     with torch.no_grad():
-        form, plane = PF.disp_operand(disp_layered, B, N, H, W, grad=False, row_views=False)
-        flags = (C.PD_TAIL_MIXTURE if use_mixture_loss else 0) | _DISP_FLAG[form] | bf16
-        if ray_norm is None:
-            ray_norm = camera_ray_norm(H, W, raw_logits.device)
-        if use_mixture_loss:
-            C.require_gpu_tensor("raw_sigma", raw_sigma, (B, N, H, W), dtype=st)
-        C.require_gpu_tensor("disp_layered", plane, (B, N, H, W) if form == PF.DENSE else (B, N))
-        C.require_gpu_tensor("ray_norm", ray_norm, (H, W))
-        rl, rs, dl, ray = map(_contig, (raw_logits.detach(), raw_sigma.detach() if use_mixture_loss else None, plane,
-                                        ray_norm.detach()))
+        flags, raw_sigma, plane, ray_norm = _plade_operands(raw_logits, raw_sigma, disp_layered, ray_norm, use_mixture_loss,
+                                                            grad=False)
+        rl, rs, dl, ray = _checked(flags, N, raw_logits.detach(), None if raw_sigma is None else raw_sigma.detach(), plane,
+                                   "ray_norm", ray_norm.detach())
         dev = rl.device
         disp, depth, conf, index, best, stash = _infer_outputs(B, H, W, dev, want, 1)
         lib = C.load()
@@ -432,18 +439,8 @@ def plade_tail_inference(raw_logits, raw_sigma, disp_layered, ray_norm=None, use
             C.check(lib.pd_plade_tail_infer(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(dl), C.ptr(ray), C.ptr(disp),
                                             C.ptr(depth), C.ptr(conf), C.ptr(index), C.ptr(best), C.ptr(stash),
                                             C.stream_handle(dev)), "pd_plade_tail_infer")
-
-    def layers(want_pi=True, want_probability=True):
-        with torch.no_grad():
-            pi = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_pi else None
-            prob = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_probability else None
-            with C.on_device(dev):
-                C.check(lib.pd_plade_tail_layers(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(dl), C.ptr(ray), C.ptr(stash),
-                                                 C.ptr(pi), C.ptr(prob), C.stream_handle(dev)), "pd_plade_tail_layers")
-        return pi, prob
-
-    layers.stash = stash   # (what pd_*_tail_fwd would have written: kept for layers(), readable for a caller that wants it)
-    return InferenceTail(disp, depth, conf, index, best, layers if stash is not None else None)
+    layers = _layers_of("pd_plade_tail_layers", N, flags, (rl, rs, dl, ray), stash) if stash is not None else None
+    return InferenceTail(disp, depth, conf, index, best, layers)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -83,10 +83,6 @@ def _gate_closed(rs):
     return (rs.float() <= -12.0) | (rs.float() >= 30.0)
 
 
-def _stash_of(layers):
-    return dict(zip(layers.__code__.co_freevars, (c.cell_contents for c in layers.__closure__)))["stash"]
-
-
 def _levels(B, N, W, g):
     lv = torch.arange(N, dtype=torch.float32)[None, :, None, None] + torch.rand(B, N, 1, 1, generator=g) - 0.5
     return (300.0 * (W / 640.0) * (2.0 / 300.0) ** (lv / max(N - 1, 1))).to(DEV)
@@ -118,7 +114,7 @@ def _decoder_route(rl_b, rs_b, pm, lv, ups, mix, dense, widen):
         grads.append(cast(gs))
     torch.autograd.backward(outs, grads)
     return dict(a=a, logits=logits.detach(), sigma=sigma.detach() if mix else None, disp=disp.detach(), depth=depth.detach(),
-                stash=_stash_of(layers), layers=layers, g_rl=a.grad, g_rs=s.grad if mix else None, g_dl=leaf.grad)
+                stash=layers.stash, layers=layers, g_rl=a.grad, g_rs=s.grad if mix else None, g_dl=leaf.grad)
 
 
 def _decoder_case(shape, mix, mask, dense, offset=False, seed=0):

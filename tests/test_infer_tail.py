@@ -28,10 +28,6 @@ DISP_FORMS = ("plane", "dense", "rows")
 MASK_FORMS = (None, "dense", "rows")
 
 
-def _stash_of(layers):
-    return dict(zip(layers.__code__.co_freevars, (c.cell_contents for c in layers.__closure__)))["stash"]
-
-
 def _levels(B, N, W, g):
     """Per-plane disparities as the decoders space them (decreasing with the plane index), jittered per image."""
     lv = torch.arange(N, dtype=torch.float32)[None, :, None, None] + 0.5 * (torch.rand(B, N, 1, 1, generator=g) - 0.5)
@@ -111,7 +107,7 @@ def _run_decoder(shape, disp_form, mask_form, mix, bf16, seed=0):
         res = ops.decoder_tail_inference(rl, rs if mix else None, pm, dl, use_mixture_loss=mix, want=ALL)
     want = oracle.decoder_tail(rl.double().cpu(), rs.double().cpu(), dense_pm.double().cpu(), dense_dl.double().cpu(), shape[3],
                                use_mixture_loss=mix)
-    _check(res, disp, depth, _stash_of(layers), layers(False, True)[1], want["probability"], dense_dl)
+    _check(res, disp, depth, layers.stash, layers(False, True)[1], want["probability"], dense_dl)
     return res
 
 
@@ -150,7 +146,7 @@ def test_decoder_tail_inference_on_the_reference_plane_set(mix, bf16):
     dense_dl, dense_pm = dl.contiguous(), pm.contiguous()
     want = oracle.decoder_tail(rl.double().cpu(), rs.double().cpu(), dense_pm.double().cpu(), dense_dl.double().cpu(), W,
                                use_mixture_loss=mix)
-    _check(res, disp, depth, _stash_of(layers), layers(False, True)[1], want["probability"], dense_dl)
+    _check(res, disp, depth, layers.stash, layers(False, True)[1], want["probability"], dense_dl)
     if mix:   # a masked plane has weight 0: never the best one
         assert bool((res.plane_index[:, :, :2] < 49).all())
 
@@ -217,7 +213,7 @@ def _run_plade(shape, disp_form, mix, bf16, seed=0):
         res = ops.plade_tail_inference(rl, rs if mix else None, dl, use_mixture_loss=mix, want=ALL)
     want = oracle.plade_tail(rl.double().cpu(), rs.double().cpu(), dense_dl.double().cpu(), W, ray.double().cpu()[None],
                              use_mixture_loss=mix)
-    _check(res, disp, depth, _stash_of(layers), layers(False, True)[1], want["probability"], dense_dl)
+    _check(res, disp, depth, layers.stash, layers(False, True)[1], want["probability"], dense_dl)
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
