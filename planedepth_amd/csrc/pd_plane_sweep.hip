@@ -411,7 +411,7 @@ static int validate(const pd_sweep_desc* d, const float* src, const float* logit
 }
 
 // What PD_IMPL_AUTO does with a second source row whose weight is fp32 noise of the reference's y round trip
-// (pd_rowshift_common.h: two_row_form): it is dropped when the weight is below PD_AUTO_ROW_EPS (0: never).  Decided by the
+// (pd_rowgeom.h: two_row_form): it is dropped when the weight is below PD_AUTO_ROW_EPS (0: never).  Decided by the
 // parity suite run under the modes (tests/test_gpu_parity.py: row_mode; profiles/r05_parity.md).  PD_ROW_EPS in the
 // environment (read once, diagnostics) overrides the compiled-in value.
 #ifndef PD_AUTO_ROW_EPS

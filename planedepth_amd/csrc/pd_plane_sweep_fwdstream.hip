@@ -29,7 +29,7 @@
 //   * PD_RENDER_PROB: the planes of a pixel arrive in order in one wave, so the transmittance is a register.
 //
 // Exactness.  The pairing "left tap of target xt on plane n = source column xt + k" is the row-stream backward's premise
-// (pd_rowshift_common.h: stream_ix, irregular_tol; NOTEBOOK.md 3.6.3): planes whose frac(s d) is closer than irregular_tol
+// (pd_rowgeom.h: stream_ix, irregular_tol; NOTEBOOK.md 3.6.3): planes whose frac(s d) is closer than irregular_tol
 // to an integer take a general per-pixel path (exact floor(ix) per pixel, dword loads), and so does the one segment per
 // plane that straddles column 0 under a negative shift (a 12-byte load that STARTS left of the row reads as zeros as a
 // whole).  Weights and samples are the reference's expressions in the row-shift forward's order.
@@ -63,86 +63,10 @@ constexpr int kFsSeg = 2 * kWave;      // target pixels per wave
 constexpr int kFsGuard = 4;            // zero cells on each side of the colour row
 constexpr int kFsThreadsMax = 1024;    // 16 waves: rows up to 2048 pixels
 
-typedef float v3f __attribute__((ext_vector_type(3)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v3f fs_load3(Rsrc r, unsigned byte_off) {
-  return __builtin_bit_cast(v3f, __builtin_amdgcn_raw_buffer_load_b96(r, (int)byte_off, 0, 0));
-}
-
-template <class T, int NROWS>
-struct FsTaps {   // the taps of one plane for the lane's two pixels: L[c .. c+2] per live source row
-  float l[NROWS][3], s[NROWS][3];
-  float dist[2];  // PD_RENDER_PROB: the decoder's inter-plane distances at the two TARGET pixels (trainer.py:587)
-};
-// bf16 storage: the raw 8 bytes of ONE load per tensor and row, four elements from the 4-byte-aligned column c or c - 1
-// (the parity of c = xt + k is the parity of k: wave-uniform); the three taps are picked and widened when the plane is reduced
-// (fs_taps), so the ring holds 2 VGPRs per tensor and row instead of 3.
-template <int NROWS>
-struct FsTaps<Bf16, NROWS> {
-  unsigned l[NROWS][2], s[NROWS][2];
-  float dist[2];
-};
-// Byte offset of the lane's tap load for source column c = xt0 + k (even xt0): fp32 at c, bf16 at the even column c - (k & 1).
+// Byte offset of the lane's tap load for source column c = xt0 + k (even xt0): fp32 at c, bf16 at the even column c - (k & 1)
+// (the parity of c is the parity of k: wave-uniform; stream_taps then picks elements 1 .. 3 of the four).
 template <class T> __device__ __forceinline__ unsigned fs_tap_off(int c, int k) {
   return sizeof(T) == 4 ? (unsigned)c << 2 : (unsigned)(c - (k & 1)) << 1;
-}
-template <int NROWS>
-__device__ __forceinline__ void fs_taps(const FsTaps<float, NROWS>& g, int, float (&l)[NROWS][3], float (&s)[NROWS][3]) {
-#pragma unroll
-  for (int r = 0; r < NROWS; ++r)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { l[r][i] = g.l[r][i]; s[r][i] = g.s[r][i]; }
-}
-__device__ __forceinline__ void bf16_taps3(const unsigned (&w)[2], bool odd, float (&t)[3]) {   // elements (0,1,2) or (1,2,3)
-  t[0] = odd ? bf16_hi(w[0]) : bf16_lo(w[0]);
-  t[1] = odd ? bf16_lo(w[1]) : bf16_hi(w[0]);
-  t[2] = odd ? bf16_hi(w[1]) : bf16_lo(w[1]);
-}
-template <int NROWS>
-__device__ __forceinline__ void fs_taps(const FsTaps<Bf16, NROWS>& g, int k, float (&l)[NROWS][3], float (&s)[NROWS][3]) {
-#pragma unroll
-  for (int r = 0; r < NROWS; ++r) { bf16_taps3(g.l[r], k & 1, l[r]); bf16_taps3(g.s[r], k & 1, s[r]); }
-}
-
-struct FsRow {    // workgroup-uniform
-  int b, y, yA, yB;
-  float wA, wB;
-};
-
-template <bool MIX, int NROWS>
-__device__ __forceinline__ void fs_issue(FsTaps<Bf16, NROWS>& g, const SweepArgs& a, const FsRow& r, int n, unsigned off, int HW) {
-  const Bf16* pl = plane_ptr_t(elems<Bf16>(a.logits) + (long)r.b * a.N * HW, n, HW);
-  auto ld = [&](const Bf16* row, unsigned (&w)[2]) {
-    const v2u v = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(row_rsrc_t(row, a.W), (int)off, 0, 0));
-    w[0] = v.x; w[1] = v.y;
-  };
-  ld(pl + (long)r.yA * a.W, g.l[0]);
-  if (NROWS == 2) ld(pl + (long)r.yB * a.W, g.l[NROWS - 1]);
-  if (MIX) {
-    const Bf16* ps = plane_ptr_t(elems<Bf16>(a.sigma) + (long)r.b * a.N * HW, n, HW);
-    ld(ps + (long)r.yA * a.W, g.s[0]);
-    if (NROWS == 2) ld(ps + (long)r.yB * a.W, g.s[NROWS - 1]);
-  }
-}
-template <bool MIX, int NROWS>
-__device__ __forceinline__ void fs_issue(FsTaps<float, NROWS>& g, const SweepArgs& a, const FsRow& r, int n, unsigned off, int HW) {
-  const float* pl = plane_ptr(a.logits + (long)r.b * a.N * HW, n, HW);
-  const v3f la = fs_load3(row_rsrc(pl + (long)r.yA * a.W, a.W), off);
-  g.l[0][0] = la.x; g.l[0][1] = la.y; g.l[0][2] = la.z;
-  if (NROWS == 2) {
-    const v3f lb = fs_load3(row_rsrc(pl + (long)r.yB * a.W, a.W), off);
-    g.l[NROWS - 1][0] = lb.x; g.l[NROWS - 1][1] = lb.y; g.l[NROWS - 1][2] = lb.z;
-  }
-  if (MIX) {
-    const float* ps = plane_ptr(a.sigma + (long)r.b * a.N * HW, n, HW);
-    const v3f sa = fs_load3(row_rsrc(ps + (long)r.yA * a.W, a.W), off);
-    g.s[0][0] = sa.x; g.s[0][1] = sa.y; g.s[0][2] = sa.z;
-    if (NROWS == 2) {
-      const v3f sb = fs_load3(row_rsrc(ps + (long)r.yB * a.W, a.W), off);
-      g.s[NROWS - 1][0] = sb.x; g.s[NROWS - 1][1] = sb.y; g.s[NROWS - 1][2] = sb.z;
-    }
-  }
 }
 
 // The lane's two pixels on a plane that does not qualify for the 12-byte form: exact floor(ix) per pixel, dword loads
@@ -157,7 +81,7 @@ __device__ __forceinline__ void fs_accumulate(FwdAcc& acc, RenderState& rs, floa
 }
 
 template <class T, bool MIX, int NROWS, bool RENDER>
-__device__ __forceinline__ void fs_general_plane(const SweepArgs& a, const FsRow& r, const float4* __restrict__ col, int n,
+__device__ __forceinline__ void fs_general_plane(const SweepArgs& a, const StreamRow& r, const float4* __restrict__ col, int n,
                                                  float sd, float xt0f, int HW, float Wm1, float rcpWm1, const float* t,
                                                  const float* ea, bool automask, FwdAcc* acc, RenderState* rs,
                                                  const float* dist) {
@@ -202,29 +126,15 @@ __device__ __forceinline__ void fs_stage_row(const SweepArgs& a, const RowSel& r
   const int CW = W + 2 * kFsGuard;
   const bool two = row.nrows == 2;
   const float* srcb = a.src + (long)b * 3 * HW;
-  auto blended = [&](int x) {   // source colour at column x of the (vertically blended) row; zero outside the row
-    float4 cc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (x >= 0 && x < W) {
-      const float* p = srcb + (long)row.yA * W + x;
-      cc = make_float4(p[0], p[HW], p[2 * HW], 0.0f);
-      if (two) {   // fl(B*wB + fl(A*wA)): the rounding the row-stream backward stages (its knife-edge note applies here too)
-        const float* q = srcb + (long)row.yB * W + x;
-        cc = make_float4(fmaf(q[0], row.wB, cc.x * row.wA), fmaf(q[HW], row.wB, cc.y * row.wA), fmaf(q[2 * HW], row.wB, cc.z * row.wA), 0.0f);
-      }
-    }
-    return cc;
-  };
   for (int cidx = tix; cidx < CW && y < a.H; cidx += nthr) {
     const int x = cidx - kFsGuard;
-    col[cidx] = blended(x);
+    col[cidx] = blended_colour(srcb, row, two, x, W, HW);
   }
-  const float tol = irregular_tol(W);
   for (int i = tix; i < N && y < a.H; i += nthr) {
     const float sd = staged_shift(a, b, i, y);
-    const float fl = floorf(sd), fr = sd - fl;
-    const bool inview = fabsf(sd) < (float)(W + 1);
-    const int irr = (inview && (fr < tol || fr > 1.0f - tol)) ? 1 : 0;
-    shift[i] = make_int2(__float_as_int(sd), (int)fl * 2 + irr);
+    ShiftClass c;
+    classify_shift(sd, W, c);
+    shift[i] = pack_shift(sd, c);
   }
 }
 
@@ -236,11 +146,7 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
                                                 float* __restrict__ stash) {
   constexpr int D = (NROWS == 1) ? (RENDER ? PD_FS_D1 - 1 : PD_FS_D1) : PD_FS_D2;   // (compositing: the ring also carries dists — one slot less keeps it out of scratch)
   const int W = a.W, N = a.N, HW = a.H * a.W;
-  FsRow r;
-  r.y = y;
-  r.b = b;
-  r.yA = row.yA; r.yB = (NROWS == 2) ? row.yB : row.yA;
-  r.wA = row.wA; r.wB = (NROWS == 2) ? row.wB : 0.0f;
+  const StreamRow r = make_stream_row<NROWS>(b, y, row);
   const bool automask = MIX ? AUTO : (bool)(a.flags & PD_AUTOMASK);
   const float Wm1 = (float)(W - 1), rcpWm1 = refined_rcp(Wm1);
   const float* srcb = a.src + (long)r.b * 3 * HW;
@@ -268,23 +174,24 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
   FwdAcc acc[2];
   RenderState rs[2];
   float dmax[2] = {-INFINITY, -INFINITY};   // fixed-reference softmax: largest exponent used so far
-  FsTaps<T, NROWS> g[D + 1];
+  StreamTaps<T, NROWS> g[D + 1];
+  float gdist[D + 1][2];   // PD_RENDER_PROB: the decoder's inter-plane distances at the two TARGET pixels (trainer.py:587), beside the ring
   int pn = 0;
   // A plane's staged shift is read from LDS ONE iteration before its tap loads are issued and kept in scalar registers until
   // the plane is reduced (one LDS read per iteration, off the critical path, instead of two round trips at the head of every
   // iteration).
   int sh_sd[D + 1], sh_kk[D + 1];          // wave-uniform (SGPRs): the shifts of the planes whose taps are in flight
   int2 sh_next = shift[0];       // LDS read in flight: the shift of the next plane to be prefetched
-  auto prefetch = [&](FsTaps<T, NROWS>& grp, int slot) {
+  auto prefetch = [&](StreamTaps<T, NROWS>& grp, int slot) {
     const int n = min(pn, N - 1);   // past the end: re-load the last plane (unused) — unconditional issue keeps the wait counts right
     sh_sd[slot] = __builtin_amdgcn_readfirstlane(sh_next.x);
     sh_kk[slot] = __builtin_amdgcn_readfirstlane(sh_next.y);
     sh_next = shift[min(pn + 1, N - 1)];
-    const int k = sh_kk[slot] >> 1;
-    fs_issue<MIX, NROWS>(grp, a, r, n, fs_tap_off<T>(xt0 + k, k), HW);
+    const int k = packed_k(sh_kk[slot]);
+    issue_taps<MIX, NROWS, 0>(grp, a, r, n, fs_tap_off<T>(xt0 + k, k), 0, W, HW);
     if (RENDER) {   // unshifted, coalesced: read where the pixels are, not where they sample (the last plane has none: alpha = 1)
       const float2 d2 = *reinterpret_cast<const float2*>(a.dists + ((long)r.b * (N - 1) + min(n, N - 2)) * HW + pix);
-      grp.dist[0] = d2.x; grp.dist[1] = d2.y;
+      gdist[slot][0] = d2.x; gdist[slot][1] = d2.y;
     }
     ++pn;
   };
@@ -294,22 +201,22 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
   // to 0).  Loads that start further left are dropped cleanly, those at >= 0 are exact.  (bf16: W is even, so no dword
   // straddles the row's end: the per-dword check drops exactly the columns >= W.)
   auto general_form = [&](int kk, int c0) {
-    if (sizeof(T) == 4) return (kk & 1) || (c0 < 0 && c0 + 2 * (kWave - 1) >= -3);
-    const int e0 = c0 - ((kk >> 1) & 1);
-    return (kk & 1) || (e0 < 0 && e0 + 2 * (kWave - 1) >= -4);
+    if (sizeof(T) == 4) return packed_irr(kk) || (c0 < 0 && c0 + 2 * (kWave - 1) >= -3);
+    const int e0 = c0 - (packed_k(kk) & 1);
+    return packed_irr(kk) || (e0 < 0 && e0 + 2 * (kWave - 1) >= -4);
   };
-  auto step = [&](const FsTaps<T, NROWS>& gq, int n, int slot, int next_slot) {
-    const float sd = __int_as_float(sh_sd[slot]);
+  auto step = [&](const StreamTaps<T, NROWS>& gq, int n, int slot, int next_slot) {
+    const float sd = packed_sd(sh_sd[slot]);
     const int kk = sh_kk[slot];
-    const int k = kk >> 1;
+    const int k = packed_k(kk);
     const int c0 = seg * kFsSeg + k;   // source column of the segment's first left tap (wave-uniform); lane i loads c0 + 2i ..
     if (general_form(kk, c0)) {
-      fs_general_plane<T, MIX, NROWS, RENDER>(a, r, col, n, sd, xt0f, HW, Wm1, rcpWm1, t, ea, automask, acc, rs, gq.dist);
+      fs_general_plane<T, MIX, NROWS, RENDER>(a, r, col, n, sd, xt0f, HW, Wm1, rcpWm1, t, ea, automask, acc, rs, gdist[slot]);
       return;
     }
     struct { float l[NROWS][3], s[NROWS][3]; float dist[2]; } grp;
-    fs_taps(gq, k, grp.l, grp.s);
-    grp.dist[0] = gq.dist[0]; grp.dist[1] = gq.dist[1];
+    stream_taps(gq, k & 1, grp.l, grp.s);
+    grp.dist[0] = gdist[slot][0]; grp.dist[1] = gdist[slot][1];
     const int cell = min(max(xt0 + k, -kFsGuard), W + 1) + kFsGuard;
     const float4 cv0 = col[cell], cv1 = col[cell + 1], cv2 = col[cell + 2];
     const float kf = (float)k;
@@ -343,12 +250,12 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
   for (int j = 0; j < D; ++j) prefetch(g[j], j);
   if (!RENDER) {   // the reference: plane 0's scaled logit at the lane's two pixels (when plane 0 takes the 12-byte form;
     const int2 sh0 = shift[0];   // otherwise the general path's rescaling accumulator sets it when it reduces that plane)
-    const float sd = __int_as_float(__builtin_amdgcn_readfirstlane(sh0.x));
-    const int kk = __builtin_amdgcn_readfirstlane(sh0.y), k = kk >> 1, c0 = seg * kFsSeg + k;
+    const float sd = packed_sd(__builtin_amdgcn_readfirstlane(sh0.x));
+    const int kk = __builtin_amdgcn_readfirstlane(sh0.y), k = packed_k(kk), c0 = seg * kFsSeg + k;
     if (!general_form(kk, c0)) {
       const float kf = (float)k;
       float g0l[NROWS][3], g0s[NROWS][3];
-      fs_taps(g[0], k, g0l, g0s);
+      stream_taps(g[0], k & 1, g0l, g0s);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const float xtf = xt0f + (float)i, xsf = xtf + kf;
@@ -390,8 +297,8 @@ __device__ __forceinline__ float fwdstream_body(const SweepArgs& a, const RowSel
     if (__builtin_amdgcn_ballot_w64(beyond) != 0) {   // rare: this wave again, every plane through the rescaling accumulator
       acc[0] = FwdAcc(); acc[1] = FwdAcc();
       for (int q = 0; q < N; ++q)
-        fs_general_plane<T, MIX, NROWS, RENDER>(a, r, col, q, __int_as_float(__builtin_amdgcn_readfirstlane(shift[q].x)), xt0f, HW, Wm1,
-                                             rcpWm1, t, ea, automask, acc, rs, g[0].dist);
+        fs_general_plane<T, MIX, NROWS, RENDER>(a, r, col, q, packed_sd(__builtin_amdgcn_readfirstlane(shift[q].x)), xt0f, HW, Wm1,
+                                             rcpWm1, t, ea, automask, acc, rs, gdist[0]);
     }
   }
   __builtin_amdgcn_s_setprio(0);   // (the rotating priority of the plane loop ends with it)

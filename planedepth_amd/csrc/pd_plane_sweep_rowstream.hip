@@ -79,12 +79,6 @@ constexpr int kSlots = 2;               // source slots per lane
 constexpr int kSeg = kWave * kSlots;    // slots per wave iteration
 constexpr int kStreamThreadsMax = 1024;
 
-typedef float v3f __attribute__((ext_vector_type(3)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v3f buf_load3(Rsrc r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(v3f, __builtin_amdgcn_raw_buffer_load_b96(r, (int)voff, (int)soff, PD_STREAM_LOAD_AUX));
-}
 __device__ __forceinline__ void buf_store1(Rsrc r, unsigned voff, unsigned soff, unsigned w) {   // bf16: one packed pair
   __builtin_amdgcn_raw_buffer_store_b32(w, r, (int)voff, (int)soff, PD_STREAM_STORE_AUX);
 }
@@ -170,74 +164,6 @@ __device__ __forceinline__ float4 col_at(const StreamLds& L, int i) {
   return L.col[i];
 }
 
-template <class T, int NROWS>
-struct StreamGroup {   // the taps of one (plane, segment) iteration: L[xs .. xs+2] per live source row
-  float l[NROWS][3], s[NROWS][3];
-};
-template <int NROWS>
-struct StreamGroup<Bf16, NROWS> {   // bf16: the raw 8 bytes at the even slot xs (elements xs .. xs+3), widened when reduced
-  unsigned l[NROWS][2], s[NROWS][2];
-};
-template <int NROWS>
-__device__ __forceinline__ StreamGroup<float, NROWS> stream_taps(const StreamGroup<float, NROWS>& g) { return g; }
-template <int NROWS>
-__device__ __forceinline__ StreamGroup<float, NROWS> stream_taps(const StreamGroup<Bf16, NROWS>& g) {
-  StreamGroup<float, NROWS> o;
-#pragma unroll
-  for (int r = 0; r < NROWS; ++r) {
-    o.l[r][0] = bf16_lo(g.l[r][0]); o.l[r][1] = bf16_hi(g.l[r][0]); o.l[r][2] = bf16_lo(g.l[r][1]);
-    o.s[r][0] = bf16_lo(g.s[r][0]); o.s[r][1] = bf16_hi(g.s[r][0]); o.s[r][2] = bf16_lo(g.s[r][1]);
-  }
-  return o;
-}
-
-struct StreamRow {     // workgroup-uniform
-  int b, y, yA, yB;
-  float wA, wB, wy;    // vertical weights of the two source rows; adjoint weight of the own row
-};
-
-template <bool MIX, int NROWS>
-__device__ __forceinline__ void stream_issue(StreamGroup<Bf16, NROWS>& g, const SweepArgs& a, const StreamRow& r, int n, int seg,
-                                             unsigned lane8, int HW, int ext = -1) {
-  const int Wx = ext < 0 ? a.W : ext;
-  const unsigned soff = (unsigned)seg * (kSeg * 2), voff = lane8 >> 1;   // (lane8: the fp32 form's offset, 8 bytes per lane)
-  auto ld = [&](const Bf16* row, unsigned (&w)[2]) {
-    const v2u v = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(row_rsrc_t(row, Wx), (int)voff, (int)soff, PD_STREAM_LOAD_AUX));
-    w[0] = v.x; w[1] = v.y;
-  };
-  const Bf16* pl = plane_ptr_t(elems<Bf16>(a.logits) + (long)r.b * a.N * HW, n, HW);
-  ld(pl + (long)r.yA * a.W, g.l[0]);
-  if (NROWS == 2) ld(pl + (long)r.yB * a.W, g.l[NROWS - 1]);
-  if (MIX) {
-    const Bf16* ps = plane_ptr_t(elems<Bf16>(a.sigma) + (long)r.b * a.N * HW, n, HW);
-    ld(ps + (long)r.yA * a.W, g.s[0]);
-    if (NROWS == 2) ld(ps + (long)r.yB * a.W, g.s[NROWS - 1]);
-  }
-}
-template <bool MIX, int NROWS>
-__device__ __forceinline__ void stream_issue(StreamGroup<float, NROWS>& g, const SweepArgs& a, const StreamRow& r, int n, int seg,
-                                             unsigned lane8, int HW, int ext = -1) {
-  // ext: the row descriptors' extent in floats (wave-uniform); 0 turns the item's loads into hardware no-ops that return zeros
-  const int Wx = ext < 0 ? a.W : ext;
-  const unsigned soff = (unsigned)seg * (kSeg * 4);
-  const float* pl = plane_ptr(a.logits + (long)r.b * a.N * HW, n, HW);
-  const v3f la = buf_load3(row_rsrc(pl + (long)r.yA * a.W, Wx), lane8, soff);
-  g.l[0][0] = la.x; g.l[0][1] = la.y; g.l[0][2] = la.z;
-  if (NROWS == 2) {
-    const v3f lb = buf_load3(row_rsrc(pl + (long)r.yB * a.W, Wx), lane8, soff);
-    g.l[NROWS - 1][0] = lb.x; g.l[NROWS - 1][1] = lb.y; g.l[NROWS - 1][2] = lb.z;
-  }
-  if (MIX) {
-    const float* ps = plane_ptr(a.sigma + (long)r.b * a.N * HW, n, HW);
-    const v3f sa = buf_load3(row_rsrc(ps + (long)r.yA * a.W, Wx), lane8, soff);
-    g.s[0][0] = sa.x; g.s[0][1] = sa.y; g.s[0][2] = sa.z;
-    if (NROWS == 2) {
-      const v3f sb = buf_load3(row_rsrc(ps + (long)r.yB * a.W, Wx), lane8, soff);
-      g.s[NROWS - 1][0] = sb.x; g.s[NROWS - 1][1] = sb.y; g.s[NROWS - 1][2] = sb.z;
-    }
-  }
-}
-
 // Gradient pair store of the lane's two slots.  bf16: one packed dword; `defer` (LDS, wave-uniform; bf16 only): lane 0 keeps its
 // fp32 pair there instead (its store is sent beyond the descriptor's range: dropped), the epilogue adds the missing addend and stores.
 template <class T>
@@ -267,12 +193,13 @@ __device__ __forceinline__ void stream_store(const SweepArgs& a, const BwdOut& o
 // One regular (plane, segment) iteration.  carry_*: right-tap contribution of the previous segment's last slot (wave
 // uniform); returns this segment's in the same variables.
 template <class T, bool MIX, int NROWS, bool PK, int TAIL>
-__device__ __forceinline__ void stream_compute(const StreamGroup<T, NROWS>& gq, const SweepArgs& a, const BwdOut& o,
+__device__ __forceinline__ void stream_compute(const StreamTaps<T, NROWS>& gq, const SweepArgs& a, const BwdOut& o,
                                                const StreamRow& r, const StreamLds& L, int n, int seg, int k, float sd,
                                                int lane, unsigned lane8, float lane2f, int HW, float Wm1, float rcpWm1,
                                                int want_plane, int gl_bytes, int gs_bytes, float& carry_l,
                                                float& carry_s, float& gacc, float* defer) {
-  const StreamGroup<float, NROWS> g = stream_taps(gq);
+  StreamTaps<float, NROWS> g;
+  stream_taps(gq, false, g.l, g.s);
   const int xs0 = seg * kSeg + lane * kSlots;
   const float xs0f = (float)(seg * kSeg) + lane2f;
   const float xt0f = xs0f - (float)k;   // integers below 2^24: exact
@@ -412,7 +339,8 @@ __device__ __forceinline__ float stream_general_slot(   // (as a call: 123 VGPRs
 // Stage target row r.y of image r.b for its workgroup: per-target-pixel context (cell = pixel + 2, zero-gradient guard cells),
 // the (vertically blended) source colour row and, TAIL, the decoder tail's per-source-pixel terms.
 template <bool MIX, int NROWS, bool PK, int TAIL>
-__device__ __forceinline__ void stream_stage_ctx(const SweepArgs& a, const BwdOut& o, const StreamRow& r, const StreamLds& L, int HW) {
+__device__ __forceinline__ void stream_stage_ctx(const SweepArgs& a, const BwdOut& o, const StreamRow& r, const RowSel& row,
+                                                 const StreamLds& L, int HW) {
   const int W = a.W;
   const float* srcb = a.src + (long)r.b * 3 * HW;
   for (int cidx = threadIdx.x; cidx < L.CW; cidx += blockDim.x) {
@@ -422,14 +350,7 @@ __device__ __forceinline__ void stream_stage_ctx(const SweepArgs& a, const BwdOu
     float4 cc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (x >= 0 && x < W) {
       c = make_pixel_ctx<MIX>(a, o, r.b, r.y * W + x, HW);
-      const float* p = srcb + (long)r.yA * W + x;
-      cc = make_float4(p[0], p[HW], p[2 * HW], 0.0f);
-      if (NROWS == 2) {
-        const float* q = srcb + (long)r.yB * W + x;
-        // fl(B*wB + fl(A*wA)): the rounding of the four-tap sum of the target-ordered kernels when the column weights are (1, 0)
-        // — with tgt == src and a zero disparity, sign(c - t) sits on the last ulp (knife edge (d))
-        cc = make_float4(fmaf(q[0], r.wB, cc.x * r.wA), fmaf(q[HW], r.wB, cc.y * r.wA), fmaf(q[2 * HW], r.wB, cc.z * r.wA), 0.0f);
-      }
+      cc = blended_colour(srcb, row, NROWS == 2, x, W, HW);
     }
     if (TAIL) {   // per SOURCE pixel of the row: what the decoder tail's backward needs (tail_term); zeros outside the row
       float4 tc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -454,14 +375,11 @@ __device__ __forceinline__ void stream_stage_ctx(const SweepArgs& a, const BwdOu
 template <int TAIL>
 __device__ __forceinline__ int stage_shift(const SweepArgs& a, const StreamLds& L, int i, float plane_i, bool masked, int nseg) {
   const int W = a.W;
-  const float lim = (float)(W + 2), tol = irregular_tol(W);
-  const float sdr = a.sign * plane_i;
-  const float sd = (!masked && sdr >= -lim && sdr <= lim) ? sdr : ((sdr < 0.0f && !masked) ? -lim : lim);  // NaN -> +lim
-  const float fl = floorf(sd), fr = sd - fl;
-  const int k = (int)fl;
-  const bool inview = fabsf(sd) < (float)(W + 1);
-  const int irr = (inview && (fr < tol || fr > 1.0f - tol)) ? 1 : 0;
-  L.shift[i] = make_int2(__float_as_int(sd), k * 2 + irr);
+  const float sd = clamp_shift(a.sign * plane_i, W, masked);
+  ShiftClass c;
+  classify_shift(sd, W, c);
+  const int k = c.k, irr = c.irr ? 1 : 0;
+  L.shift[i] = pack_shift(sd, c);
   if (TAIL) L.dpl[i] = plane_i;
   if (TAIL == kTailRows) L.mrow[i] = masked ? 0 : 1;
   L.red[i] = 0.0f;
@@ -473,7 +391,7 @@ __device__ __forceinline__ int stage_shift(const SweepArgs& a, const StreamLds& 
     else hi = min(nseg, max(0, (W + 1 + k + kSeg - 1) / kSeg));
   }
   L.live[i] = lo | (hi << 16);
-  return (irr || (k < 0 && inview)) ? 1 : 0;
+  return (irr || (k < 0 && c.inview)) ? 1 : 0;
 }
 
 template <class T, bool MIX, int NROWS, bool PK, int TAIL>
@@ -481,12 +399,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   constexpr int D = (NROWS == 1) ? PD_STREAM_D1 : PD_STREAM_D2;
   constexpr bool BF = sizeof(T) == 2;   // bf16 storage (never with TAIL)
   const int W = a.W, N = a.N, HW = a.H * a.W;
-  StreamRow r;
-  r.y = y;
-  r.b = b;
-  r.yA = row.yA; r.yB = (NROWS == 2) ? row.yB : row.yA;
-  r.wA = row.wA; r.wB = (NROWS == 2) ? row.wB : 0.0f;
-  r.wy = row.wy_main;
+  const StreamRow r = make_stream_row<NROWS>(b, y, row);
   const int lane = threadIdx.x & (kWave - 1);
   const int nwaves = __builtin_amdgcn_readfirstlane(blockDim.x >> 6), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nseg = (W + kSeg - 1) / kSeg;
@@ -510,11 +423,12 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
     ++ss;
     if (ss == nseg) { ss = 0; ++nn; }
   };
-  StreamGroup<T, NROWS> g[D + 1];
-  auto prefetch = [&](StreamGroup<T, NROWS>& grp) {
-    int ext = -1;
+  StreamTaps<T, NROWS> g[D + 1];
+  auto prefetch = [&](StreamTaps<T, NROWS>& grp) {
+    int ext = W;   // the row descriptors' extent in elements (wave-uniform)
     if (kDead) ext = (pseg < (p_live & 0xFFFF) || pseg >= (p_live >> 16)) ? 0 : W;   // a dead item's loads: no-ops that return zeros
-    stream_issue<MIX, NROWS>(grp, a, r, min(pn, N - 1), pseg, lane8, HW, ext);   // past the end: re-load the last plane (unused)
+    issue_taps<MIX, NROWS, PD_STREAM_LOAD_AUX>(grp, a, r, min(pn, N - 1), BF ? lane8 >> 1 : lane8, (unsigned)pseg * (kSeg * (int)sizeof(T)),
+                                               ext, HW);   // past the end: re-load the last plane (unused)
     advance(pn, pseg);
     if (kDead && pseg == 0) p_live = __builtin_amdgcn_readfirstlane(L.live[min(pn, N - 1)]);   // (once per plane)
   };
@@ -522,7 +436,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   // ---- stage the row: per-target-pixel context, blended colour row, per-plane shifts -----------------------------
   __builtin_amdgcn_s_setprio(3);   // a workgroup that has just arrived gets through its dependent round trips ahead of the streaming ones
   int special;
-  stream_stage_ctx<MIX, NROWS, PK, TAIL>(a, o, r, L, HW);
+  stream_stage_ctx<MIX, NROWS, PK, TAIL>(a, o, r, row, L, HW);
   if (threadIdx.x == 0) *L.special = 0;
   __syncthreads();
   {
@@ -542,7 +456,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
     // (kTailRows: a plane that is masked on this row is staged out of view, which is never irregular — every plane that gets
     // here is in view, its tail term is owed in full)
     for (int n2 = 0; n2 < N; ++n2) {
-      if (!(L.shift[n2].y & 1)) continue;
+      if (!packed_irr(L.shift[n2].y)) continue;
       for (int x = threadIdx.x; x < W; x += blockDim.x) {
         const long at = ((long)r.b * N + n2) * HW + (long)r.y * W + x;
         float il = 0.0f, is = 0.0f;
@@ -560,16 +474,16 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   if (kDead) p_live = __builtin_amdgcn_readfirstlane(L.live[min(pn, N - 1)]);
 
   bool first = true;   // bf16: the wave's first item (its first slot pair waits for the previous wave's carry when it starts mid-row)
-  auto step = [&](const StreamGroup<T, NROWS>& grp) {
+  auto step = [&](const StreamTaps<T, NROWS>& grp) {
     const int2 sh = L.shift[n];
     const int lv = kDead ? __builtin_amdgcn_readfirstlane(L.live[n]) : 0;
-    const float sd = __int_as_float(__builtin_amdgcn_readfirstlane(sh.x));
+    const float sd = packed_sd(__builtin_amdgcn_readfirstlane(sh.x));
     const int kk = __builtin_amdgcn_readfirstlane(sh.y);
-    const int k = kk >> 1;
+    const int k = packed_k(kk);
     float* defer = nullptr;   // bf16: where lane 0 parks its fp32 pair (a slot that takes one more addend in the epilogue)
     if (BF) {
       if (first && seg != 0) defer = L.handin + wave * 4;
-      else if (seg == 0 && k < 0 && fabsf(sd) < (float)(W + 1) && !(kk & 1)) {   // epilogue (2): the x0 = -1 target adds to column 0
+      else if (seg == 0 && k < 0 && fabsf(sd) < (float)(W + 1) && !packed_irr(kk)) {   // epilogue (2): the x0 = -1 target adds to column 0
         defer = L.fix + n * 4;
         if (lane == 0) L.fixed[n] = 1;
       }
@@ -579,9 +493,9 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
     if (kDead && (seg < (lv & 0xFFFF) || seg >= (lv >> 16))) {   // dead item (wave-uniform): zeros to store, nothing to read
       stream_store<T>(a, o, r, n, seg, lane, lane8, HW, gl_bytes, gs_bytes, MIX, 0.0f, 0.0f, 0.0f, 0.0f, defer);
       carry_l = carry_s = 0.0f;
-    } else if (BF && (kk & 1)) {   // irregular plane, bf16: settled as a whole row in LDS after the loop
+    } else if (BF && packed_irr(kk)) {   // irregular plane, bf16: settled as a whole row in LDS after the loop
       carry_l = carry_s = 0.0f;
-    } else if (kk & 1) {   // irregular plane (wave-uniform branch): exact per-lane floor, atomics into the zero-filled row
+    } else if (packed_irr(kk)) {   // irregular plane (wave-uniform branch): exact per-lane floor, atomics into the zero-filled row
 #pragma unroll
       for (int i = 0; i < kSlots; ++i) {
         const float gd = stream_general_slot<T, MIX, NROWS, PK, TAIL>(a, o, r, L, n, seg * kSeg + lane * kSlots + i, k, sd, true, HW, Wm1, rcpWm1);
@@ -631,7 +545,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   // (1) range boundaries inside a row: the first slot of the next wave's first segment lacks the carry
   if (BF && wave > 0 && i0 < i1 && lane == 0) {   // bf16: fl(slot + carry) from the parked fp32 pair, rounded once
     const int ns = i0 / nseg, ss = i0 - ns * nseg;
-    if (ss != 0 && !(L.shift[ns].y & 1)) {
+    if (ss != 0 && !packed_irr(L.shift[ns].y)) {
       const float hl = L.hand[(wave - 1) * 2], hs = L.hand[(wave - 1) * 2 + 1];
       const float* p = L.handin + wave * 4;
       const long at = ((long)r.b * N + ns) * HW + (long)r.y * W + ss * kSeg;
@@ -641,7 +555,7 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
   }
   if (!BF && wave > 0 && i0 < i1 && lane == 0) {
     const int ns = i0 / nseg, ss = i0 - ns * nseg;
-    if (ss != 0 && !(L.shift[ns].y & 1)) {
+    if (ss != 0 && !packed_irr(L.shift[ns].y)) {
       const float hl = L.hand[(wave - 1) * 2], hs = L.hand[(wave - 1) * 2 + 1];
       const long at = ((long)r.b * N + ns) * HW + (long)r.y * W + ss * kSeg;
       if (o.g_logits && hl != 0.0f) unsafeAtomicAdd(o.g_logits + at, hl);
@@ -654,8 +568,8 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
     // bf16: (2) on the regular planes, into the parked fp32 pair of column 0, then rounded once
     for (int j = threadIdx.x; j < N; j += blockDim.x) {
       const int2 sh = L.shift[j];
-      if ((sh.y & 1) || !L.fixed[j]) continue;
-      const float gd = stream_general_slot<T, MIX, NROWS, PK, TAIL, true>(a, o, r, L, j, -1, sh.y >> 1, __int_as_float(sh.x), true, HW,
+      if (packed_irr(sh.y) || !L.fixed[j]) continue;
+      const float gd = stream_general_slot<T, MIX, NROWS, PK, TAIL, true>(a, o, r, L, j, -1, packed_k(sh.y), packed_sd(sh.x), true, HW,
                                                                            Wm1, rcpWm1, L.fix + j * 4, L.fix + j * 4 + 2);
       if (want_plane && gd != 0.0f) atomicAdd(&L.red[j], gd);
     }
@@ -671,12 +585,12 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
     const int s_end = nseg * kSeg;
     for (int n2 = 0; n2 < N; ++n2) {
       const int2 sh = L.shift[n2];
-      if (!(sh.y & 1)) continue;   // (workgroup-uniform)
+      if (!packed_irr(sh.y)) continue;   // (workgroup-uniform)
       for (int x = threadIdx.x; x < 2 * L.CWr; x += blockDim.x) L.irr[x] = 0.0f;
       __syncthreads();
       float gd = 0.0f;
       for (int xs = (int)threadIdx.x - 2; xs <= s_end; xs += blockDim.x)
-        gd += stream_general_slot<T, MIX, NROWS, PK, TAIL, true>(a, o, r, L, n2, xs, sh.y >> 1, __int_as_float(sh.x), true, HW, Wm1,
+        gd += stream_general_slot<T, MIX, NROWS, PK, TAIL, true>(a, o, r, L, n2, xs, packed_k(sh.y), packed_sd(sh.x), true, HW, Wm1,
                                                                  rcpWm1, L.irr, L.irr + L.CWr);
       if (want_plane) {
         const float v = wave_sum_hi(gd);
@@ -697,11 +611,11 @@ __device__ __forceinline__ void stream_body(const SweepArgs& a, const BwdOut& o,
     for (int j = threadIdx.x; j < 3 * N; j += blockDim.x) {
       const int pn2 = j / 3, which = j - pn2 * 3;
       const int2 sh = L.shift[pn2];
-      const int kk = sh.y, k = kk >> 1;
-      const bool irr = kk & 1;
+      const int kk = sh.y, k = packed_k(kk);
+      const bool irr = packed_irr(kk);
       const int xs = (which == 0) ? -1 : ((which == 1) ? -2 : s_end);
       const bool on = (which == 0) || irr;
-      const float gd = stream_general_slot<T, MIX, NROWS, PK, TAIL>(a, o, r, L, pn2, xs, k, __int_as_float(sh.x), on, HW, Wm1, rcpWm1);
+      const float gd = stream_general_slot<T, MIX, NROWS, PK, TAIL>(a, o, r, L, pn2, xs, k, packed_sd(sh.x), on, HW, Wm1, rcpWm1);
       if (want_plane && gd != 0.0f) atomicAdd(&L.red[pn2], gd);
     }
     __syncthreads();

@@ -43,17 +43,17 @@ struct RowTaps {        // per pixel, plane-independent
   int ra, rb;           // clamped source rows
   float wa, wb;         // their weights (0 when the row is outside the image)
 };
-__device__ __forceinline__ RowTaps row_taps(int y, int H) {
-  const float iy = normalise_roundtrip((float)y, (float)(H - 1));
-  const float yf = floorf(iy), yf1 = yf + 1.0f;
-  const bool va = (yf >= 0.0f) && (yf <= (float)(H - 1)), vb = (yf1 >= 0.0f) && (yf1 <= (float)(H - 1));
-  const int y0 = (int)fminf(fmaxf(yf, -2.0f), (float)H);
+__device__ __forceinline__ RowTaps row_taps(int y, int H) {   // make_row_sel's footprint with clamped rows and zeroed weights
+  const RowSel s = make_row_sel(y, H);
+  // lower / upper are make_row_sel's use0 / use1: yB is always y0 + 1, and with one live row yA is y0 (!= yB) when it is the lower
+  // row and y0 + 1 (== yB) when it is the upper one; wA is wy0 whenever the lower row is live, wB is wy1 always.
+  const bool lower = s.nrows == 2 || (s.nrows == 1 && s.yA != s.yB), upper = s.nrows == 2 || (s.nrows == 1 && s.yA == s.yB);
   RowTaps r;
   r.y = y;
-  r.ra = min(max(y0, 0), H - 1);
-  r.rb = min(max(y0 + 1, 0), H - 1);
-  r.wa = va ? yf1 - iy : 0.0f;
-  r.wb = vb ? iy - yf : 0.0f;
+  r.ra = min(max(s.yB - 1, 0), H - 1);
+  r.rb = min(max(s.yB, 0), H - 1);
+  r.wa = lower ? s.wA : 0.0f;
+  r.wb = upper ? s.wB : 0.0f;
   return r;
 }
 
@@ -177,15 +177,6 @@ __global__ __launch_bounds__(kBlock) void warp_sum_kernel(WarpArgs a, float cap,
 // weights), and the sampling position costs make_col_tap's 7 operations instead of the general chain — half the
 // instructions of the gather kernels above in a VALU-bound loop.  FLIP reads the pair at the mirrored columns.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __amdgpu_buffer_rsrc_t PRsrc;
-typedef float v2f_b __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ PRsrc pp_row_rsrc(const float* row, int W) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, W * 4, 0x00020000);
-}
-__device__ __forceinline__ v2f_b pp_load2(PRsrc r, unsigned byte_off) {
-  return __builtin_bit_cast(v2f_b, __builtin_amdgcn_raw_buffer_load_b64(r, (int)byte_off, 0, 0));
-}
-
 struct RowPair {   // where the pair load goes and how its two dwords are weighted
   unsigned off;
   float e0, e1;
@@ -203,23 +194,22 @@ __device__ __forceinline__ RowPair row_pair(const ColTap& t, int W) {
   return p;
 }
 
-// the shift s*d_n, clamped like the sweep's staged shifts (beyond +-(W+1) nothing is in view; keeps x0*4 from aliasing)
+// the shift s*d_n, clamped like the sweep's staged shifts (clamp_shift; keeps x0*4 from aliasing)
 __device__ __forceinline__ float plane_shift(const WarpArgs& a, int b, int n, int y) {
-  const float sd = a.sign * a.disp[b * a.dimg + n * a.dplane + (y & a.ymask)], lim = (float)(a.W + 2);
-  return (sd >= -lim && sd <= lim) ? sd : ((sd < 0.0f) ? -lim : lim);   // NaN -> +lim
+  return clamp_shift(a.sign * a.disp[b * a.dimg + n * a.dplane + (y & a.ymask)], a.W, false);
 }
 
 template <bool FLIP, int NR, int U>
 __device__ __forceinline__ void rows_group(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b,
                                            int n0, int x, int HW, float (&out)[U]) {
   RowPair rp[U];
-  v2f_b va[U], vb[U];
+  v2f va[U], vb[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     rp[u] = row_pair<FLIP>(make_col_tap((float)x + plane_shift(a, b, n0 + u, r.y), a.Wm1, a.rcpWm1), a.W);
     const float* pl = pb + (long)(n0 + u) * HW;   // wave-uniform
-    va[u] = pp_load2(pp_row_rsrc(pl + (long)r.ra * a.W, a.W), rp[u].off);
-    if (NR == 2) vb[u] = pp_load2(pp_row_rsrc(pl + (long)r.rb * a.W, a.W), rp[u].off);
+    va[u] = buf_load2(row_rsrc(pl + (long)r.ra * a.W, a.W), rp[u].off);
+    if (NR == 2) vb[u] = buf_load2(row_rsrc(pl + (long)r.rb * a.W, a.W), rp[u].off);
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -296,10 +286,6 @@ __global__ __launch_bounds__(kWave) void warp_sum_rows_kernel(WarpArgs a, float 
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kSegPix = 2 * kWave;   // pixels per wave
 constexpr int kSegWaves = 4;         // waves per workgroup (independent items)
-typedef float v3f_pp __attribute__((ext_vector_type(3)));
-__device__ __forceinline__ v3f_pp pp_load3(PRsrc r, unsigned byte_off) {
-  return __builtin_bit_cast(v3f_pp, __builtin_amdgcn_raw_buffer_load_b96(r, (int)byte_off, 0, 0));
-}
 
 struct SegPlane {   // wave-uniform: one plane's shift for this segment
   float sd;
@@ -320,13 +306,11 @@ __device__ __forceinline__ float shift_of(float shifts, int j) {   // j: wave-un
 template <bool FLIP>
 __device__ __forceinline__ SegPlane seg_plane(const WarpArgs& a, float sd) {
   SegPlane p;
+  ShiftClass c;
+  classify_shift(sd, a.W, c);
   p.sd = sd;
-  const float fl = floorf(p.sd), fr = p.sd - fl;
-  p.k = (int)fl;
-  const float tol = irregular_tol(a.W);
-  const bool inview = fabsf(p.sd) < (float)(a.W + 1);
-  const bool irr = inview && (fr < tol || fr > 1.0f - tol);
-  p.general = irr;   // (a load that would start left of the row is re-aimed per lane: seg_load)
+  p.k = c.k;
+  p.general = c.irr;   // (a load that would start left of the row is re-aimed per lane: seg_load)
   return p;
 }
 
@@ -341,8 +325,8 @@ __device__ __forceinline__ SegAim seg_aim(int start) {
   m.off = (start <= -3) ? 0x7FFFFFF0u : ((unsigned)(start + m.adj) << 2);
   return m;
 }
-__device__ __forceinline__ v3f_pp seg_place(const v3f_pp& t, int adj) {
-  v3f_pp o;
+__device__ __forceinline__ v3f seg_place(const v3f& t, int adj) {
+  v3f o;
   o.x = (adj == 0) ? t.x : 0.0f;
   o.y = (adj == 0) ? t.y : ((adj == 1) ? t.x : 0.0f);
   o.z = (adj == 0) ? t.z : ((adj == 1) ? t.y : t.x);
@@ -351,8 +335,8 @@ __device__ __forceinline__ v3f_pp seg_place(const v3f_pp& t, int adj) {
 
 // the two samples of a lane on one plane from its loaded taps (A = first live row, B = second)
 template <bool FLIP, int NR>
-__device__ __forceinline__ void seg_values(const WarpArgs& a, const RowTaps& r, const SegPlane& p, float x0f, const v3f_pp& ta,
-                                           const v3f_pp& tb, float& v0, float& v1) {
+__device__ __forceinline__ void seg_values(const WarpArgs& a, const RowTaps& r, const SegPlane& p, float x0f, const v3f& ta,
+                                           const v3f& tb, float& v0, float& v1) {
   const float kf = (float)p.k;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -380,7 +364,7 @@ __device__ __forceinline__ void seg_group(const WarpArgs& a, const float* __rest
   const int nlim = min(nend, a.N);
   {
     SegPlane sp[G];
-    v3f_pp ta[G], tb[G];
+    v3f ta[G], tb[G];
     int adj[G];
 #pragma unroll
     for (int u = 0; u < G; ++u) {
@@ -389,8 +373,8 @@ __device__ __forceinline__ void seg_group(const WarpArgs& a, const float* __rest
       const float* pl = pb + (long)n * HW;
       const SegAim aim = seg_aim(FLIP ? a.W - 3 - (x0 + sp[u].k) : x0 + sp[u].k);
       adj[u] = aim.adj;
-      ta[u] = pp_load3(pp_row_rsrc(pl + (long)r.ra * a.W, a.W), aim.off);
-      if (NR == 2) tb[u] = pp_load3(pp_row_rsrc(pl + (long)r.rb * a.W, a.W), aim.off);
+      ta[u] = buf_load3(row_rsrc(pl + (long)r.ra * a.W, a.W), aim.off);
+      if (NR == 2) tb[u] = buf_load3(row_rsrc(pl + (long)r.rb * a.W, a.W), aim.off);
       else tb[u] = ta[u];
     }
 #pragma unroll
@@ -532,12 +516,11 @@ __device__ __forceinline__ bool chain_needs(int r, int t, int H) {
   const RowTaps q = row_taps(t, H);
   return (q.ra == r && q.wa != 0.0f) || (q.rb == r && q.wb != 0.0f);
 }
-// the second warp's shifts of planes 0 .. 63 under target row yt, one per lane (plane_shift's clamp)
+// the second warp's shifts of planes 0 .. 63 under target row yt, one per lane (clamp_shift, as plane_shift)
 __device__ __forceinline__ float chain_shifts(const float* __restrict__ disp2, float sign2, int rows2, int b, int N, int H, int yt,
-                                              float lim) {
+                                              int W) {
   const int n = min((int)(threadIdx.x & (kWave - 1)), N - 1);
-  const float sdr = sign2 * disp2[rows2 ? (b * N + n) * H + yt : b * N + n];
-  return (sdr >= -lim && sdr <= lim) ? sdr : ((sdr < 0.0f) ? -lim : lim);   // NaN -> +lim
+  return clamp_shift(sign2 * disp2[rows2 ? (b * N + n) * H + yt : b * N + n], W, false);
 }
 
 template <bool FLIP, int NR, int NMAX, bool ROWS2>
@@ -583,13 +566,12 @@ __device__ __forceinline__ void chain_row(const WarpArgs& a, const float* __rest
     }
   }
   __syncthreads();
-  const float lim = (float)(W + 2);
   for (int v = 0; v < (rows2 ? 3 : 1); ++v) {   // S_r under the shifts of target row y, y - 1, y + 1 (workgroup-uniform)
     const int yt = (v == 0) ? y : ((v == 1) ? y - 1 : y + 1);
     if (v > 0 && !chain_needs(y, yt, a.H)) continue;
     const int x0 = seg * kSegPix + 2 * lane;
     float acc0 = 0.0f, acc1 = 0.0f;
-    const float sh2 = chain_shifts(disp2, sign2, rows2, b, N, a.H, yt, lim);
+    const float sh2 = chain_shifts(disp2, sign2, rows2, b, N, a.H, yt, W);
     for (int n = 0; n < N; ++n) {
       const float sd = shift_of(sh2, n);
       const float* row = lds + n * RS;
@@ -675,7 +657,6 @@ __device__ __forceinline__ void chain_row_split(const WarpArgs& a, const float* 
       if (nb + j < ne) *reinterpret_cast<float2*>(lds + (nb + j) * RS + 2 + x0) = make_float2(l0[j] * c0, l1[j] * c1);
   }
   __syncthreads();   // (every wave has read the stats by now: the buffer is free for the partial sums)
-  const float lim = (float)(W + 2);
   constexpr int NV = ROWS2 ? 3 : 1;
   float accv[NV][2];
   bool need[NV];
@@ -686,7 +667,7 @@ __device__ __forceinline__ void chain_row_split(const WarpArgs& a, const float* 
     accv[v][0] = accv[v][1] = 0.0f;
     if (!need[v]) continue;
     float acc0 = 0.0f, acc1 = 0.0f;
-    const float sh2 = chain_shifts(disp2, sign2, rows2, b, N, a.H, yt, lim);
+    const float sh2 = chain_shifts(disp2, sign2, rows2, b, N, a.H, yt, W);
     for (int n = nb; n < ne; ++n) {
       const float sd = shift_of(sh2, n);
       const float* row = lds + n * RS;

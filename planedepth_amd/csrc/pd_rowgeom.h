@@ -1,5 +1,7 @@
-// Row geometry shared by the row-organised sweep kernels (pd_plane_sweep_rowshift.hip, pd_plane_sweep_rowstage.hip):
-// the vertical footprint of a target row and the bit-exact horizontal sampling position of the reference.
+// Pure geometry of a target row, shared by the row-organised kernels (pd_plane_sweep_fwdstream.hip, pd_plane_sweep_rowstream.hip,
+// pd_plane_sweep_rowshift.hip with pd_rowshift_fwd.h, pd_postprocess.hip): the vertical footprint of a row and its pairing with a
+// neighbour, the bit-exact horizontal sampling position of the reference, and a plane's shift along the row (clamp, classification,
+// the packed form kept in LDS).  Nothing in this file touches memory: pd_rowshift_common.h is the memory layer on top of it.
 #pragma once
 #include <math.h>
 
@@ -33,7 +35,40 @@ __device__ __forceinline__ RowSel make_row_sel(int y, int H) {
   return r;
 }
 
-// ---- row pairs (forward: pd_rowshift_fwd.h has the full story; backward: pd_plane_sweep_rowstream.hip) -------------------
+// The one-row bodies drop the multiplications by the vertical weight: they run only for rows whose single live source
+// row is the row itself with weight exactly 1 (every row whose normalise -> un-normalise round trip is exact).  Anything
+// else with one live row (weight 1 - eps at an image border) is rewritten as a two-row footprint with a zero second
+// weight on the same row, which the two-row bodies handle in full generality.
+// Vertical round-trip noise.  The reference's y -> normalise -> un-normalise chain returns y + e with |e| <= 6e-6 for a
+// quarter of the rows (fp32 rounding; exact arithmetic gives y), which makes grid_sample blend in the NEXT source row
+// with weight e.  (Forward values and per-pixel gradients always use that second row; only the ADJOINT's e-weighted
+// term into the neighbouring row is dropped: pd_plane_sweep_rowshift.hip's header.)  Serving that second row exactly
+// doubles the loads of those rows (measured at 8x49x192x640: forward
+// 0.137 -> 0.104 ms, backward 0.31 -> 0.30 ms, HBM reads -20% without it).  It is served by default all the same:
+// dropping it moves results by up to e * (range of the logits), measured 4e-5 (rgb_rec) .. 1e-4 (g_sigma) of the
+// tensors' range on random inputs — the whole 1e-4 parity budget.  PD_IMPL_FAST_ROWS opts into dropping a second row
+// whose weight is below 2^-16 (smooth network outputs make the difference far smaller than random test data does).
+// row_eps: a second source row whose weight is BELOW it is dropped (0: none is — PD_IMPL_EXACT_ROWS).
+__device__ __forceinline__ RowSel two_row_form(RowSel r, float row_eps) {
+  if (row_eps > 0.0f && r.nrows == 2) {
+    const bool a_main = r.wA >= r.wB;
+    if ((a_main ? r.wB : r.wA) < row_eps) {
+      r.nrows = 1;
+      r.yA = a_main ? r.yA : r.yB;
+      r.wA = 1.0f;
+      r.wy_main = 1.0f;
+      return r;
+    }
+  }
+  if (r.nrows == 1 && (r.wA != 1.0f || r.wy_main != 1.0f)) {
+    r.nrows = 2;
+    r.yB = r.yA;
+    r.wB = 0.0f;
+  }
+  return r;
+}
+
+// ---- row pairs (pd_rowshift_fwd.h has the full story) ------------------------------------------------------------------
 // A row y whose vertical round trip is inexact samples (1 - eps) * row y + eps * row p with p = y +- 1 ("leans" on p).  When p
 // is exact, or leans back on y, one workgroup serves BOTH target rows from the two source rows it loads anyway, and the
 // workgroup of p retires at once.  The rule is local (rows y-1 .. y+1), so every workgroup decides its own role without a table:
@@ -91,10 +126,9 @@ __device__ __forceinline__ PairW pair_weights(int y, int p, int H) {
   return w;
 }
 
-// ---- host mirrors (launch planning only: which rows go together, in which order) ---------------------------------------
-// make_row_sel / row_lean / pair_role on the host, operation by operation in fp32 (volatile: no contraction, no excess
-// precision).  The kernels never TRUST these for correctness: a unit table built from them says which rows a workgroup serves,
-// and the device re-derives every footprint itself (a pair the device's own arithmetic does not confirm is served row by row).
+// ---- host mirror (launch planning only: which rows go together, in which order) ----------------------------------------
+// make_row_sel on the host, operation by operation in fp32 (volatile: no contraction, no excess precision).  The kernels never
+// TRUST it for correctness: a table built from it says which rows a workgroup serves, and the device re-derives every footprint.
 struct HostRowSel { int nrows, yA, yB; float wA, wB, wy_main; };
 inline HostRowSel host_row_sel(int y, int H) {
   volatile float hm1 = (float)(H - 1);
@@ -119,35 +153,6 @@ inline HostRowSel host_row_sel(int y, int H) {
   r.wy_main = (y0 == y) ? wy0 : ((y0 + 1 == y) ? wy1 : 0.0f);
   return r;
 }
-inline int host_row_lean(int y, int H) {
-  if (y < 0 || y >= H) return 0;
-  const HostRowSel r = host_row_sel(y, H);
-  if (r.nrows != 2) return 0;
-  return (r.yA == y) ? +1 : -1;
-}
-inline bool host_leads(int y, int H) {
-  const int l = host_row_lean(y, H);
-  if (l == 0) return false;
-  const int p = y + l;
-  const int lp = host_row_lean(p, H);
-  if (lp == -l) return y < p;
-  if (lp != 0) return false;
-  if (l == -1) return host_row_lean(p - 1, H) != +1;
-  return true;
-}
-// 0 single, 1 leader (partner = the row it takes along), 2 absorbed (partner = its leader)
-inline int host_pair_role(int y, int H, int& partner) {
-  partner = y;
-  const int l = host_row_lean(y, H);
-  if (l != 0) {
-    partner = y + l;
-    if (host_leads(y, H)) return 1;
-    return (host_row_lean(partner, H) == -l && host_leads(partner, H)) ? 2 : 0;
-  }
-  if (host_row_lean(y - 1, H) == +1 && host_leads(y - 1, H)) { partner = y - 1; return 2; }
-  if (host_row_lean(y + 1, H) == -1 && host_leads(y + 1, H)) { partner = y + 1; return 2; }
-  return 0;
-}
 
 struct ColTap {    // horizontal footprint of one target pixel on one plane
   int x0;          // floor(ix)
@@ -158,23 +163,67 @@ struct ColTap {    // horizontal footprint of one target pixel on one plane
 //   reference:  q = px/(W-1);  g = (q - 0.5)*2;            [trainer.py:550-552]
 //               ix = ((g + 1)/2) * (W-1)                    [grid_sample, align_corners=True]
 //   (g + 1)/2 = fl(2h + 1)/2 with h = fl(q - 0.5); scaling by 2 commutes with rounding, so it equals fl(h + 0.5).
-// |px| <= 2W+2 by construction (the per-plane shift is clamped to +-(W+2) when it is staged), so floor(ix) converts
-// to int without saturating and x0*4 cannot alias into the row.
+// The ONE chain: every row kernel's ix goes through here (contraction off: each operation rounds on its own).
+__device__ __forceinline__ float reference_ix(float px, float Wm1, float rcpWm1) {
+#pragma clang fp contract(off)
+  const float q = div_by(px, Wm1, rcpWm1);
+  const float h = q - 0.5f;
+  const float hh = h + 0.5f;
+  return hh * Wm1;
+}
+// ix for target column xtf (an integer-valued float) under the shift sd; the sum rounds on its own as well
+__device__ __forceinline__ float stream_ix(float xtf, float sd, float Wm1, float rcpWm1) {
+#pragma clang fp contract(off)
+  const float px = xtf + sd;
+  return reference_ix(px, Wm1, rcpWm1);
+}
+// |px| <= 2W+2 by construction (the per-plane shift is clamped to +-(W+2), clamp_shift), so floor(ix) converts to int without
+// saturating and x0*4 cannot alias into the row.
 __device__ __forceinline__ ColTap make_col_tap(float px, float Wm1, float rcpWm1) {
   ColTap t;
-  float ix;
-  {
-#pragma clang fp contract(off)
-    const float q = div_by(px, Wm1, rcpWm1);
-    const float h = q - 0.5f;
-    const float hh = h + 0.5f;
-    ix = hh * Wm1;
-  }
+  const float ix = reference_ix(px, Wm1, rcpWm1);
   const float xf = floorf(ix);
   t.w0 = (xf + 1.0f) - ix;
   t.w1 = ix - xf;
   t.x0 = (int)xf;
   return t;
 }
+
+// ---- a plane's shift along the row ---------------------------------------------------------------------------------------
+// sd = sign * disparity, clamped to +-(W+2): beyond +-(W+1) nothing is in view either way.  NaN -> +lim.  `masked` (PD_MASK_ROWS: a
+// masked plane samples as all-zero features, trainer.py:580 — exactly what a plane shifted out of view does, every tap being
+// outside the row) overrides the shift with +lim.
+__device__ __forceinline__ float clamp_shift(float sd, int W, bool masked) {
+  const float lim = (float)(W + 2);
+  return (!masked && sd >= -lim && sd <= lim) ? sd : ((sd < 0.0f && !masked) ? -lim : lim);
+}
+
+// frac(s*d) closer than this to an integer: the plane takes the general path of the kernels that pair target xt with source
+// column xt + floor(s*d).  Worst-case error of the coordinate chain against exact arithmetic: fl(x + sd) <= ulp(2W)/2, the
+// division, the two additions and the product by W-1 each <= ulp(.)/2 scaled by W-1 — 5.4e-7 * W in total (3.1e-4 at W = 640);
+// the threshold keeps a factor of 2.4-3 up to W = 4096 (NOTEBOOK.md 3.6.3).
+__device__ __forceinline__ float irregular_tol(int W) { return 2.5e-4f + 1.25e-6f * (float)W; }
+
+struct ShiftClass {
+  int k;         // floor(sd): the left tap of target xt is source column xt + k
+  bool irr;      // in view and within irregular_tol of an integer
+  bool inview;   // |sd| < W + 1
+};
+// (fills `c` in place: returned by value, the same function cost the post-process's segment and chain kernels 3-8 VGPRs each,
+// four of them an occupancy step — profiles/row_layer_refactor_ab.md)
+__device__ __forceinline__ void classify_shift(float sd, int W, ShiftClass& c) {
+  const float fl = floorf(sd), fr = sd - fl;
+  c.k = (int)fl;
+  const float tol = irregular_tol(W);
+  const bool inview = fabsf(sd) < (float)(W + 1);
+  const bool irr = inview && (fr < tol || fr > 1.0f - tol);
+  c.irr = irr;
+  c.inview = inview;
+}
+// The stream kernels keep a plane's shift in LDS as (bits of sd, 2k + irr) — integers: a float-typed slot may flush a denormal.
+__device__ __forceinline__ int2 pack_shift(float sd, const ShiftClass& c) { return make_int2(__float_as_int(sd), c.k * 2 + (c.irr ? 1 : 0)); }
+__device__ __forceinline__ float packed_sd(int bits) { return __int_as_float(bits); }
+__device__ __forceinline__ int packed_k(int kk) { return kk >> 1; }
+__device__ __forceinline__ bool packed_irr(int kk) { return kk & 1; }
 
 }  // namespace pd

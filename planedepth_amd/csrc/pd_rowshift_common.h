@@ -1,6 +1,7 @@
-// Memory-access layer and row staging shared by the row-organised sweep kernels (pd_plane_sweep_rowshift.hip: one pixel
-// per lane; the segment-stream forward and the row-stream backward): dispatch order, buffer resources per (plane, row), tap
-// loads, colour rows in LDS, per-plane shifts.
+// Memory layer of a target row, on top of pd_rowgeom.h's geometry, shared by the row-organised kernels (pd_plane_sweep_rowshift.hip
+// with pd_rowshift_fwd.h: one pixel per lane; pd_plane_sweep_fwdstream.hip and pd_plane_sweep_rowstream.hip: two per lane;
+// pd_postprocess.hip): dispatch order, buffer resources per (plane, row), the 8- and 12-byte tap loads and the stores, the tap
+// ring of the two stream kernels, colour rows in LDS, the staged per-plane shifts.
 #pragma once
 #include <stdlib.h>
 
@@ -8,10 +9,8 @@
 
 namespace pd {
 
-constexpr int kMaxRowThreads = 1024;
-
 // Tuning knobs (scripts/build_variants.sh builds variants with -D...): plane-group size and the occupancy the register
-// allocator must leave room for (waves per SIMD), per kernel.
+// allocator must leave room for (waves per SIMD), of the plane-group forward and the row-shift backward.
 #ifndef PD_FWD_U
 #define PD_FWD_U 4
 #endif
@@ -20,12 +19,6 @@ constexpr int kMaxRowThreads = 1024;
 #endif
 #ifndef PD_BWD_U
 #define PD_BWD_U 2
-#endif
-#ifndef PD_STORE_AUX
-#define PD_STORE_AUX 0  // cache-policy bits of the gradient stores (experiments: 1 = sc0, 2 = nt, 16 = sc1)
-#endif
-#ifndef PD_LOAD_AUX
-#define PD_LOAD_AUX 0   // same for the tap loads
 #endif
 #ifndef PD_BWD_OCC
 #define PD_BWD_OCC 3
@@ -58,39 +51,6 @@ __device__ __forceinline__ int bwd_rowid(int B, int H) {
   return H - 1 - wg_rowid(B, H);
 }
 
-// The one-row bodies drop the multiplications by the vertical weight: they run only for rows whose single live source
-// row is the row itself with weight exactly 1 (every row whose normalise -> un-normalise round trip is exact).  Anything
-// else with one live row (weight 1 - eps at an image border) is rewritten as a two-row footprint with a zero second
-// weight on the same row, which the two-row bodies handle in full generality.
-// Vertical round-trip noise.  The reference's y -> normalise -> un-normalise chain returns y + e with |e| <= 6e-6 for a
-// quarter of the rows (fp32 rounding; exact arithmetic gives y), which makes grid_sample blend in the NEXT source row
-// with weight e.  (Forward values and per-pixel gradients always use that second row; only the ADJOINT's e-weighted
-// term into the neighbouring row is dropped: pd_plane_sweep_rowshift.hip's header.)  Serving that second row exactly
-// doubles the loads of those rows (measured at 8x49x192x640: forward
-// 0.137 -> 0.104 ms, backward 0.31 -> 0.30 ms, HBM reads -20% without it).  It is served by default all the same:
-// dropping it moves results by up to e * (range of the logits), measured 4e-5 (rgb_rec) .. 1e-4 (g_sigma) of the
-// tensors' range on random inputs — the whole 1e-4 parity budget.  PD_IMPL_FAST_ROWS opts into dropping a second row
-// whose weight is below 2^-16 (smooth network outputs make the difference far smaller than random test data does).
-// row_eps: a second source row whose weight is BELOW it is dropped (0: none is — PD_IMPL_EXACT_ROWS).
-__device__ __forceinline__ RowSel two_row_form(RowSel r, float row_eps) {
-  if (row_eps > 0.0f && r.nrows == 2) {
-    const bool a_main = r.wA >= r.wB;
-    if ((a_main ? r.wB : r.wA) < row_eps) {
-      r.nrows = 1;
-      r.yA = a_main ? r.yA : r.yB;
-      r.wA = 1.0f;
-      r.wy_main = 1.0f;
-      return r;
-    }
-  }
-  if (r.nrows == 1 && (r.wA != 1.0f || r.wy_main != 1.0f)) {
-    r.nrows = 2;
-    r.yB = r.yA;
-    r.wB = 0.0f;
-  }
-  return r;
-}
-
 // ---- memory access layer ------------------------------------------------------------------------------------------
 // Row-sized buffer resources (SRD in SGPRs, built from workgroup-uniform values only) give three things at once:
 //   * a 32-bit per-lane byte offset instead of 64-bit address arithmetic (the u64 adds were ~15% of all VALU cycles);
@@ -98,6 +58,9 @@ __device__ __forceinline__ RowSel two_row_form(RowSel r, float row_eps) {
 //     which IS grid_sample's padding_mode="zeros" — no validity compares, selects or clamped indices in the forward;
 //   * loads without exec-mask branches, so a whole group's loads issue back to back.
 typedef __amdgpu_buffer_rsrc_t Rsrc;
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v3f __attribute__((ext_vector_type(3)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ Rsrc row_rsrc(const float* row, int W) {  // `row` must be wave-uniform
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, W * 4, 0x00020000);
@@ -118,7 +81,7 @@ __device__ __forceinline__ float buf_load(Rsrc r, unsigned byte_off) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0));
 }
 __device__ __forceinline__ void buf_store(Rsrc r, unsigned byte_off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)byte_off, 0, PD_STORE_AUX);
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)byte_off, 0, 0);
 }
 
 // Offset of plane n inside one image's [N,H,W] block, in floats: a 32-bit product (the host checks N*H*W < 2^31) added
@@ -154,10 +117,13 @@ struct Taps {
   float a0, a1, b0, b1;  // row A (x0, x0+1), row B (x0, x0+1)
 };
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ v2f buf_load2(Rsrc r, unsigned byte_off) {  // 8 bytes at any 4-byte-aligned offset
-  return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, (int)byte_off, 0, PD_LOAD_AUX));
+  return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(r, (int)byte_off, 0, 0));
+}
+// 12 bytes at vector offset + scalar offset (wave-uniform); AUX: the cache-policy bits (1 = sc0, 2 = nt, 16 = sc1), an immediate
+template <int AUX = 0>
+__device__ __forceinline__ v3f buf_load3(Rsrc r, unsigned voff, unsigned soff = 0) {
+  return __builtin_bit_cast(v3f, __builtin_amdgcn_raw_buffer_load_b96(r, (int)voff, (int)soff, AUX));
 }
 
 // Both horizontal taps of a row come from ONE 8-byte load at column x0 (measured on gfx950, scripts/probes/buf_probe:
@@ -286,16 +252,13 @@ __device__ __forceinline__ void colour_dx(const ColourTaps<NROWS>& t, const RowS
   }
 }
 
-// Shift of plane i along target row `yrow` of image b: sign * disparity clamped to +-(W+2) (beyond +-(W+1) nothing is in
-// view either way).
+// Shift of plane i along target row `yrow` of image b: sign * disparity through clamp_shift; under PD_MASK_ROWS the row's mask
+// value overrides it (out of view).
 __device__ __forceinline__ float staged_shift(const SweepArgs& a, int b, int i, int yrow) {
-  const float lim = (float)(a.W + 2);
   const long di = (a.flags & PD_DISP_ROWS) ? ((long)b * a.N + i) * a.H + yrow : (long)b * a.N + i;
   const float sd = a.sign * a.plane[di];
-  // PD_MASK_ROWS: a masked plane samples as all-zero features (trainer.py:580) — exactly what a plane shifted out
-  // of view does (every tap is outside the row), so the row's mask value just overrides the shift
   const bool masked = a.mask_rows && a.mask_rows[((long)b * a.N + i) * a.H + yrow] == 0.0f;
-  return (!masked && sd >= -lim && sd <= lim) ? sd : ((sd < 0.0f && !masked) ? -lim : lim);  // NaN -> +lim
+  return clamp_shift(sd, a.W, masked);
 }
 
 // Stage the live source colour rows of image b into LDS as float4 (with zero guard cells), plus the per-plane shifts
@@ -322,22 +285,105 @@ __device__ __forceinline__ void stage_row_constants(const SweepArgs& a, int b, c
   for (int i = threadIdx.x; i < a.N; i += blockDim.x) sdisp[i] = staged_shift(a, b, i, yrow);
 }
 
-// ---- shared by the source-ordered backward (pd_plane_sweep_rowstream.hip) and the segment-stream forward (pd_plane_sweep_fwdstream.hip) ----
-// frac(s*d) closer than this to an integer: the plane takes the general path.  Worst-case error of the coordinate
-// chain against exact arithmetic: fl(x + sd) <= ulp(2W)/2, the division, the two additions and the product by W-1
-// each <= ulp(.)/2 scaled by W-1 — 5.4e-7 * W in total (3.1e-4 at W = 640); the threshold keeps a factor of 2.4-3
-// up to W = 4096 (NOTEBOOK.md 3.6.3).
-__device__ __forceinline__ float irregular_tol(int W) { return 2.5e-4f + 1.25e-6f * (float)W; }
-
-// ix of the reference for target column xtf (an integer-valued float) under the shift sd: make_col_tap's chain
-__device__ __forceinline__ float stream_ix(float xtf, float sd, float Wm1, float rcpWm1) {
-#pragma clang fp contract(off)
-  const float px = xtf + sd;
-  const float q = div_by(px, Wm1, rcpWm1);
-  const float h = q - 0.5f;
-  const float hh = h + 0.5f;
-  return hh * Wm1;
+// ---- the two stream kernels (pd_plane_sweep_fwdstream.hip, pd_plane_sweep_rowstream.hip): a lane owns two adjacent columns -------
+struct StreamRow {     // workgroup-uniform: the target row a wave works on
+  int b, y, yA, yB;
+  float wA, wB, wy;    // vertical weights of the two source rows; adjoint weight of the own row (backward)
+};
+template <int NROWS>
+__device__ __forceinline__ StreamRow make_stream_row(int b, int y, const RowSel& row) {
+  StreamRow r;
+  r.y = y;
+  r.b = b;
+  r.yA = row.yA; r.yB = (NROWS == 2) ? row.yB : row.yA;
+  r.wA = row.wA; r.wB = (NROWS == 2) ? row.wB : 0.0f;
+  r.wy = row.wy_main;
+  return r;
 }
 
+// One slot of the tap ring: the taps of a lane's two columns on one plane, L[c .. c+2] per live source row, logits and sigma.
+template <class T, int NROWS>
+struct StreamTaps {
+  float l[NROWS][3], s[NROWS][3];
+};
+// bf16 storage: the raw 8 bytes of ONE load per tensor and row, four elements from a 4-byte-aligned (even) column; the three taps
+// are picked and widened when the plane is reduced (stream_taps), so a slot holds 2 VGPRs per tensor and row instead of 3.
+template <int NROWS>
+struct StreamTaps<Bf16, NROWS> {
+  unsigned l[NROWS][2], s[NROWS][2];
+};
+
+// Issue the tap loads of plane n for row r into slot g: per tensor (sigma with MIX) and live source row ONE load at byte offset
+// voff (per lane) + soff (wave-uniform) through a descriptor of Wx elements (the row's width; 0 turns the loads into hardware
+// no-ops that return zeros), cache-policy bits AUX.  soff = 0, Wx = a.W and AUX = 0 fold to the plain per-lane load.
+template <bool MIX, int NROWS, int AUX>
+__device__ __forceinline__ void issue_taps(StreamTaps<float, NROWS>& g, const SweepArgs& a, const StreamRow& r, int n, unsigned voff,
+                                           unsigned soff, int Wx, int HW) {
+  auto ld = [&](const float* row, float (&t)[3]) {
+    const v3f v = buf_load3<AUX>(row_rsrc(row, Wx), voff, soff);
+    t[0] = v.x; t[1] = v.y; t[2] = v.z;
+  };
+  const float* pl = plane_ptr(a.logits + (long)r.b * a.N * HW, n, HW);
+  ld(pl + (long)r.yA * a.W, g.l[0]);
+  if (NROWS == 2) ld(pl + (long)r.yB * a.W, g.l[NROWS - 1]);
+  if (MIX) {
+    const float* ps = plane_ptr(a.sigma + (long)r.b * a.N * HW, n, HW);
+    ld(ps + (long)r.yA * a.W, g.s[0]);
+    if (NROWS == 2) ld(ps + (long)r.yB * a.W, g.s[NROWS - 1]);
+  }
+}
+template <bool MIX, int NROWS, int AUX>
+__device__ __forceinline__ void issue_taps(StreamTaps<Bf16, NROWS>& g, const SweepArgs& a, const StreamRow& r, int n, unsigned voff,
+                                           unsigned soff, int Wx, int HW) {
+  auto ld = [&](const Bf16* row, unsigned (&w)[2]) {
+    const v2u v = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(row_rsrc_t(row, Wx), (int)voff, (int)soff, AUX));
+    w[0] = v.x; w[1] = v.y;
+  };
+  const Bf16* pl = plane_ptr_t(elems<Bf16>(a.logits) + (long)r.b * a.N * HW, n, HW);
+  ld(pl + (long)r.yA * a.W, g.l[0]);
+  if (NROWS == 2) ld(pl + (long)r.yB * a.W, g.l[NROWS - 1]);
+  if (MIX) {
+    const Bf16* ps = plane_ptr_t(elems<Bf16>(a.sigma) + (long)r.b * a.N * HW, n, HW);
+    ld(ps + (long)r.yA * a.W, g.s[0]);
+    if (NROWS == 2) ld(ps + (long)r.yB * a.W, g.s[NROWS - 1]);
+  }
+}
+
+// The three fp32 taps of a slot per row and tensor.  bf16: elements (0,1,2) of the loaded four, or (1,2,3) when the first tap sits
+// at the odd column (`odd`, wave-uniform: the forward loads from the even column below an odd one; the backward never does).
+__device__ __forceinline__ void bf16_taps3(const unsigned (&w)[2], bool odd, float (&t)[3]) {
+  t[0] = odd ? bf16_hi(w[0]) : bf16_lo(w[0]);
+  t[1] = odd ? bf16_lo(w[1]) : bf16_hi(w[0]);
+  t[2] = odd ? bf16_hi(w[1]) : bf16_lo(w[1]);
+}
+template <int NROWS>
+__device__ __forceinline__ void stream_taps(const StreamTaps<float, NROWS>& g, bool, float (&l)[NROWS][3], float (&s)[NROWS][3]) {
+#pragma unroll
+  for (int r = 0; r < NROWS; ++r)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { l[r][i] = g.l[r][i]; s[r][i] = g.s[r][i]; }
+}
+template <int NROWS>
+__device__ __forceinline__ void stream_taps(const StreamTaps<Bf16, NROWS>& g, bool odd, float (&l)[NROWS][3], float (&s)[NROWS][3]) {
+#pragma unroll
+  for (int r = 0; r < NROWS; ++r) { bf16_taps3(g.l[r], odd, l[r]); bf16_taps3(g.s[r], odd, s[r]); }
+}
+
+// The colour cell both stream kernels stage in LDS: source colour at column x of the row's footprint, zero outside the row; with
+// two live source rows (`two`) vertically blended as fl(B*wB + fl(A*wA)) — the rounding of the four-tap sum of the target-ordered
+// kernels when the column weights are (1, 0): with tgt == src and a zero disparity, sign(c - t) sits on the last ulp (DESIGN.md
+// section 5, knife edge (d)), so the forward and the backward must stage the same bits.
+__device__ __forceinline__ float4 blended_colour(const float* __restrict__ srcb, const RowSel& row, bool two, int x, int W, int HW) {
+  float4 cc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (x >= 0 && x < W) {
+    const float* p = srcb + (long)row.yA * W + x;
+    cc = make_float4(p[0], p[HW], p[2 * HW], 0.0f);
+    if (two) {
+      const float* q = srcb + (long)row.yB * W + x;
+      cc = make_float4(fmaf(q[0], row.wB, cc.x * row.wA), fmaf(q[HW], row.wB, cc.y * row.wA), fmaf(q[2 * HW], row.wB, cc.z * row.wA), 0.0f);
+    }
+  }
+  return cc;
+}
 
 }  // namespace pd

@@ -1,10 +1,8 @@
 // Forward of the row-organised plane sweep (PD_WARP_DISP, one disparity per (image, plane) or per (image, plane, row)):
-// the plane-group pipeline, the work split inside a row workgroup, the row pairs, and the per-row bodies.  Shared by
-//   * pd_plane_sweep_rowshift.hip   — one workgroup per target row (any mask form, --render_probability), and
-//   * pd_plane_sweep_rowpersist.hip — persistent workgroups that walk rows and stage the NEXT row's colour rows and
-//     shifts by LDS-DMA while the current row's plane loop runs (the headline forward).
-// The bodies take their row constants (colour rows, per-plane shifts) already staged in LDS; `CL` says how the colour
-// rows lie there.
+// the plane-group pipeline, the work split inside a row workgroup, the row pairs, and the per-row bodies of
+// pd_plane_sweep_rowshift.hip (one workgroup per target row: any mask form, --render_probability).  The bodies take their row
+// constants (colour rows, per-plane shifts) already staged in LDS; `CL` says how the colour rows lie there (the planar layout
+// served the persistent variant archived as docs/archive/experiments/pd_plane_sweep_rowpersist.hip.txt).
 #pragma once
 #include <stdlib.h>
 

@@ -1,4 +1,5 @@
-// Per-(pixel, plane) sampling geometry shared by the general sweep kernels (pd_plane_sweep.hip, pd_plane_sweep_tile.hip).
+// Per-(pixel, plane) sampling geometry of the general sweep kernels (pd_plane_sweep.hip; the tile kernel that shared it is
+// archived under docs/archive/).
 #pragma once
 #include "pd_sweep.h"
 

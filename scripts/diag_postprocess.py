@@ -1,6 +1,12 @@
 """Per-call device time of the post-process operators at the benchmark shape (run once per PD_PP_SEG setting: the
-library reads the switch once per process).  python scripts/diag_postprocess.py [--batch 4 --planes 49]"""
+library reads the switch once per process).  python scripts/diag_postprocess.py [--batch 4 --planes 49]
+
+--ab name=path [name=path ...]: A/B of library builds on pd_post_process instead — the libraries are loaded side by side through
+ctypes and called directly, interleaved round by round (--rounds windows of --iters calls each between two device events); per
+library the median and the spread (min .. max) of the windows, and whether each later median lies inside the first one's spread."""
 import argparse
+import ctypes
+import json
 import os
 import sys
 
@@ -8,6 +14,55 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from planedepth_amd import ops  # noqa: E402
+
+
+def ab(a, logits, prob, disp, dl):
+    from planedepth_amd import _capi as C
+    B, N, H, W = a.batch, a.planes, a.height, a.width
+    libs = []
+    for spec in a.ab:
+        name, _, path = spec.partition("=")
+        lib = ctypes.CDLL(path or C.LIB_PATH)
+        for fn, (res, args) in C.SIGNATURES.items():
+            getattr(lib, fn).restype, getattr(lib, fn).argtypes = res, args
+        libs.append((name, lib))
+    st = C.stream_handle(logits.device)
+    lv = dl[:, :, 0, 0].contiguous()                                    # per-plane disparities [2B,N]
+    ws = torch.empty(max(int(l.pd_post_process_workspace_floats(B, N, H, W)) for _, l in libs), device=logits.device)
+    dpp, mn = torch.empty(B, 1, H, W, device=logits.device), torch.empty(B, 1, H, W, device=logits.device)
+
+    def call(lib):
+        rc = lib.pd_post_process(B, N, H, W, 0, C.ptr(logits), C.ptr(prob), C.ptr(disp), C.ptr(lv), C.ptr(ws), C.ptr(dpp), C.ptr(mn), st)
+        assert rc == 0, lib.pd_last_error()
+
+    times = {name: [] for name, _ in libs}
+    for _, lib in libs:
+        for _ in range(10):
+            call(lib)
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):
+        for name, lib in libs:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(a.iters):
+                call(lib)
+            e.record()
+            torch.cuda.synchronize()
+            times[name].append(s.elapsed_time(e) / a.iters)
+    med = lambda v: sorted(v)[len(v) // 2] if len(v) % 2 else 0.5 * (sorted(v)[len(v) // 2 - 1] + sorted(v)[len(v) // 2])
+    out = {}
+    print("pd_post_process %dx%dx%dx%d, ms per call over %d rounds of %d" % (B, N, H, W, a.rounds, a.iters))
+    for name, _ in libs:
+        t = times[name]
+        out[name] = {"median_ms": med(t), "min_ms": min(t), "max_ms": max(t), "rounds": t}
+        print("%-12s median %.4f  min %.4f  max %.4f" % (name, med(t), min(t), max(t)))
+    first = out[libs[0][0]]
+    for name, _ in libs[1:]:
+        out[name]["inside_first_spread"] = first["min_ms"] <= out[name]["median_ms"] <= first["max_ms"]
+        print("%-12s median %s %s's spread" % (name, "inside" if out[name]["inside_first_spread"] else "OUTSIDE", libs[0][0]))
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump({"shape": [B, N, H, W], "results": out}, fh, indent=1)
 
 
 def main():
@@ -18,6 +73,9 @@ def main():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--xz", type=int, default=0, help="the last K planes get a disparity that grows with the row (ground planes): a [B,N,H,1] map expanded along x")
+    ap.add_argument("--ab", nargs="+", default=None, help="name=path of library builds: A/B of pd_post_process, interleaved in this process")
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
     B, N, H, W = a.batch, a.planes, a.height, a.width
     dev = torch.device("cuda:0")
@@ -32,6 +90,8 @@ def main():
         rows[:, N - a.xz:] = rows[:, N - a.xz:] * gain
         dl = rows.expand(-1, -1, -1, W)
     disp = (prob * dl).sum(1, True)
+    if a.ab:
+        return ab(a, logits, prob, disp, dl)
 
     def timed(fn):
         for _ in range(5):

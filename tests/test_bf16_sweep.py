@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def _stream_tol(W):   # pd_rowshift_common.h irregular_tol(W)
+def _stream_tol(W):   # pd_rowgeom.h irregular_tol(W)
     return 2.5e-4 + 1.25e-6 * W
 
 

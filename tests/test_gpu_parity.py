@@ -25,7 +25,7 @@ ILL_CONDITIONED = {"homo_mix_stereo": {"g_Rt"}}
 @pytest.fixture(params=["exact", "fast"])
 def row_mode(request):
     """Both treatments of a second source row whose bilinear weight is fp32 noise of the reference's y round trip (<= 6e-6 at
-    H = 192; pd_rowshift_common.h: two_row_form): PD_IMPL_EXACT_ROWS serves it, PD_IMPL_FAST_ROWS drops it below 2^-16.
+    H = 192; pd_rowgeom.h: two_row_form): PD_IMPL_EXACT_ROWS serves it, PD_IMPL_FAST_ROWS drops it below 2^-16.
     VERDICT r4 #1a: every oracle / golden parity test of the disp path runs under both, at the same 1e-4 — which of the
     two PD_IMPL_AUTO means (pd_sweep_auto_row_eps) follows from that, not from taste.  Only the row kernels look at the
     mode; the other kernels run as under PD_IMPL_AUTO."""
@@ -226,7 +226,7 @@ def test_rowshift_kernels_vs_general_kernels_and_oracle(W, side, disps):
 
 
 def _stream_tol(W):
-    """pd_plane_sweep_rowstream.hip irregular_tol(W): closer than this to an integer, a shift takes the general path."""
+    """pd_rowgeom.h irregular_tol(W): closer than this to an integer, a shift takes the general path."""
     return 2.5e-4 + 1.25e-6 * W
 
 
