@@ -106,6 +106,37 @@ def elementwise_report(a, b, rtol=1e-4, floor=1e-4):
     return dict(max_norm_err=rel_err(a, b), frac_beyond=float((r > 1).double().mean()), worst_over_allowance=float(r.max()))
 
 
+def slice_report(got, ref64, plane_floor):
+    """Row-scaled companion of rel_err for the sweep's tensors: every (b, n, y) row of a [B,*,H,W] tensor is measured against its
+    OWN largest reference entry, so a low-probability plane, a partly visible row or the row under a horizon mask has the same
+    relative budget as the tensor's loudest row.
+
+      D[b,n,y] = max(max_x |ref[b,n,y,:]|, plane_floor * max_{y,x} |ref[b,n]|),   err = max |got - ref| / D over rows with D > 0.
+
+    Tensors without a W axis ([B,N], [B,N,H], [B,N,1,1], [B,4,4], scalars) are compared per element: D = |ref|, floored by
+    plane_floor * max|ref| of the tensor.  A (b, n) plane whose reference is identically zero has D = 0: ``got`` there must stay
+    within 1e-6 * max|ref| of the tensor (1e-6 absolute for an all-zero tensor, as test_gpu_parity._compare has it) —
+    ``zero_ok`` — and ``zero_planes`` / ``zero_rows`` count them, so that a case table that claims to cover them can say so."""
+    g, r = got.detach().double().cpu(), ref64.detach().double().cpu()
+    assert g.shape == r.shape, (tuple(g.shape), tuple(r.shape))
+    scale = float(r.abs().max()) if r.numel() else 0.0
+    diff = (g - r).abs()
+    if r.dim() == 4 and r.shape[3] > 1:
+        rowmax = r.abs().amax(3)                                   # [B,N,H]
+        planemax = rowmax.amax(2, keepdim=True)                    # [B,N,1]
+        D = torch.maximum(rowmax, plane_floor * planemax)
+        diff = diff.amax(3)
+        zero_planes = int((planemax == 0).sum())
+    else:
+        D = torch.maximum(r.abs(), torch.full_like(r, plane_floor * scale))
+        zero_planes = int(scale == 0.0)
+    live = D > 0
+    err = float((diff[live] / D[live]).max()) if bool(live.any()) else 0.0
+    zero_abs = float(diff[~live].max()) if bool((~live).any()) else 0.0
+    return dict(err=err, zero_planes=zero_planes, zero_rows=int((~live).sum()), zero_abs=zero_abs,
+                zero_ok=zero_abs <= (1e-6 * scale if scale > 0.0 else 1e-6), scale=scale)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # BASELINE configs[3] as the trainer runs it: all target sides, decoder-made xz planes (tests/golden/trainer_mono.npz)
 # ---------------------------------------------------------------------------------------------------------------------
