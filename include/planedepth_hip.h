@@ -474,6 +474,35 @@ size_t pd_post_process_workspace_floats(int B, int N, int H, int W);
 int pd_post_process(int B, int N, int H, int W, int flags, const float* logits, const float* probability, const float* disp,
                     const float* disp_layered, float* workspace, float* disp_pp, float* mask_novel, pd_stream_t stream);
 
+/* Which kernel serves a post-process call: the ONE decision the three entry points above dispatch on, answered on the host (no
+ * GPU needed: the LDS size falls back to gfx950's 160 KiB) from the shape, the flags and the ALIGNMENT of the buffers named —
+ * the pointers are never dereferenced, and NULL stands for an 8-byte aligned buffer.  An entry point launches what its query
+ * reports and nothing else (a combination without a kernel is an error return, not a fall-back).
+ *   family     the warps: per-pixel gather (dense disparities), row kernels (one pixel per lane), segment kernels (a pixel pair
+ *              per lane: even W, 8-byte aligned out, the softmax with N <= 64); the fused call: the six single warps (each on
+ *              its own pd_warp_route), the row chain with one wave per segment (pp_chain_kernel), or with the planes of a
+ *              segment dealt to three waves (pp_chain_split_kernel: W <= 640)
+ *   flip       PD_PP_FLIP_SRC (a template argument of every warp kernel; the chains run both reads: 0)
+ *   nmax       the planes a lane's registers are unrolled over: 32 / 52 / 64 (segment softmax, pp_chain_kernel), 11 / 18 / 22
+ *              per part (pp_chain_split_kernel); 0 = a run-time loop over the planes
+ *   rows2      the chains' second warp takes per-row shifts (PD_PP_DISP_ROWS): three S maps per chain
+ *   alias      pp_chain_split_kernel keeps the parts' statistics inside the row buffer (the row buffer nearly fills the LDS)
+ *   lds_bytes  dynamic LDS per workgroup */
+enum pd_pp_kind { PD_PP_KIND_SOFTMAX = 0, PD_PP_KIND_SUM = 1 };
+enum pd_pp_family {
+  PD_PP_FAMILY_GATHER = 0, PD_PP_FAMILY_ROWS = 1, PD_PP_FAMILY_SEG = 2,          /* pd_warp_softmax / pd_warp_sum */
+  PD_PP_FAMILY_SINGLE = 3, PD_PP_FAMILY_CHAIN = 4, PD_PP_FAMILY_CHAIN_SPLIT = 5  /* pd_post_process */
+};
+typedef struct pd_pp_route {
+  int32_t family; /* pd_pp_family */
+  int32_t flip, nmax, rows2, alias;
+  uint32_t lds_bytes;
+} pd_pp_route;
+/* flags as for the entry point (pd_warp_route: PD_PP_FLIP_SRC included); returns PD_OK, or the entry point's own refusal of
+ * the shape or the flags. */
+int pd_warp_route(int kind, int B, int N, int H, int W, int flags, const void* out, pd_pp_route* route);
+int pd_post_process_route(int B, int N, int H, int W, int flags, const void* workspace, const void* disp_pp, pd_pp_route* route);
+
 /*
  * Trainer.add_flip_right_inputs (trainer.py:252-276): out [2B,C,H,W] = cat([own, flip(other, -1)]);
  * negate_c0 flips the sign of channel 0 in the mirrored half (the x-coordinate channel of `grid`, trainer.py:258-260).

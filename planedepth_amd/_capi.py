@@ -53,6 +53,16 @@ def sweep_view(**tensors):
     return v
 
 
+PD_PP_KIND_SOFTMAX, PD_PP_KIND_SUM = 0, 1
+PD_PP_FAMILIES = ("gather", "rows", "seg", "single", "chain", "chain_split")   # pd_pp_family, by value
+
+
+class PpRoute(ctypes.Structure):
+    """Mirror of ``pd_pp_route``: the kernel a post-process call is served by (pd_warp_route / pd_post_process_route)."""
+    _fields_ = [("family", ctypes.c_int32), ("flip", ctypes.c_int32), ("nmax", ctypes.c_int32), ("rows2", ctypes.c_int32),
+                ("alias", ctypes.c_int32), ("lds_bytes", ctypes.c_uint32)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
@@ -103,6 +113,8 @@ SIGNATURES = {
     "pd_warp_sum": (_I, [_I] * 4 + [_F, _I, _P, _P, _F, _P, _P]),
     "pd_post_process_workspace_floats": (ctypes.c_size_t, [_I] * 4),
     "pd_post_process": (_I, [_I] * 5 + [_P] * 8),
+    "pd_warp_route": (_I, [_I] * 6 + [_P, ctypes.POINTER(PpRoute)]),
+    "pd_post_process_route": (_I, [_I] * 5 + [_P, _P, ctypes.POINTER(PpRoute)]),
     "pd_pp_combine": (_I, [_I] * 3 + [_P] * 5),
     "pd_cat_flip": (_I, [_I] * 4 + [_P, _P, _I, _P, _P]),
     "pd_plane_levels_fwd": (_I, [_I, _I, _F, _F, _F, _P, _P, _P, _P]),

@@ -802,13 +802,14 @@ static bool rows_applicable(const WarpArgs& a, int B) {
   return !a.dense && a.H <= 65535 && B <= 65535 && a.W <= (1 << 24);
 }
 
+// (query: a route query — shape and flags only, no tensors)
 static int warp_args(WarpArgs& a, int B, int N, int H, int W, float sign, int flags, const float* planes,
-                     const float* disp) {
+                     const float* disp, bool query = false) {
   PD_REQUIRE(B > 0 && B <= 65535 && N > 0 && H > 0 && W > 1, "bad shape");
   PD_REQUIRE((long)H * W < (1L << 31), "image too large");
   PD_REQUIRE((flags & ~(PD_PP_DISP_DENSE | PD_PP_FLIP_SRC | PD_PP_DISP_ROWS)) == 0, "unknown flags");
   PD_REQUIRE(!((flags & PD_PP_DISP_DENSE) && (flags & PD_PP_DISP_ROWS)), "PD_PP_DISP_DENSE and PD_PP_DISP_ROWS exclude each other");
-  PD_REQUIRE(planes && disp, "NULL pointer");
+  PD_REQUIRE(query || (planes && disp), "NULL pointer");
   a.N = N; a.H = H; a.W = W;
   a.dense = (flags & PD_PP_DISP_DENSE) != 0;
   a.rows = (flags & PD_PP_DISP_ROWS) != 0;
@@ -828,6 +829,56 @@ static int warp_args(WarpArgs& a, int B, int N, int H, int W, float sign, int fl
   return 0;
 }
 
+// The route of pd_warp_softmax / pd_warp_sum (include/planedepth_hip.h: pd_pp_route).  The entry points switch on what this returns,
+// pd_warp_route reports it: there is no second copy of a predicate.
+static pd_pp_route warp_route(int kind, const WarpArgs& a, int B, const void* out) {
+  pd_pp_route r = {};
+  r.flip = a.flip;
+  const bool softmax = kind == PD_PP_KIND_SOFTMAX;
+  if (seg_applicable(a, B, static_cast<const float*>(out), softmax ? 64 : 1 << 20)) {
+    r.family = PD_PP_FAMILY_SEG;
+    r.nmax = !softmax ? 0 : (a.N <= 32 ? 32 : (a.N <= 52 ? 52 : 64));   // (52: the 49 planes)
+  } else {
+    r.family = rows_applicable(a, B) ? PD_PP_FAMILY_ROWS : PD_PP_FAMILY_GATHER;
+  }
+  return r;
+}
+
+// The route of pd_post_process.  Row chains where the softmax of a row fits the CU's LDS: per-plane (or per-row) disparities,
+// pixel pairs, N <= 64.
+static pd_pp_route post_process_route(int B, int N, int H, int W, int flags, const void* workspace, const void* disp_pp) {
+  pd_pp_route r = {};
+  r.family = PD_PP_FAMILY_SINGLE;
+  const size_t chain_lds = (size_t)N * (W + 4) * sizeof(float);
+  if (!(flags & PD_PP_DISP_DENSE) && !switches().pp_seg_off && (W % 2 == 0) && W <= 8 * kSegPix && N <= 64 && H <= 65535 &&
+      chain_lds <= device_lds_bytes() && (long)2 * B * H < (1L << 31) &&
+      ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(disp_pp)) & 7) == 0) {
+    r.rows2 = (flags & PD_PP_DISP_ROWS) ? 1 : 0;
+    const int nseg = ceil_div(W, kSegPix);
+    // planes dealt to P = 3 waves per segment where the workgroup (3 nseg <= 16 waves) and its LDS (row buffer + one float2 per
+    // pixel and part) fit; else one wave per segment
+    const size_t side_lds = chain_lds + (size_t)3 * nseg * kSegPix * sizeof(float2);
+    const bool alias = side_lds > device_lds_bytes();   // the parts' statistics / partial sums inside the row buffer (needs 9 maps of
+                                                        // nseg x 128 float2 there: N >= 18 at W = 640)
+    if (3 * nseg <= 16 && (!alias || (size_t)9 * nseg * kSegPix * sizeof(float2) <= chain_lds)) {
+      r.family = PD_PP_FAMILY_CHAIN_SPLIT;
+      r.nmax = N <= 33 ? 11 : (N <= 54 ? 18 : 22);
+      r.alias = alias ? 1 : 0;
+      r.lds_bytes = (uint32_t)(alias ? chain_lds : side_lds);
+    } else {
+      r.family = PD_PP_FAMILY_CHAIN;
+      r.nmax = N <= 32 ? 32 : (N <= 52 ? 52 : 64);
+      r.lds_bytes = (uint32_t)chain_lds;
+    }
+  }
+  return r;
+}
+
+static int no_kernel(const char* what, const pd_pp_route& r) {
+  set_error("%s: no kernel for route (family %d, flip %d, nmax %d, rows2 %d, alias %d)", what, r.family, r.flip, r.nmax, r.rows2, r.alias);
+  return PD_ERR_UNSUPPORTED;
+}
+
 }  // namespace pd
 
 using namespace pd;
@@ -837,27 +888,39 @@ extern "C" int pd_warp_softmax(int B, int N, int H, int W, float sign, int flags
   WarpArgs a;
   if (int rc = warp_args(a, B, N, H, W, sign, flags, planes, disp)) return rc;
   PD_REQUIRE(out && out != planes, "out must be a distinct buffer");
-  if (seg_applicable(a, B, out, 64)) {
-    const int nseg = ceil_div(W, kSegPix);
-    const dim3 g((unsigned)(((long)B * H * nseg + kSegWaves - 1) / kSegWaves));
-    if (N <= 32) { if (a.flip) warp_softmax_seg_kernel<true, 32><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out);
-                   else        warp_softmax_seg_kernel<false, 32><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out); }
-    else if (N <= 52) { if (a.flip) warp_softmax_seg_kernel<true, 52><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out);   // (49 planes)
-                        else        warp_softmax_seg_kernel<false, 52><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out); }
-    else         { if (a.flip) warp_softmax_seg_kernel<true, 64><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out);
-                   else        warp_softmax_seg_kernel<false, 64><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out); }
-    return check_launch("warp_softmax_seg_kernel");
+  const pd_pp_route r = warp_route(PD_PP_KIND_SOFTMAX, a, B, out);
+  switch (r.family) {
+    case PD_PP_FAMILY_SEG: {
+      const int nseg = ceil_div(W, kSegPix);
+      const dim3 g((unsigned)(((long)B * H * nseg + kSegWaves - 1) / kSegWaves));
+#define PD_PP_SOFTMAX_SEG(NMAX)                                                                                             \
+      do {                                                                                                                  \
+        if (r.flip) warp_softmax_seg_kernel<true, NMAX><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out);       \
+        else        warp_softmax_seg_kernel<false, NMAX><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out);      \
+      } while (0)
+      switch (r.nmax) {
+        case 32: PD_PP_SOFTMAX_SEG(32); break;
+        case 52: PD_PP_SOFTMAX_SEG(52); break;
+        case 64: PD_PP_SOFTMAX_SEG(64); break;
+        default: return no_kernel("pd_warp_softmax", r);
+      }
+#undef PD_PP_SOFTMAX_SEG
+      return check_launch("warp_softmax_seg_kernel");
+    }
+    case PD_PP_FAMILY_ROWS: {
+      dim3 g(ceil_div(W, kWave), H, B);
+      if (r.flip) warp_softmax_rows_kernel<true><<<g, kWave, 0, (hipStream_t)stream>>>(a, out);
+      else        warp_softmax_rows_kernel<false><<<g, kWave, 0, (hipStream_t)stream>>>(a, out);
+      return check_launch("warp_softmax_rows_kernel");
+    }
+    case PD_PP_FAMILY_GATHER: {
+      dim3 grid(ceil_div(H * W, kBlock), B);
+      if (r.flip) warp_softmax_kernel<true><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, out);
+      else        warp_softmax_kernel<false><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, out);
+      return check_launch("warp_softmax_kernel");
+    }
+    default: return no_kernel("pd_warp_softmax", r);
   }
-  if (rows_applicable(a, B)) {
-    dim3 g(ceil_div(W, kWave), H, B);
-    if (a.flip) warp_softmax_rows_kernel<true><<<g, kWave, 0, (hipStream_t)stream>>>(a, out);
-    else        warp_softmax_rows_kernel<false><<<g, kWave, 0, (hipStream_t)stream>>>(a, out);
-    return check_launch("warp_softmax_rows_kernel");
-  }
-  dim3 grid(ceil_div(H * W, kBlock), B);
-  if (a.flip) warp_softmax_kernel<true><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, out);
-  else        warp_softmax_kernel<false><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, out);
-  return check_launch("warp_softmax_kernel");
 }
 
 extern "C" int pd_warp_sum(int B, int N, int H, int W, float sign, int flags, const float* planes, const float* disp,
@@ -865,23 +928,39 @@ extern "C" int pd_warp_sum(int B, int N, int H, int W, float sign, int flags, co
   WarpArgs a;
   if (int rc = warp_args(a, B, N, H, W, sign, flags, planes, disp)) return rc;
   PD_REQUIRE(out, "NULL output");
-  if (seg_applicable(a, B, out, 1 << 20)) {
-    const int nseg = ceil_div(W, kSegPix);
-    const dim3 g((unsigned)(((long)B * H * nseg + kSegWaves - 1) / kSegWaves));
-    if (a.flip) warp_sum_seg_kernel<true><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, cap, out);
-    else        warp_sum_seg_kernel<false><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, cap, out);
-    return check_launch("warp_sum_seg_kernel");
+  const pd_pp_route r = warp_route(PD_PP_KIND_SUM, a, B, out);
+  switch (r.family) {
+    case PD_PP_FAMILY_SEG: {
+      const int nseg = ceil_div(W, kSegPix);
+      const dim3 g((unsigned)(((long)B * H * nseg + kSegWaves - 1) / kSegWaves));
+      if (r.nmax != 0) return no_kernel("pd_warp_sum", r);
+      if (r.flip) warp_sum_seg_kernel<true><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, cap, out);
+      else        warp_sum_seg_kernel<false><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, cap, out);
+      return check_launch("warp_sum_seg_kernel");
+    }
+    case PD_PP_FAMILY_ROWS: {
+      dim3 g(ceil_div(W, kWave), H, B);
+      if (r.flip) warp_sum_rows_kernel<true><<<g, kWave, 0, (hipStream_t)stream>>>(a, cap, out);
+      else        warp_sum_rows_kernel<false><<<g, kWave, 0, (hipStream_t)stream>>>(a, cap, out);
+      return check_launch("warp_sum_rows_kernel");
+    }
+    case PD_PP_FAMILY_GATHER: {
+      dim3 grid(ceil_div(H * W, kBlock), B);
+      if (r.flip) warp_sum_kernel<true><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, cap, out);
+      else        warp_sum_kernel<false><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, cap, out);
+      return check_launch("warp_sum_kernel");
+    }
+    default: return no_kernel("pd_warp_sum", r);
   }
-  if (rows_applicable(a, B)) {
-    dim3 g(ceil_div(W, kWave), H, B);
-    if (a.flip) warp_sum_rows_kernel<true><<<g, kWave, 0, (hipStream_t)stream>>>(a, cap, out);
-    else        warp_sum_rows_kernel<false><<<g, kWave, 0, (hipStream_t)stream>>>(a, cap, out);
-    return check_launch("warp_sum_rows_kernel");
-  }
-  dim3 grid(ceil_div(H * W, kBlock), B);
-  if (a.flip) warp_sum_kernel<true><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, cap, out);
-  else        warp_sum_kernel<false><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, cap, out);
-  return check_launch("warp_sum_kernel");
+}
+
+extern "C" int pd_warp_route(int kind, int B, int N, int H, int W, int flags, const void* out, pd_pp_route* route) {
+  PD_REQUIRE(kind == PD_PP_KIND_SOFTMAX || kind == PD_PP_KIND_SUM, "kind must be PD_PP_KIND_SOFTMAX or PD_PP_KIND_SUM");
+  PD_REQUIRE(route, "NULL route");
+  WarpArgs a;
+  if (int rc = warp_args(a, B, N, H, W, 1.0f, flags, nullptr, nullptr, true)) return rc;
+  *route = warp_route(kind, a, B, out);
+  return PD_OK;
 }
 
 extern "C" int pd_pp_combine(int B, int H, int W, const float* disp, const float* o_fr, const float* o_l, float* disp_pp,
@@ -912,10 +991,8 @@ extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const floa
   float* o_l = workspace + (size_t)B * img;
   float* o_fr = o_l + (size_t)B * P;
   int rc;
-  // Row chains where the softmax of a row fits the CU's LDS: per-plane disparities, pixel pairs, N <= 64
-  const size_t chain_lds = (size_t)N * (W + 4) * sizeof(float);
-  if (!(flags & PD_PP_DISP_DENSE) && !switches().pp_seg_off && (W % 2 == 0) && W <= 8 * kSegPix && N <= 64 && H <= 65535 &&
-      chain_lds <= device_lds_bytes() && (long)2 * B * H < (1L << 31) && ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(disp_pp)) & 7) == 0) {
+  const pd_pp_route r = post_process_route(B, N, H, W, flags, workspace, disp_pp);
+  if (r.family == PD_PP_FAMILY_CHAIN_SPLIT || r.family == PD_PP_FAMILY_CHAIN) {
     ChainArgs c;
     const int rowsf = flags & PD_PP_DISP_ROWS;
     if ((rc = warp_args(c.w[0], B, N, H, W, +1.0f, rowsf, logits, dl_r))) return rc;
@@ -923,15 +1000,11 @@ extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const floa
     c.disp2[0] = dl_l; c.sign2[0] = -1.0f;
     c.disp2[1] = dl_r; c.sign2[1] = +1.0f;
     c.S[0] = workspace; c.S[1] = workspace + (size_t)3 * B * P;   // [3][B,1,H,W] each
-    c.B = B; c.rows2 = rowsf ? 1 : 0;
+    c.B = B; c.rows2 = r.rows2;
     const int nseg = ceil_div(W, kSegPix);
     const dim3 grid((unsigned)(2 * B * H));
-    // planes dealt to P = 3 waves per segment where the workgroup (3 nseg <= 16 waves) and its LDS (row buffer + one float2 per
-    // pixel and part) fit; else one wave per segment
-    const size_t side_lds = chain_lds + (size_t)3 * nseg * kSegPix * sizeof(float2);
-    const bool alias = side_lds > device_lds_bytes();   // the parts' statistics / partial sums inside the row buffer (needs 9 maps of
-    const size_t split_lds = alias ? chain_lds : side_lds;   // nseg x 128 float2 there: N >= 18 at W = 640)
-    if (3 * nseg <= 16 && (!alias || (size_t)9 * nseg * kSegPix * sizeof(float2) <= chain_lds)) {
+    const size_t chain_lds = r.lds_bytes, split_lds = r.lds_bytes;
+    if (r.family == PD_PP_FAMILY_CHAIN_SPLIT) {   // planes dealt to P = 3 waves per segment
       const dim3 block3(3 * nseg * kWave);
 #define PD_PP_SPLIT_(NPART, R2, AL)                                                                                                 \
       do {                                                                                                                        \
@@ -941,10 +1014,15 @@ extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const floa
       } while (0)
 #define PD_PP_SPLIT(NPART)                                                                              \
       do {                                                                                              \
-        if (alias) { if (c.rows2) PD_PP_SPLIT_(NPART, true, true); else PD_PP_SPLIT_(NPART, false, true); } \
-        else       { if (c.rows2) PD_PP_SPLIT_(NPART, true, false); else PD_PP_SPLIT_(NPART, false, false); } \
+        if (r.alias) { if (r.rows2) PD_PP_SPLIT_(NPART, true, true); else PD_PP_SPLIT_(NPART, false, true); } \
+        else         { if (r.rows2) PD_PP_SPLIT_(NPART, true, false); else PD_PP_SPLIT_(NPART, false, false); } \
       } while (0)
-      if (N <= 33) PD_PP_SPLIT(11); else if (N <= 54) PD_PP_SPLIT(18); else PD_PP_SPLIT(22);
+      switch (r.nmax) {
+        case 11: PD_PP_SPLIT(11); break;
+        case 18: PD_PP_SPLIT(18); break;
+        case 22: PD_PP_SPLIT(22); break;
+        default: return no_kernel("pd_post_process", r);
+      }
 #undef PD_PP_SPLIT_
 #undef PD_PP_SPLIT
       if ((rc = check_launch("pp_chain_split_kernel"))) return rc;
@@ -960,7 +1038,12 @@ extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const floa
       pp_chain_kernel<NMAX, R2><<<grid, block, chain_lds, (hipStream_t)stream>>>(c);                                        \
     } while (0)
 #define PD_PP_CHAIN(NMAX) do { if (c.rows2) PD_PP_CHAIN_(NMAX, true); else PD_PP_CHAIN_(NMAX, false); } while (0)
-    if (N <= 32) PD_PP_CHAIN(32); else if (N <= 52) PD_PP_CHAIN(52); else PD_PP_CHAIN(64);
+    switch (r.nmax) {
+      case 32: PD_PP_CHAIN(32); break;
+      case 52: PD_PP_CHAIN(52); break;
+      case 64: PD_PP_CHAIN(64); break;
+      default: return no_kernel("pd_post_process", r);
+    }
 #undef PD_PP_CHAIN
 #undef PD_PP_CHAIN_
     if ((rc = check_launch("pp_chain_kernel"))) return rc;
@@ -968,10 +1051,20 @@ extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const floa
     if ((rc = check_launch("pp_rows_finish_kernel"))) return rc;
     return pd_warp_sum(B, N, H, W, +1.0f, flags, probability, dl_r, 1.0f, mask_novel, stream);                           // :463-465
   }
+  if (r.family != PD_PP_FAMILY_SINGLE) return no_kernel("pd_post_process", r);
   if ((rc = pd_warp_softmax(B, N, H, W, +1.0f, flags, logits, dl_r, planes, stream))) return rc;                         // :443-446
   if ((rc = pd_warp_sum(B, N, H, W, -1.0f, flags, planes, dl_l, 1.0f, o_l, stream))) return rc;                         // :447-449
   if ((rc = pd_warp_softmax(B, N, H, W, -1.0f, flags | PD_PP_FLIP_SRC, logits + (size_t)B * img, dl_l, planes, stream))) return rc;   // :451-453
   if ((rc = pd_warp_sum(B, N, H, W, +1.0f, flags, planes, dl_r, 1.0f, o_fr, stream))) return rc;                        // :454-456
   if ((rc = pd_pp_combine(B, H, W, disp, o_fr, o_l, disp_pp, stream))) return rc;                                        // :458-461
   return pd_warp_sum(B, N, H, W, +1.0f, flags, probability, dl_r, 1.0f, mask_novel, stream);                             // :463-465
+}
+
+extern "C" int pd_post_process_route(int B, int N, int H, int W, int flags, const void* workspace, const void* disp_pp,
+                                     pd_pp_route* route) {
+  PD_REQUIRE(B > 0 && N > 0 && H > 0 && W > 1, "bad shape");
+  PD_REQUIRE((flags & ~(PD_PP_DISP_DENSE | PD_PP_DISP_ROWS)) == 0, "unknown flags");
+  PD_REQUIRE(route, "NULL route");
+  *route = post_process_route(B, N, H, W, flags, workspace, disp_pp);
+  return PD_OK;
 }

@@ -31,7 +31,7 @@ from .losses import (  # noqa: F401
     _MaskedPhotometric, masked_photometric, _row_strided, _SmoothLoss, smooth_loss_disp,
     _FeatureDistance, feature_distance)
 from .postprocess import (  # noqa: F401
-    _pp_disp, warp_softmax, warp_sum, pp_combine, post_process_disp, post_process_disp_stepwise, cat_flip,
+    _pp_disp, warp_route, post_process_route, warp_softmax, warp_sum, pp_combine, post_process_disp, post_process_disp_stepwise, cat_flip,
     crop_grid)
 from .metrics import (  # noqa: F401
     DepthEval, PackedGT, pack_gt, eval_depth_errors, resize_disp, trainer_depth_metrics, summarize)

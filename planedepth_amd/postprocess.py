@@ -1,6 +1,8 @@
 """Forward-only operators around the batch: the self-distillation post-process (trainer.py:404-466), the batch doubling of
 add_flip_right_inputs (trainer.py:252-276), the dataset's crop grid (datasets/pair_transforms.py:27-56).
 """
+import ctypes
+
 from . import _capi as C
 from . import planeform as PF
 from ._buffers import torch, _contig
@@ -16,6 +18,30 @@ def _pp_disp(disp_layered, B, N, H, W, row_uniform=False):
     networks/depth_decoder.py:153-181; yz planes are not) and for a [B,N,H,1] map, which the expand over x makes a row view."""
     form, disp = PF.disp_operand(disp_layered, B, N, H, W, promise=row_uniform or (disp_layered.shape[-1] == 1 and W > 1), grad=False)
     return disp, _DISP_FLAG[form]
+
+
+def _route_dict(r):
+    return dict(family=C.PD_PP_FAMILIES[r.family], flip=bool(r.flip), nmax=int(r.nmax), rows2=bool(r.rows2), alias=bool(r.alias),
+                lds_bytes=int(r.lds_bytes))
+
+
+def warp_route(kind, B, N, H, W, flags=0, out_ptr=0):
+    """The kernel ``pd_warp_softmax`` (``kind="softmax"``) / ``pd_warp_sum`` (``"sum"``) runs for this shape, these
+    ``PD_PP_*`` flags and an ``out`` buffer at address ``out_ptr`` (only its alignment counts; 0: 8-byte aligned), as a dict
+    of ``pd_pp_route``'s fields with the family by name.  Answered on the host: no GPU needed."""
+    r = C.PpRoute()
+    C.check(C.load().pd_warp_route({"softmax": C.PD_PP_KIND_SOFTMAX, "sum": C.PD_PP_KIND_SUM}[kind], B, N, H, W, int(flags),
+                                   ctypes.c_void_p(int(out_ptr)), ctypes.byref(r)), "pd_warp_route")
+    return _route_dict(r)
+
+
+def post_process_route(B, N, H, W, flags=0, workspace_ptr=0, disp_pp_ptr=0):
+    """The kernels ``pd_post_process`` runs (B: half of the doubled batch): ``family`` "chain" / "chain_split" (the fused row
+    chains) or "single" (two warp-softmaxes, three warp-sums and the blend, each on its own ``warp_route``)."""
+    r = C.PpRoute()
+    C.check(C.load().pd_post_process_route(B, N, H, W, int(flags), ctypes.c_void_p(int(workspace_ptr)),
+                                           ctypes.c_void_p(int(disp_pp_ptr)), ctypes.byref(r)), "pd_post_process_route")
+    return _route_dict(r)
 
 
 def warp_softmax(planes, disp_layered, sign, flip_src=False, row_uniform=False):
