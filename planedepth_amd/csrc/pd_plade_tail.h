@@ -41,18 +41,20 @@ __device__ __forceinline__ void plade_operands(const PladeArgs& a, int b, int n,
   o.rs = MIX ? ldv<PX>(elems<ST>(a.raw_sigma) + ((long)b * a.N + n) * a.HW + pix) : splat<PX>(0.0f);
 }
 
-// Plane n at one pixel: the next depth layer zn, the distance to it along the ray, alpha and pi = alpha * T.  zc = this plane's
-// depth layer, T = the transmittance in front of it; both stay with the caller, which moves them on (T *= plade_keep(alpha),
+// Plane n at one pixel: the next depth layer zn, the distance to it along the ray, alpha, pi = alpha * T and e = exp(-relu(l) dist),
+// which is d alpha / d (relu(l) dist) — the backward takes it from here: 1 - alpha has lost e's low bits once alpha is near 1.  zc =
+// this plane's depth layer, T = the transmittance in front of it; both stay with the caller, which moves them on (T *= plade_keep(alpha),
 // zc = zn) when it is done with them — the backward uses T first.  c = tail_depth_scale(W), r = the ray's length.
 struct PladeStep {
-  float zn, dist, alpha, p;
+  float zn, dist, alpha, p, e;
 };
 __device__ __forceinline__ PladeStep plade_step(bool last, float c, float dn, float rl, float r, float zc, float T) {
-  PladeStep s = {zc, 0.0f, 1.0f, 0.0f};
+  PladeStep s = {zc, 0.0f, 1.0f, 0.0f, 0.0f};
   if (!last) {
     s.zn = c / dn;                                                       // plade_net.py:311
     s.dist = (s.zn - zc) * r;                                            // :312-315
-    s.alpha = 1.0f - __expf(-fmaxf(rl, 0.0f) * s.dist);                  // :317
+    s.e = __expf(-fmaxf(rl, 0.0f) * s.dist);
+    s.alpha = 1.0f - s.e;                                                // :317
   }
   s.p = s.alpha * T;                                                     // :320
   return s;
@@ -72,6 +74,12 @@ __device__ __forceinline__ float plade_accumulate(float p, float rs, float dv, f
   }
   Sd += p * dv;
   return p;
+}
+// Backward: d loss / d pi_n at one pixel from gD = d loss / d disp — through u_n = pi_n / sigma_n with the mixture (d disp / d u_n =
+// (d_n - disp) / S), directly without.  Both passes of plade_bwd_kernel take it from here: their sums must meet in the same values.
+template <bool MIX>
+__device__ __forceinline__ float plade_g_p(float gD, float dv, float dsp, float sw, float sg) {
+  return MIX ? gD * (dv - dsp) / sw / sg : gD * dv;
 }
 // and the pixel's results once every plane is in; sw is the stash (sum of the weights, 1 without the mixture)
 template <bool MIX>

@@ -9,8 +9,12 @@
 // The reference runs ~20 full-tensor ATen passes (two cats, a cumprod, ...).  One thread owns one pixel (four with 16-byte
 // accesses where the shapes allow) and streams its planes once; pi / probability are produced on demand
 // (pd_plade_tail_layers).  Backward: with p_n = alpha_n T_n, g_alpha_n = g_p_n T_n - (sum_{k>n} g_p_k p_k) / (1 - alpha_n +
-// 1e-10), and sum_k g_p_k p_k is known in closed form — 0 with the mixture weights (d disp / d u_k = (d_k - disp) / S sums
-// to zero against u), g_disp * disp without — so the backward is one front-to-back pass too; the distance gradient
+// 1e-10).  The sum over the planes BEHIND n is taken front to back as total - prefix_n, and it is tiny next to both wherever the
+// planes in front hold the probability (an occluded plane, an opaque one): a first pass over the conv outputs forms the total of
+// the very terms the second pass adds up again, both in fp64, so that the difference keeps the relative accuracy of its own terms.
+// (The closed form of the total — 0 with the mixture weights, g_disp * disp without — is right to 1e-7 of the LARGEST term only,
+// as is an fp32 prefix: measured per element, g_raw_logits was 5e-3 .. 3e-2 and the per-plane g_disp_layered 6e-4 away from fp64
+// where the reference's own fp32 run is 4e-5; tests/test_tail_forms.py, profiles/tail_form_parity.md.)  The distance gradient
 // reaches disp_layered through the two depth layers it subtracts.
 // PD_TAIL_BF16: raw_logits / raw_sigma, logits / sigma and their gradients hold bf16 (storage type ST = Bf16; the rule of
 // pd_decoder_tail.hip: exact widening, the fp32 arithmetic in the same order, one rounding per bf16 output element); dists and
@@ -116,10 +120,29 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
     dsp = ldv<PX>(disp + (long)b * a.HW + pix);
     gD = tail_upstream<PX>(g_disp, g_depth, (long)b * a.HW + pix, dsp, c);
   }
-  float T[PX], zc[PX], prefix[PX], gprev[PX];
+  float T[PX], zc[PX], gprev[PX];
+  double total[PX], prefix[PX];   // sum_k g_p_k p_k over all planes / over the planes up to n: products and sums in fp64
   Px<PX> dv = plade_disp<PX>(a, b, 0, px0);
 #pragma unroll
-  for (int j = 0; j < PX; ++j) { T[j] = 1.0f; zc[j] = c / dv.v[j]; prefix[j] = 0.0f; gprev[j] = 0.0f; }
+  for (int j = 0; j < PX; ++j) { T[j] = 1.0f; zc[j] = c / dv.v[j]; total[j] = 0.0; }
+  if (active) {   // first pass: the total, from the values the second pass forms again (plade_step, plade_g_p)
+    for (int n = 0; n < N; ++n) {
+      PladeOperands<PX> q;
+      plade_operands<ST, MIX, PX>(a, b, n, px0, dv, q);
+#pragma unroll
+      for (int j = 0; j < PX; ++j) {
+        const PladeStep s = plade_step(n == N - 1, c, q.dn.v[j], q.rl.v[j], r.v[j], zc[j], T[j]);
+        const float sg = MIX ? clamp_sigma(sigmoid_f(q.rs.v[j])) : 1.0f;
+        total[j] += (double)plade_g_p<MIX>(gD.v[j], dv.v[j], dsp.v[j], sw.v[j], sg) * (double)s.p;
+        T[j] *= plade_keep(s.alpha);
+        zc[j] = s.zn;
+      }
+      dv = q.dn;
+    }
+    dv = plade_disp<PX>(a, b, 0, px0);
+  }
+#pragma unroll
+  for (int j = 0; j < PX; ++j) { T[j] = 1.0f; zc[j] = c / dv.v[j]; prefix[j] = 0.0; gprev[j] = 0.0f; }
   for (int n = 0; n < N; ++n) {
     const bool last = (n == N - 1);
     float gd_sum = 0.0f;
@@ -134,27 +157,25 @@ __global__ __launch_bounds__(kBlock) void plade_bwd_kernel(PladeArgs a, const fl
       for (int j = 0; j < PX; ++j) {
         const PladeStep s = plade_step(last, c, q.dn.v[j], q.rl.v[j], r.v[j], zc[j], T[j]);
         const float alpha = s.alpha, dist = s.dist, p = s.p, rl = q.rl.v[j];
-        float g_p, gd_direct, rtot;
+        float sg = 1.0f, gd_direct;
         if (MIX) {
-          const float sgu = sigmoid_f(q.rs.v[j]), sg = clamp_sigma(sgu);
+          const float sgu = sigmoid_f(q.rs.v[j]);
+          sg = clamp_sigma(sgu);
           const float u = p / sg;
           const float g_u = gD.v[j] * (dv.v[j] - dsp.v[j]) / sw.v[j];      // d disp / d u_n = (d_n - disp) / S
-          g_p = g_u / sg;
           const float gsig = gs.v[j] - g_u * u / sg;                       // d u / d sigma = -u / sigma
           o_s.v[j] = (sgu == sg) ? gsig * sgu * (1.0f - sgu) : 0.0f;       // clamp gate (inclusive bounds), sigmoid'
           gd_direct = gD.v[j] * u / sw.v[j];                               // d disp / d d_n = probability_n
-          rtot = 0.0f;                                                     // sum_k g_p_k p_k = g_disp (disp - disp)
         } else {
-          g_p = gD.v[j] * dv.v[j];
           gd_direct = gD.v[j] * p;
-          rtot = gD.v[j] * dsp.v[j];
         }
-        prefix[j] += g_p * p;
+        const float g_p = plade_g_p<MIX>(gD.v[j], dv.v[j], dsp.v[j], sw.v[j], sg);
+        prefix[j] += (double)g_p * (double)p;
         const float keep = plade_keep(alpha);
         float g_dist = 0.0f;
         if (!last) {
-          const float g_alpha = g_p * T[j] - (rtot - prefix[j]) / keep;
-          const float da = 1.0f - alpha;                                   // exp(-relu(l) dist)
+          const float g_alpha = g_p * T[j] - (float)(total[j] - prefix[j]) / keep;   // (the planes behind n)
+          const float da = s.e;                                            // exp(-relu(l) dist) = d alpha / d (relu(l) dist)
           o_l.v[j] = gl.v[j] + ((rl > 0.0f) ? g_alpha * dist * da : 0.0f);
           g_dist = gt.v[j] + g_alpha * fmaxf(rl, 0.0f) * da;
         }

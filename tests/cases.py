@@ -137,6 +137,32 @@ def slice_report(got, ref64, plane_floor):
                 zero_ok=zero_abs <= (1e-6 * scale if scale > 0.0 else 1e-6), scale=scale)
 
 
+def term_report(got, ref64, allowance):
+    """Per-ELEMENT companion of rel_err for the decoder tails: every element is measured against its own ``allowance`` — the sum of
+    the absolute values of the terms the fp64 formula adds to produce it, taken from the fp64 oracle's tensors (the element's
+    conditioning; |ref| itself for a tensor that is one term, which makes it the plain relative error).
+
+      err = max |got - ref| / allowance over the elements with allowance > 0;
+      zero_abs = max |got - ref| over the others: where every term is exactly 0 (a masked logit and its gradient, sigma's gradient
+      behind a closed clamp gate) the result has to be exactly 0 as well.
+
+    ``worst`` is the index of the element that gives ``err``; ``zeros`` counts the elements with allowance 0."""
+    g, r, a = got.detach().double().cpu(), ref64.detach().double().cpu(), allowance.detach().double().cpu()
+    assert g.shape == r.shape == a.shape, (tuple(g.shape), tuple(r.shape), tuple(a.shape))
+    assert bool((a >= 0).all())
+    diff = (g - r).abs()
+    live = a > 0
+    err, worst = 0.0, None
+    if bool(live.any()):
+        q = torch.where(live, diff / a.clamp_min(1e-300), torch.zeros_like(diff))
+        q = torch.where(torch.isnan(q), torch.full_like(q, float("inf")), q)   # (a NaN in ``got`` is the worst error, not none)
+        flat = int(q.argmax())
+        err, worst = float(q.flatten()[flat]), tuple(int(i) for i in np.unravel_index(flat, tuple(q.shape))) if q.dim() else ()
+    dead = diff[~live]
+    zero_abs = float(torch.where(torch.isnan(dead), torch.full_like(dead, float("inf")), dead).max()) if dead.numel() else 0.0
+    return dict(err=err, zero_abs=zero_abs, zeros=int((~live).sum()), worst=worst)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # BASELINE configs[3] as the trainer runs it: all target sides, decoder-made xz planes (tests/golden/trainer_mono.npz)
 # ---------------------------------------------------------------------------------------------------------------------
