@@ -704,10 +704,10 @@ class _HomographyMatrices(torch.autograd.Function):
         ctx.save_for_backward(distance, norm, T, K, inv_K)
         ctx.mode, ctx.rows = mode, rows
         ctx.set_materialize_grads(False)   # (else autograd zero-fills gradients for the non-differentiable Rn / mask: two launches)
-        ctx.mark_non_differentiable(Rn)
         if mode == C.PD_HMAT_STEREO_ROWS:
-            ctx.mark_non_differentiable(mask)
+            ctx.mark_non_differentiable(mask, Rn)   # (one call: a second call replaces the first one's set)
             return shift, mask, Rn
+        ctx.mark_non_differentiable(Rn)
         return Hm, Rn
 
     @staticmethod
