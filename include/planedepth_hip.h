@@ -519,6 +519,40 @@ int pd_cat_flip(int B, int C, int H, int W, const float* own, const float* other
 int pd_crop_grid(int B, int H, int W, const int32_t* params, float* grid, pd_stream_t stream);
 
 /*
+ * The images of the data pipeline on the device (pd_input_pipeline.hip): ToTensor, RandomResizeCrop / Resize, RandomGamma,
+ * RandomBrightness and RandomColorBrightness of datasets/pair_transforms.py (:27-56, :66-84, :94-141) as mono_dataset.py:149-187
+ * drives them, from the decoded frames to the cropped windows in one launch; the resized full frame is never formed.
+ *   src        the B * V decoded frames (V views per sample), padded to one size: PD_SRC_U8_HWC [B,V,Hmax,Wmax,3] uint8, or
+ *              PD_SRC_F32_CHW [B,V,3,Hmax,Wmax] fp32 (values as ToTensor leaves them)
+ *   src_hw     [B][2] int32 (hs, ws): the true frame size of sample b, shared by its views.  Rows / columns beyond it are padding
+ *              and never influence a result (nor are they read)
+ *   crop       [B][4] int32 (full_w, full_h, w0, h0), the layout of pd_crop_grid: the frame is resized to full_h x full_w and the
+ *              H x W window at (h0, w0) is kept.  Resize is full = (W, H), origin 0
+ *   flags      [B] int32, pd_pipe_flags: which augmentation stages run for sample b, and the horizontal flip (the source is read
+ *              mirrored, ws - 1 - x: the transpose mono_dataset.py applies before everything else)
+ *   aug        [B][V][5] fp32 (gamma, brightness, c0, c1, c2)
+ *   color      [B,V,3,H,W]: bicubic (A = -0.75, align_corners=True), clamped to [0, 1].  The source coordinate
+ *              (y + h0) (hs - 1) / (full_h - 1) is split into floor and fraction by an integer division, exactly; uint8 / 255 is
+ *              correctly rounded; full == source copies the source bit for bit
+ *   color_aug  [B,V,3,H,W]: color, then x^gamma (PD_PIPE_GAMMA), min(x * brightness, 1) (PD_PIPE_BRIGHTNESS), min(x * c_ch, 1)
+ *              (PD_PIPE_CHANNEL), in this order; a stage whose bit is clear is skipped, so flags without stage bits give color's bits
+ * Memory: every tap is clamped into the true frame and hs, ws into Hmax, Wmax, whatever the parameter tensors hold, so no byte
+ * outside `src` is read for any parameter values; writes cover exactly the two outputs.
+ * Limits, refused on the host: B * V <= 65535, H, W <= 65536, Hmax, Wmax <= 32768, Hmax * Wmax * 12 < 2^31.
+ *
+ * pd_resize_crop_nearest: the depth_gt branch (:50-54, :79-82).  src [B,1,Hd,Wd] fp32 with its own src_hw -> out [B,1,H,W] by
+ * ATen's legacy nearest index min((int)floorf((float)dst * scale), in - 1), scale = (float)in / (float)full in fp32, with the same
+ * crop window and flip bit (np.fliplr of the source).  A selection: bit-exact.
+ */
+enum pd_src_format { PD_SRC_U8_HWC = 0, PD_SRC_F32_CHW = 1 };
+enum pd_pipe_flags { PD_PIPE_GAMMA = 1, PD_PIPE_BRIGHTNESS = 2, PD_PIPE_CHANNEL = 4, PD_PIPE_FLIP = 8 };
+int pd_resize_crop_augment(int B, int V, int Hmax, int Wmax, int H, int W, int src_dtype, const void* src, const int32_t* src_hw,
+                           const int32_t* crop, const int32_t* flags, const float* aug, float* color, float* color_aug,
+                           pd_stream_t stream);
+int pd_resize_crop_nearest(int B, int Hd, int Wd, int H, int W, const float* src, const int32_t* src_hw, const int32_t* crop,
+                           const int32_t* flags, float* out, pd_stream_t stream);
+
+/*
  * The decoders' disparity levels (networks/depth_decoder.py:147-152, networks/plade_net.py:280-285), one launch each way:
  *   disp[m] = disp_max * (disp_min / disp_max) ** (levels[m] / (no_levels - 1));   distance[m] = dist_num / disp[m]
  * over M = B * N values (levels = arange(no_levels) + the learnt residual; dist_num = 0.1 * 0.58 * W, `distance` may be NULL).

@@ -29,6 +29,8 @@ PD_IMPL_EXACT_ROWS = 6
 PD_EVAL_POST_PROCESS, PD_EVAL_EIGEN, PD_EVAL_MEDIAN, PD_EVAL_TRAINER = 1, 2, 4, 8
 PD_EVAL_TILE = 16384   # GT pixels per tile of pd_depth_eval (enum in the header)
 PD_DTYPE_F32, PD_DTYPE_BF16 = 0, 1   # pd_dtype: the element type of pd_feature_distance_*'s feature tensors
+PD_SRC_U8_HWC, PD_SRC_F32_CHW = 0, 1   # pd_src_format: the decoded frames pd_resize_crop_augment reads
+PD_PIPE_GAMMA, PD_PIPE_BRIGHTNESS, PD_PIPE_CHANNEL, PD_PIPE_FLIP = 1, 2, 4, 8   # pd_pipe_flags, per sample
 
 
 class SweepDesc(ctypes.Structure):
@@ -122,6 +124,8 @@ SIGNATURES = {
     "pd_plane_geometry_fwd": (_I, [_I] * 6 + [_F] * 4 + [_P] * 7),
     "pd_plane_geometry_bwd": (_I, [_I] * 6 + [_F] * 4 + [_P] * 7),
     "pd_crop_grid": (_I, [_I] * 3 + [_P, _P, _P]),
+    "pd_resize_crop_augment": (_I, [_I] * 7 + [_P] * 8),
+    "pd_resize_crop_nearest": (_I, [_I] * 5 + [_P] * 6),
     "pd_selftest_division": (_I, [_F, _I, _F, _F, _P, _P]),
     "pd_experiments": (_I, []),
     "pd_build_flags": (_I, []),
