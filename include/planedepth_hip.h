@@ -553,6 +553,39 @@ int pd_resize_crop_nearest(int B, int Hd, int Wd, int H, int W, const float* src
                            const int32_t* flags, float* out, pd_stream_t stream);
 
 /*
+ * The decoders' positional encoding of inputs["grid"] (pd_grid_embed.hip): `epconv` on the full-resolution grid followed by
+ * F.interpolate(bilinear, align_corners=True) to every decoder level (networks/depth_decoder.py:123-139, networks/pose_net.py:137-140,
+ * networks/plade_net.py:150-158), as ONE launch that evaluates the embedding at the four source points of each output pixel and
+ * blends: nothing of the size [B,.,H,W] is written or kept.
+ *   grid       [B,2,H,W] fp32, any values, not only windows of one linspace (the flipped half of a batch holds the negated, mirrored x)
+ *   sizes      n_levels pairs (h_l, w_l) of int32 ON THE HOST, read before the call returns; 1 <= n_levels <= 8, every side >= 1, not
+ *              required to divide H or W, and a level may be as large as the source or larger
+ *   kind       PD_EMBED_NEURAL: e1 = ELU(W1 g + b1) with 16 hidden channels, out = ELU(W2 e1 + b2), 1 <= E <= 16 (ELU: alpha = 1, expm1
+ *              on the negative branch; `multires` is ignored).  PD_EMBED_FREQUENCY: cat(g, sin(g 2^k), cos(g 2^k)), k < multires, in
+ *              layers.py:308-354's channel order, E = 2 + 4 multires, multires <= 16.  PD_EMBED_IDENTITY: the grid itself, E = 2.  The
+ *              last two read no `params` and have no backward
+ *   params     one block of 48 + 17 E floats: W1 [16,2], b1 [16], W2 [E,16], b2 [E]
+ *   out        the levels' [B,E,h_l,w_l] one after the other in one flat buffer of B E sum(h_l w_l) floats
+ * Resampling as ATen's upsample_bilinear2d: blend along x, then along y.  The source coordinate y (H - 1) / (h_l - 1) is split into
+ * floor and fraction by an integer division (exact at any size; row 0, fraction 0 for h_l = 1); the second tap is clamped to the last
+ * row / column.  A level of the source's size reproduces the embedding at the pixel, the identity kind the grid's bits.
+ *
+ * pd_grid_embed_bwd (neural kind): g_out in the forward's flat layout -> g_params, the gradient in the layout of `params`
+ * (g_W1 [16,2], g_b1 [16], g_W2 [E,16], g_b2 [E]).  z1, e1, z2 are recomputed per tap from the grid: the forward leaves nothing behind.
+ * No float atomics: private sums per lane, a wave and workgroup reduction into `workspace`
+ * (pd_grid_embed_bwd_workspace_floats(B, E, n_levels, sizes) floats = min(ceil(B sum(h_l w_l) / 256), 512) (48 + 17 E); host only,
+ * callable without a GPU, 0 for arguments the backward refuses), then a fixed-order sum: two runs give the same bits.  grid gets no
+ * gradient.
+ * Limits, refused on the host: H, W <= 32768, every level side <= 65536, B sum(h_l w_l) < 2^31 - 2^17.
+ */
+enum pd_embed_kind { PD_EMBED_NEURAL = 0, PD_EMBED_FREQUENCY = 1, PD_EMBED_IDENTITY = 2 };
+int pd_grid_embed_fwd(int B, int H, int W, int kind, int E, int multires, int n_levels, const int32_t* sizes, const float* grid,
+                      const float* params, float* out, pd_stream_t stream);
+size_t pd_grid_embed_bwd_workspace_floats(int B, int E, int n_levels, const int32_t* sizes);
+int pd_grid_embed_bwd(int B, int H, int W, int E, int n_levels, const int32_t* sizes, const float* grid, const float* params,
+                      const float* g_out, float* g_params, float* workspace, pd_stream_t stream);
+
+/*
  * The decoders' disparity levels (networks/depth_decoder.py:147-152, networks/plade_net.py:280-285), one launch each way:
  *   disp[m] = disp_max * (disp_min / disp_max) ** (levels[m] / (no_levels - 1));   distance[m] = dist_num / disp[m]
  * over M = B * N values (levels = arange(no_levels) + the learnt residual; dist_num = 0.1 * 0.58 * W, `distance` may be NULL).

@@ -31,6 +31,7 @@ PD_EVAL_TILE = 16384   # GT pixels per tile of pd_depth_eval (enum in the header
 PD_DTYPE_F32, PD_DTYPE_BF16 = 0, 1   # pd_dtype: the element type of pd_feature_distance_*'s feature tensors
 PD_SRC_U8_HWC, PD_SRC_F32_CHW = 0, 1   # pd_src_format: the decoded frames pd_resize_crop_augment reads
 PD_PIPE_GAMMA, PD_PIPE_BRIGHTNESS, PD_PIPE_CHANNEL, PD_PIPE_FLIP = 1, 2, 4, 8   # pd_pipe_flags, per sample
+PD_EMBED_NEURAL, PD_EMBED_FREQUENCY, PD_EMBED_IDENTITY = 0, 1, 2   # pd_embed_kind: what pd_grid_embed_fwd evaluates at a grid point
 
 
 class SweepDesc(ctypes.Structure):
@@ -126,6 +127,9 @@ SIGNATURES = {
     "pd_crop_grid": (_I, [_I] * 3 + [_P, _P, _P]),
     "pd_resize_crop_augment": (_I, [_I] * 7 + [_P] * 8),
     "pd_resize_crop_nearest": (_I, [_I] * 5 + [_P] * 6),
+    "pd_grid_embed_fwd": (_I, [_I] * 7 + [_P] * 5),
+    "pd_grid_embed_bwd_workspace_floats": (ctypes.c_size_t, [_I] * 3 + [_P]),
+    "pd_grid_embed_bwd": (_I, [_I] * 5 + [_P] * 7),
     "pd_selftest_division": (_I, [_F, _I, _F, _F, _P, _P]),
     "pd_experiments": (_I, []),
     "pd_build_flags": (_I, []),

@@ -88,7 +88,7 @@ int reduce_partials(const float* partials, float* out, int nblk, int M, int B, h
 // Kept for callers that check them: the experiments library and the timing-ablation builds are gone, so both are always 0.
 extern "C" int pd_experiments(void) { return 0; }
 extern "C" int pd_build_flags(void) { return 0; }
-extern "C" int pd_version(void) { (void)pd::switches(); return 280; /* 0.2.8: pd_resize_crop_augment, pd_resize_crop_nearest (pd_input_pipeline.hip: the input pipeline on the device; pd_src_format, pd_pipe_flags); 0.2.7: removed the experiments library (PD_EXPERIMENTS; PD_IMPL_TILE always PD_ERR_UNSUPPORTED), the timing-ablation and trace builds (PD_DIAGNOSTICS, PD_ABLATE, PD_FS_ABL, PD_FS_TRACE, PD_FS_LDS_PAD, PD_STREAM_ABL), the settled build switches (PD_FS_SHRING, PD_FS_FIXREF, PD_FS_PRIO, PD_FS_PRIO_PERIOD, PD_FS_REVERSE, PD_FS_BALANCE, PD_FS_REGROUP, PD_FS_ROUNDS, PD_STREAM_DEAD, PD_STREAM_PRIO, PD_VARIANT, PD_FWD_PF, PD_BWD_PF, PD_PF_DEPTH, PD_BWD_PF_DEPTH, PD_TC_PREFETCH, PD_BWD_REVERSE, PD_BWD_HANDOVER, PD_XCD_BAND, PD_PP_CHAIN_SPLIT, PD_GEN_NOSCATTER, PD_GS_NOSCATTER) and the environment switches PD_UNI_CHUNK, PD_ROW_WAVES, PD_NO_ROWPAIR, PD_FWD_STREAM, PD_PP_ROWS, PD_PP_CHAIN; the plane-uniform backward's workspace is smaller; 0.2.6: pd_post_process (+ _workspace_floats), pd_pp_combine, pd_plane_levels_fwd/bwd, PD_PP_SEG (segment-form post-process warps), homography row products in torch.matmul's rounding order; 0.2.5: pd_build_flags (timing-ablation switches need -DPD_DIAGNOSTICS), pd_plane_sweep_bwd_tail, pd_sweep_bwd_tail_fuses, pd_sweep_bwd_plane_adds, pd_sweep_auto_row_eps, PD_BWD_PLANE_ZEROED, PD_IMPL_EXACT_ROWS, PD_ROW_EPS; 0.2.4: pd_uniform_fwd_pair / pd_uniform_bwd_pair (pd_sweep_view), pd_plade_tail_*, PD_PH_MEAN_ZEROED; 0.2.3: segment-stream forward (pd_plane_sweep_fwdstream.hip; PD_IMPL_ROWS1 selects the plane-group forward too), pd_source_hash; 0.2.2: gather backward for per-plane homographies (pd_debug_gather_flags), pd_uniform_gather_pair + PD_BWD_DEFER_GATHER, packed wide-row context; 0.2.1: row-stream backward, PD_IMPL_UNIFORM_DIRECT, pd_experiments, environment switches read once; 0.2.0: PD_HOMO_UNIFORM, PD_BWD_ACCUMULATE, pd_homography_matrices_*, pd_masked_photometric_*, pd_crop_grid; 0.1.1: fused mean of ph_map */ }
+extern "C" int pd_version(void) { (void)pd::switches(); return 290; /* 0.2.9: pd_grid_embed_fwd, pd_grid_embed_bwd, pd_grid_embed_bwd_workspace_floats (pd_grid_embed.hip: the decoders' positional encoding of the grid, embedding and bilinear pyramid in one launch; pd_embed_kind); 0.2.8: pd_resize_crop_augment, pd_resize_crop_nearest (pd_input_pipeline.hip: the input pipeline on the device; pd_src_format, pd_pipe_flags); 0.2.7: removed the experiments library (PD_EXPERIMENTS; PD_IMPL_TILE always PD_ERR_UNSUPPORTED), the timing-ablation and trace builds (PD_DIAGNOSTICS, PD_ABLATE, PD_FS_ABL, PD_FS_TRACE, PD_FS_LDS_PAD, PD_STREAM_ABL), the settled build switches (PD_FS_SHRING, PD_FS_FIXREF, PD_FS_PRIO, PD_FS_PRIO_PERIOD, PD_FS_REVERSE, PD_FS_BALANCE, PD_FS_REGROUP, PD_FS_ROUNDS, PD_STREAM_DEAD, PD_STREAM_PRIO, PD_VARIANT, PD_FWD_PF, PD_BWD_PF, PD_PF_DEPTH, PD_BWD_PF_DEPTH, PD_TC_PREFETCH, PD_BWD_REVERSE, PD_BWD_HANDOVER, PD_XCD_BAND, PD_PP_CHAIN_SPLIT, PD_GEN_NOSCATTER, PD_GS_NOSCATTER) and the environment switches PD_UNI_CHUNK, PD_ROW_WAVES, PD_NO_ROWPAIR, PD_FWD_STREAM, PD_PP_ROWS, PD_PP_CHAIN; the plane-uniform backward's workspace is smaller; 0.2.6: pd_post_process (+ _workspace_floats), pd_pp_combine, pd_plane_levels_fwd/bwd, PD_PP_SEG (segment-form post-process warps), homography row products in torch.matmul's rounding order; 0.2.5: pd_build_flags (timing-ablation switches need -DPD_DIAGNOSTICS), pd_plane_sweep_bwd_tail, pd_sweep_bwd_tail_fuses, pd_sweep_bwd_plane_adds, pd_sweep_auto_row_eps, PD_BWD_PLANE_ZEROED, PD_IMPL_EXACT_ROWS, PD_ROW_EPS; 0.2.4: pd_uniform_fwd_pair / pd_uniform_bwd_pair (pd_sweep_view), pd_plade_tail_*, PD_PH_MEAN_ZEROED; 0.2.3: segment-stream forward (pd_plane_sweep_fwdstream.hip; PD_IMPL_ROWS1 selects the plane-group forward too), pd_source_hash; 0.2.2: gather backward for per-plane homographies (pd_debug_gather_flags), pd_uniform_gather_pair + PD_BWD_DEFER_GATHER, packed wide-row context; 0.2.1: row-stream backward, PD_IMPL_UNIFORM_DIRECT, pd_experiments, environment switches read once; 0.2.0: PD_HOMO_UNIFORM, PD_BWD_ACCUMULATE, pd_homography_matrices_*, pd_masked_photometric_*, pd_crop_grid; 0.1.1: fused mean of ph_map */ }
 extern "C" const char* pd_last_error(void) { return pd::g_err; }
 
 // What this binary was compiled from.  The marker string is also what __graft_entry__.build() looks for in the file's bytes
