@@ -9,6 +9,7 @@
 // reference runs this under the fixed (no-grad) networks and detaches the result (:466).
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 #include <utility>
 #include "pd_common.h"
 #include "pd_rowshift_common.h"
@@ -106,23 +107,36 @@ __device__ __forceinline__ void sample_group(const WarpArgs& a, const float* __r
   }
 }
 
-// f(n, value) for every plane of this pixel, in plane order
-template <bool FLIP, int NR, typename F>
-__device__ __forceinline__ void for_each_sample(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b,
-                                                int x, int y, int HW, F f) {
+// The plane-group loop of the gather and the row kernels: f(n, value) for every plane of a pixel, in plane order, kGroup planes with
+// their loads in flight and then a tail of single planes; group(n0, v) samples planes n0 .. n0 + U - 1 into v[U]
+template <typename G, typename F>
+__device__ __forceinline__ void for_each_plane(int N, G group, F f) {
   int n = 0;
-  for (; n + kGroup <= a.N; n += kGroup) {
+  for (; n + kGroup <= N; n += kGroup) {
     float v[kGroup];
-    sample_group<FLIP, NR, kGroup>(a, pb, r, b, n, x, y, HW, v);
+    group(n, v);
 #pragma unroll
     for (int u = 0; u < kGroup; ++u) f(n + u, v[u]);
   }
-  for (; n < a.N; ++n) {
+  for (; n < N; ++n) {
     float v[1];
-    sample_group<FLIP, NR, 1>(a, pb, r, b, n, x, y, HW, v);
+    group(n, v);
     f(n, v[0]);
   }
 }
+template <bool FLIP, int NR, typename F>
+__device__ __forceinline__ void for_each_sample(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b,
+                                                int x, int y, int HW, F f) {
+  for_each_plane(a.N, [&](int n0, auto& v) __attribute__((always_inline)) { sample_group<FLIP, NR>(a, pb, r, b, n0, x, y, HW, v); }, f);
+}
+
+// Online softmax over the planes: pass 1 keeps the running maximum m and the sum Z of exp(l - m), pass 2 samples again and emits
+// exp(l - m) / Z
+__device__ __forceinline__ void softmax_accumulate(float& m, float& Z, float l) {
+  if (l > m) { Z *= __expf(m - l); m = l; }
+  Z += __expf(l - m);
+}
+__device__ __forceinline__ float softmax_emit(float l, float m, float invZ) { return __expf(l - m) * invZ; }
 
 // Softmax over the planes of the warped logits.  Pass 1 finds max and sum, pass 2 samples again and writes the
 // probabilities: N writes and (cache permitting) N reads per pixel.  Measured at 4x49x192x640: 92-100 us; parking the
@@ -140,14 +154,11 @@ __global__ __launch_bounds__(kBlock) void warp_softmax_kernel(WarpArgs a, float*
   const float* pb = a.planes + (long)b * a.N * HW;
   float* ob = out + (long)b * a.N * HW + pix;
   float m = -INFINITY, Z = 0.0f;
-  auto stat = [&](int, float l) {
-    if (l > m) { Z *= __expf(m - l); m = l; }
-    Z += __expf(l - m);
-  };
+  auto stat = [&](int, float l) { softmax_accumulate(m, Z, l); };
   if (two_rows) for_each_sample<FLIP, 2>(a, pb, r, b, x, y, HW, stat);
   else          for_each_sample<FLIP, 1>(a, pb, r, b, x, y, HW, stat);
   const float invZ = 1.0f / Z;
-  auto emit = [&](int n, float l) { ob[(long)n * HW] = __expf(l - m) * invZ; };
+  auto emit = [&](int n, float l) { ob[(long)n * HW] = softmax_emit(l, m, invZ); };
   if (two_rows) for_each_sample<FLIP, 2>(a, pb, r, b, x, y, HW, emit);
   else          for_each_sample<FLIP, 1>(a, pb, r, b, x, y, HW, emit);
 }
@@ -222,18 +233,7 @@ __device__ __forceinline__ void rows_group(const WarpArgs& a, const float* __res
 template <bool FLIP, int NR, typename F>
 __device__ __forceinline__ void rows_for_each(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b,
                                               int x, int HW, F f) {
-  int n = 0;
-  for (; n + kGroup <= a.N; n += kGroup) {
-    float v[kGroup];
-    rows_group<FLIP, NR, kGroup>(a, pb, r, b, n, x, HW, v);
-#pragma unroll
-    for (int u = 0; u < kGroup; ++u) f(n + u, v[u]);
-  }
-  for (; n < a.N; ++n) {
-    float v[1];
-    rows_group<FLIP, NR, 1>(a, pb, r, b, n, x, HW, v);
-    f(n, v[0]);
-  }
+  for_each_plane(a.N, [&](int n0, auto& v) __attribute__((always_inline)) { rows_group<FLIP, NR>(a, pb, r, b, n0, x, HW, v); }, f);
 }
 
 // grid (segments of 64 pixels, H, B), one wave per workgroup
@@ -246,14 +246,11 @@ __global__ __launch_bounds__(kWave) void warp_softmax_rows_kernel(WarpArgs a, fl
   const bool active = x < a.W;
   float* ob = out + (long)b * a.N * HW + (long)y * a.W + (active ? x : 0);
   float m = -INFINITY, Z = 0.0f;
-  auto stat = [&](int, float l) {
-    if (l > m) { Z *= __expf(m - l); m = l; }
-    Z += __expf(l - m);
-  };
+  auto stat = [&](int, float l) { softmax_accumulate(m, Z, l); };
   if (r.wb != 0.0f) rows_for_each<FLIP, 2>(a, pb, r, b, x, HW, stat);
   else              rows_for_each<FLIP, 1>(a, pb, r, b, x, HW, stat);
   const float invZ = 1.0f / Z;
-  auto emit = [&](int n, float l) { if (active) ob[(long)n * HW] = __expf(l - m) * invZ; };
+  auto emit = [&](int n, float l) { if (active) ob[(long)n * HW] = softmax_emit(l, m, invZ); };
   if (r.wb != 0.0f) rows_for_each<FLIP, 2>(a, pb, r, b, x, HW, emit);
   else              rows_for_each<FLIP, 1>(a, pb, r, b, x, HW, emit);
 }
@@ -303,7 +300,6 @@ __device__ __forceinline__ float seg_shifts(const WarpArgs& a, int b, int y, int
 __device__ __forceinline__ float shift_of(float shifts, int j) {   // j: wave-uniform lane index
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(shifts), j));
 }
-template <bool FLIP>
 __device__ __forceinline__ SegPlane seg_plane(const WarpArgs& a, float sd) {
   SegPlane p;
   ShiftClass c;
@@ -356,8 +352,8 @@ __device__ __forceinline__ void seg_values(const WarpArgs& a, const RowTaps& r, 
 
 // f(n, v0, v1) for every plane of the lane's two pixels, in plane order; loads of kGroup planes in flight
 template <bool FLIP, int NR, int G, typename F>
-__device__ __forceinline__ void seg_group(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b, int xseg,
-                                          int x0, int HW, int n0, F& f, float shifts, int sbase, int nbase = 0, int nend = 1 << 30) {
+__device__ __forceinline__ void seg_group(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b, int x0, int HW,
+                                          int n0, F& f, float shifts, int sbase, int nbase = 0, int nend = 1 << 30) {
   // planes nbase + n0 .. nbase + n0 + G - 1 (those below min(nend, N)); the callback sees the index RELATIVE to nbase, which is a
   // compile-time constant where the caller's loop is unrolled
   const float x0f = (float)x0;
@@ -369,7 +365,7 @@ __device__ __forceinline__ void seg_group(const WarpArgs& a, const float* __rest
 #pragma unroll
     for (int u = 0; u < G; ++u) {
       const int n = min(nbase + n0 + u, a.N - 1);
-      sp[u] = seg_plane<FLIP>(a, shift_of(shifts, n - sbase));
+      sp[u] = seg_plane(a, shift_of(shifts, n - sbase));
       const float* pl = pb + (long)n * HW;
       const SegAim aim = seg_aim(FLIP ? a.W - 3 - (x0 + sp[u].k) : x0 + sp[u].k);
       adj[u] = aim.adj;
@@ -399,21 +395,21 @@ __device__ __forceinline__ void seg_group(const WarpArgs& a, const float* __rest
 // compile-time plane indices and its per-plane state stays in registers; a `break` in a pragma-unrolled loop left it in scratch);
 // NMAX == 0: a run-time loop
 template <bool FLIP, int NR, int G, typename F, int... I>
-__device__ __forceinline__ void seg_groups(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b, int xseg,
-                                           int x0, int HW, F& f, std::integer_sequence<int, I...>, int nbase, int nend, float shifts) {
-  ((nbase + I * G < min(nend, a.N) ? seg_group<FLIP, NR, G>(a, pb, r, b, xseg, x0, HW, I * G, f, shifts, 0, nbase, nend) : (void)0), ...);
+__device__ __forceinline__ void seg_groups(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b, int x0, int HW,
+                                           F& f, std::integer_sequence<int, I...>, int nbase, int nend, float shifts) {
+  ((nbase + I * G < min(nend, a.N) ? seg_group<FLIP, NR, G>(a, pb, r, b, x0, HW, I * G, f, shifts, 0, nbase, nend) : (void)0), ...);
 }
 template <bool FLIP, int NR, int NMAX, typename F, int G = kGroup>   // G planes' loads in flight per wave
-__device__ __forceinline__ void seg_for_each(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b, int xseg,
-                                             int x0, int HW, F f, int nbase = 0, int nend = 1 << 30) {
+__device__ __forceinline__ void seg_for_each(const WarpArgs& a, const float* __restrict__ pb, const RowTaps& r, int b, int x0, int HW,
+                                             F f, int nbase = 0, int nend = 1 << 30) {
   if constexpr (NMAX > 0) {   // (at most 64 planes: one register of shifts)
     const float shifts = seg_shifts(a, b, r.y, 0);
-    seg_groups<FLIP, NR, G>(a, pb, r, b, xseg, x0, HW, f, std::make_integer_sequence<int, (NMAX + G - 1) / G>{}, nbase, nend, shifts);
+    seg_groups<FLIP, NR, G>(a, pb, r, b, x0, HW, f, std::make_integer_sequence<int, (NMAX + G - 1) / G>{}, nbase, nend, shifts);
   } else {
     float shifts = 0.0f;
     for (int n0 = 0; n0 < a.N; n0 += G) {
       if ((n0 & (kWave - 1)) == 0) shifts = seg_shifts(a, b, r.y, n0);   // (G divides 64)
-      seg_group<FLIP, NR, G>(a, pb, r, b, xseg, x0, HW, n0, f, shifts, n0 & ~(kWave - 1));
+      seg_group<FLIP, NR, G>(a, pb, r, b, x0, HW, n0, f, shifts, n0 & ~(kWave - 1));
     }
   }
 }
@@ -433,26 +429,41 @@ __device__ __forceinline__ SegItem seg_item(const WarpArgs& a, int B) {
   return s;
 }
 
+// The softmax with all planes of a lane's pixel pair in registers: NS slots per pixel, -inf where no plane was kept; the maxima and
+// sums are the caller's locals (as members of a struct beside the slots they cost the unrolled kernels a VGPR and scratch).
+template <int NS>
+__device__ __forceinline__ void slots_clear(float (&l0)[NS], float (&l1)[NS]) {
+#pragma unroll
+  for (int n = 0; n < NS; ++n) l0[n] = l1[n] = -INFINITY;
+}
+template <int NS>
+__device__ __forceinline__ void slots_keep(float (&l0)[NS], float (&l1)[NS], float& m0, float& m1, int n, float v0, float v1) {
+#pragma unroll
+  for (int q = 0; q < NS; ++q) if (q == n) { l0[q] = v0; l1[q] = v1; }   // (n is a compile-time constant once unrolled)
+  m0 = fmaxf(m0, v0); m1 = fmaxf(m1, v1);
+}
+// slots -> exp(slot - m), Z = their sum (an empty slot adds exp(-inf) = 0).  EMPTY_OK: no slot may have been kept at all (a part
+// without planes: m = -inf) — exp(-inf - -inf) is guarded to 0, Z = 0
+template <bool EMPTY_OK, int NS>
+__device__ __forceinline__ void slots_exp(float (&l0)[NS], float (&l1)[NS], float m0, float m1, float& Z0, float& Z1) {
+  Z0 = Z1 = 0.0f;
+#pragma unroll
+  for (int n = 0; n < NS; ++n) {
+    l0[n] = (EMPTY_OK && m0 == -INFINITY) ? 0.0f : __expf(l0[n] - m0);
+    l1[n] = (EMPTY_OK && m1 == -INFINITY) ? 0.0f : __expf(l1[n] - m1);
+    Z0 += l0[n]; Z1 += l1[n];
+  }
+}
+
 template <bool FLIP, int NR, int NMAX>
 __device__ __forceinline__ void seg_softmax_body(const WarpArgs& a, const SegItem& it, const RowTaps& r, float* __restrict__ out) {
   const int HW = a.H * a.W, lane = threadIdx.x & (kWave - 1);
   const int x0 = it.xseg + 2 * lane;
   const float* pb = a.planes + (long)it.b * a.N * HW;
-  float l0[NMAX], l1[NMAX];
-#pragma unroll
-  for (int n = 0; n < NMAX; ++n) l0[n] = l1[n] = -INFINITY;
-  float m0 = -INFINITY, m1 = -INFINITY;
-  seg_for_each<FLIP, NR, NMAX>(a, pb, r, it.b, it.xseg, x0, HW, [&](int n, float v0, float v1) {
-#pragma unroll
-    for (int q = 0; q < NMAX; ++q) if (q == n) { l0[q] = v0; l1[q] = v1; }   // (n is a compile-time constant once unrolled)
-    m0 = fmaxf(m0, v0); m1 = fmaxf(m1, v1);
-  });
-  float Z0 = 0.0f, Z1 = 0.0f;
-#pragma unroll
-  for (int n = 0; n < NMAX; ++n) {   // (planes beyond N hold -inf: they add exp(-inf) = 0)
-    l0[n] = __expf(l0[n] - m0); l1[n] = __expf(l1[n] - m1);
-    Z0 += l0[n]; Z1 += l1[n];
-  }
+  float l0[NMAX], l1[NMAX], m0 = -INFINITY, m1 = -INFINITY, Z0, Z1;
+  slots_clear(l0, l1);
+  seg_for_each<FLIP, NR, NMAX>(a, pb, r, it.b, x0, HW, [&](int n, float v0, float v1) { slots_keep(l0, l1, m0, m1, n, v0, v1); });
+  slots_exp<false>(l0, l1, m0, m1, Z0, Z1);
   if (x0 >= a.W) return;   // (W is even: the lane's two pixels are inside or outside together)
   const float i0 = 1.0f / Z0, i1 = 1.0f / Z1;
   float* ob = out + (long)it.b * a.N * HW + (long)it.y * a.W + x0;
@@ -482,8 +493,8 @@ __global__ __launch_bounds__(kSegWaves* kWave) void warp_sum_seg_kernel(WarpArgs
   const float* pb = a.planes + (long)it.b * a.N * HW;
   float acc0 = 0.0f, acc1 = 0.0f;
   auto add = [&](int, float v0, float v1) { acc0 += v0; acc1 += v1; };
-  if (r.wb != 0.0f) seg_for_each<FLIP, 2, 0>(a, pb, r, it.b, it.xseg, x0, HW, add);
-  else              seg_for_each<FLIP, 1, 0>(a, pb, r, it.b, it.xseg, x0, HW, add);
+  if (r.wb != 0.0f) seg_for_each<FLIP, 2, 0>(a, pb, r, it.b, x0, HW, add);
+  else              seg_for_each<FLIP, 1, 0>(a, pb, r, it.b, x0, HW, add);
   if (x0 < a.W) *reinterpret_cast<float2*>(out + (long)it.b * HW + (long)it.y * a.W + x0) = make_float2(fminf(acc0, cap), fminf(acc1, cap));
 }
 
@@ -502,12 +513,15 @@ __global__ __launch_bounds__(kSegWaves* kWave) void warp_sum_seg_kernel(WarpArgs
 #ifndef PD_PP_CHAIN_G
 #define PD_PP_CHAIN_G 4
 #endif
+struct ChainSide {
+  WarpArgs w;             // the chain's first warp
+  const float* disp2;     // the second warp's disparities [B,N] ([B,N,H] with rows2) and sign
+  float sign2;
+  float* S;               // [3][B,1,H,W]: S_r with the shifts of target row r, r - 1, r + 1 (the last two with rows2 only, and only
+};                        // where that neighbour blends row r in)
 struct ChainArgs {
-  WarpArgs w[2];          // first warp of chain 0 (image, plain) / chain 1 (mirrored image, PD_PP_FLIP_SRC)
-  const float* disp2[2];  // the second warp's disparities [B,N] ([B,N,H] with rows2) and sign
-  float sign2[2];
-  float* S[2];            // [3][B,1,H,W] each: S_r with the shifts of target row r, r - 1, r + 1 (the last two with rows2 only,
-  int B, rows2;           // and only where that neighbour blends row r in)
+  ChainSide side[2];      // chain 0 (image, plain) / chain 1 (mirrored image, PD_PP_FLIP_SRC)
+  int B;
 };
 // Which targets need S of source row r: r itself always; with per-row shifts also the neighbours t = r -+ 1 whose vertical taps
 // reach r (their shift differs from row r's) — the inexact rows of the y round trip, a quarter of them at H = 192.
@@ -517,47 +531,60 @@ __device__ __forceinline__ bool chain_needs(int r, int t, int H) {
   return (q.ra == r && q.wa != 0.0f) || (q.rb == r && q.wb != 0.0f);
 }
 // the second warp's shifts of planes 0 .. 63 under target row yt, one per lane (clamp_shift, as plane_shift)
-__device__ __forceinline__ float chain_shifts(const float* __restrict__ disp2, float sign2, int rows2, int b, int N, int H, int yt,
-                                              int W) {
-  const int n = min((int)(threadIdx.x & (kWave - 1)), N - 1);
-  return clamp_shift(sign2 * disp2[rows2 ? (b * N + n) * H + yt : b * N + n], W, false);
+__device__ __forceinline__ float chain_shifts(const ChainSide& s, int rows2, int b, int yt) {
+  const int N = s.w.N, n = min((int)(threadIdx.x & (kWave - 1)), N - 1);
+  return clamp_shift(s.sign2 * s.disp2[rows2 ? (b * N + n) * s.w.H + yt : b * N + n], s.w.W, false);
 }
-
-template <bool FLIP, int NR, int NMAX, bool ROWS2>
-__device__ __forceinline__ void chain_row(const WarpArgs& a, const float* __restrict__ disp2, float sign2, int rows2_, int B, int b,
-                                          int y, const RowTaps& r, float* __restrict__ lds, float* __restrict__ S) {
-  const int W = a.W, N = a.N, HW = a.H * a.W, RS = W + 4;
-  constexpr int rows2 = ROWS2 ? 1 : 0;   // (a template flag: as a run-time one it cost the per-plane case 30-50 % — NOTEBOOK 11.4)
-  (void)rows2_;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const float* pb = a.planes + (long)b * N * HW;
-  for (int i = threadIdx.x; i < 4 * N; i += blockDim.x) {   // zero guard cells: columns -2, -1, W, W + 1 of every plane
+// The row buffer [N][W + 4]: zero guard cells at columns -2, -1, W, W + 1 of every plane are the second warp's padding
+__device__ __forceinline__ void chain_zero_guards(float* __restrict__ lds, int N, int W) {
+  const int RS = W + 4;
+  for (int i = threadIdx.x; i < 4 * N; i += blockDim.x) {
     const int n = i >> 2, g = i & 3;
     lds[n * RS + (g < 2 ? g : W + g)] = 0.0f;
   }
+}
+// The second warp's taps of planes [nb, ne) at the lane's pixels x0, x0 + 1, summed over the planes: from the row buffer, with the exact
+// per-pixel taps (make_col_tap); sh2: chain_shifts
+__device__ __forceinline__ void chain_tap_sum(const WarpArgs& a, const float* __restrict__ lds, float sh2, int nb, int ne, int x0,
+                                              float& acc0, float& acc1) {
+  const int W = a.W, RS = W + 4;
+  acc0 = acc1 = 0.0f;
+  for (int n = nb; n < ne; ++n) {
+    const float sd = shift_of(sh2, n);
+    const float* row = lds + n * RS;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const ColTap t = make_col_tap((float)(x0 + i) + sd, a.Wm1, a.rcpWm1);
+      const int cell = min(max(t.x0, -2), W) + 2;
+      const float val = row[cell] * t.w0 + row[cell + 1] * t.w1;
+      if (i == 0) acc0 += val; else acc1 += val;
+    }
+  }
+}
+__device__ __forceinline__ float2* chain_S(float* __restrict__ S, int v, int B, int b, int HW, int W, int y, int x0) {   // S map v at (b, y, x0)
+  return reinterpret_cast<float2*>(S + ((long)v * B + b) * HW + (long)y * W + x0);
+}
+
+template <bool FLIP, int NR, int NMAX, bool ROWS2>
+__device__ __forceinline__ void chain_row(const ChainSide& s, int B, int b, int y, const RowTaps& r, float* __restrict__ lds) {
+  const WarpArgs& a = s.w;
+  const int W = a.W, N = a.N, HW = a.H * a.W, RS = W + 4;
+  constexpr int rows2 = ROWS2 ? 1 : 0;   // (a template flag: as a run-time one it cost the per-plane case 30-50 % — NOTEBOOK 11.4)
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const float* pb = a.planes + (long)b * N * HW;
+  chain_zero_guards(lds, N, W);
   // (one segment per wave, no loop around the unrolled planes: inside a loop every plane's shift and descriptors are
   // loop-invariant, get hoisted, and 5 500 spilled SGPRs later the kernel lives in scratch)
   const int seg = wave;
   {
     const int xseg = seg * kSegPix, x0 = xseg + 2 * lane;
-    float l0[NMAX], l1[NMAX];
-#pragma unroll
-    for (int n = 0; n < NMAX; ++n) l0[n] = l1[n] = -INFINITY;
-    float m0 = -INFINITY, m1 = -INFINITY;
-    auto keep = [&](int n, float v0, float v1) {
-#pragma unroll
-      for (int q = 0; q < NMAX; ++q) if (q == n) { l0[q] = v0; l1[q] = v1; }
-      m0 = fmaxf(m0, v0); m1 = fmaxf(m1, v1);
-    };
+    float l0[NMAX], l1[NMAX], m0 = -INFINITY, m1 = -INFINITY, Z0, Z1;
+    slots_clear(l0, l1);
+    auto keep = [&](int n, float v0, float v1) { slots_keep(l0, l1, m0, m1, n, v0, v1); };
     // (one workgroup of nseg waves per CU: the loads in flight have to come from each wave — PD_PP_CHAIN_G planes at a time)
-    seg_for_each<FLIP, NR, NMAX, decltype(keep), PD_PP_CHAIN_G>(a, pb, r, b, xseg, x0, HW, keep);
-    float Z0 = 0.0f, Z1 = 0.0f;
-#pragma unroll
-    for (int n = 0; n < NMAX; ++n) {
-      l0[n] = __expf(l0[n] - m0); l1[n] = __expf(l1[n] - m1);
-      Z0 += l0[n]; Z1 += l1[n];
-    }
+    seg_for_each<FLIP, NR, NMAX, decltype(keep), PD_PP_CHAIN_G>(a, pb, r, b, x0, HW, keep);
+    slots_exp<false>(l0, l1, m0, m1, Z0, Z1);
     if (x0 < W) {
       const float i0 = 1.0f / Z0, i1 = 1.0f / Z1;
 #pragma unroll
@@ -570,20 +597,9 @@ __device__ __forceinline__ void chain_row(const WarpArgs& a, const float* __rest
     const int yt = (v == 0) ? y : ((v == 1) ? y - 1 : y + 1);
     if (v > 0 && !chain_needs(y, yt, a.H)) continue;
     const int x0 = seg * kSegPix + 2 * lane;
-    float acc0 = 0.0f, acc1 = 0.0f;
-    const float sh2 = chain_shifts(disp2, sign2, rows2, b, N, a.H, yt, W);
-    for (int n = 0; n < N; ++n) {
-      const float sd = shift_of(sh2, n);
-      const float* row = lds + n * RS;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const ColTap t = make_col_tap((float)(x0 + i) + sd, a.Wm1, a.rcpWm1);
-        const int cell = min(max(t.x0, -2), W) + 2;
-        const float val = row[cell] * t.w0 + row[cell + 1] * t.w1;
-        if (i == 0) acc0 += val; else acc1 += val;
-      }
-    }
-    if (x0 < W) *reinterpret_cast<float2*>(S + ((long)v * B + b) * HW + (long)y * W + x0) = make_float2(acc0, acc1);
+    float acc0, acc1;
+    chain_tap_sum(a, lds, chain_shifts(s, rows2, b, yt), 0, N, x0, acc0, acc1);
+    if (x0 < W) *chain_S(s.S, v, B, b, HW, W, y, x0) = make_float2(acc0, acc1);
   }
 }
 
@@ -593,11 +609,10 @@ __device__ __forceinline__ void chain_row(const WarpArgs& a, const float* __rest
 // leaves (max, sum of exp relative to it) per pixel in LDS, takes the segment's max / sum from the P parts after a barrier, writes
 // its planes' probabilities, and after the next barrier sums ITS planes' taps of the second warp; part 0 adds the partial sums.
 template <bool FLIP, int NR, int NPART, int P, bool ROWS2, bool ALIAS>
-__device__ __forceinline__ void chain_row_split(const WarpArgs& a, const float* __restrict__ disp2, float sign2, int rows2_, int B,
-                                                int b, int y, const RowTaps& r, float* __restrict__ lds, float* __restrict__ S) {
+__device__ __forceinline__ void chain_row_split(const ChainSide& s, int B, int b, int y, const RowTaps& r, float* __restrict__ lds) {
+  const WarpArgs& a = s.w;
   const int W = a.W, N = a.N, HW = a.H * a.W, RS = W + 4;
-  constexpr int rows2 = ROWS2 ? 1 : 0;   // (a template flag: as a run-time one it cost the per-plane case 30-50 % — NOTEBOOK 11.4)
-  (void)rows2_;
+  constexpr int rows2 = ROWS2 ? 1 : 0;   // (a template flag, as in chain_row)
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nseg = (W + kSegPix - 1) / kSegPix;
@@ -608,31 +623,13 @@ __device__ __forceinline__ void chain_row_split(const WarpArgs& a, const float* 
   // INSIDE the row buffer — while no probabilities are there yet, and after the last one has been read; two more barriers
   float2* stats = ALIAS ? reinterpret_cast<float2*>(lds) : reinterpret_cast<float2*>(lds + (size_t)N * RS);
   const float* pb = a.planes + (long)b * N * HW;
-  auto zero_guards = [&]() {
-    for (int i = threadIdx.x; i < 4 * N; i += blockDim.x) {   // zero guard cells: columns -2, -1, W, W + 1 of every plane
-      const int n = i >> 2, g = i & 3;
-      lds[n * RS + (g < 2 ? g : W + g)] = 0.0f;
-    }
-  };
-  if (!ALIAS) zero_guards();
-  const int xseg = seg * kSegPix, x0 = xseg + 2 * lane;
-  float l0[NPART], l1[NPART];
-#pragma unroll
-  for (int j = 0; j < NPART; ++j) l0[j] = l1[j] = -INFINITY;
-  float m0 = -INFINITY, m1 = -INFINITY;
-  auto keep = [&](int j, float v0, float v1) {
-#pragma unroll
-    for (int q = 0; q < NPART; ++q) if (q == j) { l0[q] = v0; l1[q] = v1; }
-    m0 = fmaxf(m0, v0); m1 = fmaxf(m1, v1);
-  };
-  seg_for_each<FLIP, NR, NPART, decltype(keep), kGroup>(a, pb, r, b, xseg, x0, HW, keep, nb, ne);
-  float Z0 = 0.0f, Z1 = 0.0f;
-#pragma unroll
-  for (int j = 0; j < NPART; ++j) {   // (slots beyond the part's planes hold -inf: exp gives 0; a part without planes: m = -inf, Z = 0)
-    l0[j] = (m0 == -INFINITY) ? 0.0f : __expf(l0[j] - m0);
-    l1[j] = (m1 == -INFINITY) ? 0.0f : __expf(l1[j] - m1);
-    Z0 += l0[j]; Z1 += l1[j];
-  }
+  if (!ALIAS) chain_zero_guards(lds, N, W);
+  const int x0 = seg * kSegPix + 2 * lane;
+  float l0[NPART], l1[NPART], m0 = -INFINITY, m1 = -INFINITY, Z0, Z1;
+  slots_clear(l0, l1);
+  auto keep = [&](int j, float v0, float v1) { slots_keep(l0, l1, m0, m1, j, v0, v1); };
+  seg_for_each<FLIP, NR, NPART, decltype(keep), kGroup>(a, pb, r, b, x0, HW, keep, nb, ne);
+  slots_exp<true>(l0, l1, m0, m1, Z0, Z1);   // (a part without planes: m = -inf, Z = 0)
   stats[part * SW + x0] = make_float2(m0, Z0);
   stats[part * SW + x0 + 1] = make_float2(m1, Z1);
   __syncthreads();
@@ -649,7 +646,7 @@ __device__ __forceinline__ void chain_row_split(const WarpArgs& a, const float* 
   const float c0 = (m0 == -INFINITY) ? 0.0f : __expf(m0 - M0) / T0, c1 = (m1 == -INFINITY) ? 0.0f : __expf(m1 - M1) / T1;
   if (ALIAS) {   // every wave has its statistics in registers before the first probability overwrites them
     __syncthreads();
-    zero_guards();
+    chain_zero_guards(lds, N, W);
   }
   if (x0 < W) {
 #pragma unroll
@@ -666,19 +663,8 @@ __device__ __forceinline__ void chain_row_split(const WarpArgs& a, const float* 
     need[v] = (v == 0) || chain_needs(y, yt, a.H);
     accv[v][0] = accv[v][1] = 0.0f;
     if (!need[v]) continue;
-    float acc0 = 0.0f, acc1 = 0.0f;
-    const float sh2 = chain_shifts(disp2, sign2, rows2, b, N, a.H, yt, W);
-    for (int n = nb; n < ne; ++n) {
-      const float sd = shift_of(sh2, n);
-      const float* row = lds + n * RS;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const ColTap t = make_col_tap((float)(x0 + i) + sd, a.Wm1, a.rcpWm1);
-        const int cell = min(max(t.x0, -2), W) + 2;
-        const float val = row[cell] * t.w0 + row[cell + 1] * t.w1;
-        if (i == 0) acc0 += val; else acc1 += val;
-      }
-    }
+    float acc0, acc1;
+    chain_tap_sum(a, lds, chain_shifts(s, rows2, b, yt), nb, ne, x0, acc0, acc1);
     accv[v][0] = acc0; accv[v][1] = acc1;
     if (!ALIAS) {   // the partial sums go through the statistics' buffer, variant by variant
       if (part > 0) stats[part * SW + x0] = make_float2(acc0, acc1);
@@ -686,7 +672,7 @@ __device__ __forceinline__ void chain_row_split(const WarpArgs& a, const float* 
       if (part == 0 && x0 < W) {
 #pragma unroll
         for (int q = 1; q < P; ++q) { const float2 o = stats[q * SW + x0]; acc0 += o.x; acc1 += o.y; }
-        *reinterpret_cast<float2*>(S + ((long)v * B + b) * HW + (long)y * W + x0) = make_float2(acc0, acc1);
+        *chain_S(s.S, v, B, b, HW, W, y, x0) = make_float2(acc0, acc1);
       }
       if (ROWS2) __syncthreads();   // (the partial sums of the next variant go into the same buffer)
     }
@@ -704,41 +690,44 @@ __device__ __forceinline__ void chain_row_split(const WarpArgs& a, const float* 
         float acc0 = accv[v][0], acc1 = accv[v][1];
 #pragma unroll
         for (int q = 1; q < P; ++q) { const float2 o = stats[(v * P + q) * SW + x0]; acc0 += o.x; acc1 += o.y; }
-        *reinterpret_cast<float2*>(S + ((long)v * B + b) * HW + (long)y * W + x0) = make_float2(acc0, acc1);
+        *chain_S(s.S, v, B, b, HW, W, y, x0) = make_float2(acc0, acc1);
       }
     }
   }
 }
 
+// (The item decode and the (FLIP, NR) dispatch are spelled out in both kernels: behind one helper that hands FLIP and NR to a generic
+// lambda, the irregular planes' second-row term `A wa + B wb` was contracted the other way round in the second pixel of a lane — one
+// ulp in the NR = 2 rows of S; profiles/postprocess_refactor_ab.md.)
 template <int NPART, int P, bool ROWS2, bool ALIAS>
 __global__ __launch_bounds__(1024) void pp_chain_split_kernel(ChainArgs c) {
   extern __shared__ float chain_lds[];
-  const int H = c.w[0].H;
+  const int H = c.side[0].w.H;
   const int item = blockIdx.x;
   const int y = item % H, b = (item / H) % c.B, chain = item / (H * c.B);
   const RowTaps r = row_taps(y, H);
   if (chain == 0) {
-    if (r.wb != 0.0f) chain_row_split<false, 2, NPART, P, ROWS2, ALIAS>(c.w[0], c.disp2[0], c.sign2[0], c.rows2, c.B, b, y, r, chain_lds, c.S[0]);
-    else              chain_row_split<false, 1, NPART, P, ROWS2, ALIAS>(c.w[0], c.disp2[0], c.sign2[0], c.rows2, c.B, b, y, r, chain_lds, c.S[0]);
+    if (r.wb != 0.0f) chain_row_split<false, 2, NPART, P, ROWS2, ALIAS>(c.side[0], c.B, b, y, r, chain_lds);
+    else              chain_row_split<false, 1, NPART, P, ROWS2, ALIAS>(c.side[0], c.B, b, y, r, chain_lds);
   } else {
-    if (r.wb != 0.0f) chain_row_split<true, 2, NPART, P, ROWS2, ALIAS>(c.w[1], c.disp2[1], c.sign2[1], c.rows2, c.B, b, y, r, chain_lds, c.S[1]);
-    else              chain_row_split<true, 1, NPART, P, ROWS2, ALIAS>(c.w[1], c.disp2[1], c.sign2[1], c.rows2, c.B, b, y, r, chain_lds, c.S[1]);
+    if (r.wb != 0.0f) chain_row_split<true, 2, NPART, P, ROWS2, ALIAS>(c.side[1], c.B, b, y, r, chain_lds);
+    else              chain_row_split<true, 1, NPART, P, ROWS2, ALIAS>(c.side[1], c.B, b, y, r, chain_lds);
   }
 }
 
 template <int NMAX, bool ROWS2>
 __global__ __launch_bounds__(512) void pp_chain_kernel(ChainArgs c) {   // (at most 8 waves: 256 VGPRs for the sample registers)
   extern __shared__ float chain_lds[];
-  const int H = c.w[0].H;
+  const int H = c.side[0].w.H;
   const int item = blockIdx.x;                       // (chain, image, row): the rows of one image side by side
   const int y = item % H, b = (item / H) % c.B, chain = item / (H * c.B);
   const RowTaps r = row_taps(y, H);
   if (chain == 0) {
-    if (r.wb != 0.0f) chain_row<false, 2, NMAX, ROWS2>(c.w[0], c.disp2[0], c.sign2[0], c.rows2, c.B, b, y, r, chain_lds, c.S[0]);
-    else              chain_row<false, 1, NMAX, ROWS2>(c.w[0], c.disp2[0], c.sign2[0], c.rows2, c.B, b, y, r, chain_lds, c.S[0]);
+    if (r.wb != 0.0f) chain_row<false, 2, NMAX, ROWS2>(c.side[0], c.B, b, y, r, chain_lds);
+    else              chain_row<false, 1, NMAX, ROWS2>(c.side[0], c.B, b, y, r, chain_lds);
   } else {
-    if (r.wb != 0.0f) chain_row<true, 2, NMAX, ROWS2>(c.w[1], c.disp2[1], c.sign2[1], c.rows2, c.B, b, y, r, chain_lds, c.S[1]);
-    else              chain_row<true, 1, NMAX, ROWS2>(c.w[1], c.disp2[1], c.sign2[1], c.rows2, c.B, b, y, r, chain_lds, c.S[1]);
+    if (r.wb != 0.0f) chain_row<true, 2, NMAX, ROWS2>(c.side[1], c.B, b, y, r, chain_lds);
+    else              chain_row<true, 1, NMAX, ROWS2>(c.side[1], c.B, b, y, r, chain_lds);
   }
 }
 
@@ -753,10 +742,20 @@ __device__ __forceinline__ float chain_o(const float* __restrict__ S, int B, int
   if (r.wb != 0.0f) o = o + S[((long)((!rows2 || r.rb == y) ? 0 : ((r.rb == y + 1) ? 1 : 2)) * B + b) * HW + (long)r.rb * W + x] * r.wb;
   return fminf(o, 1.0f);
 }
+// disp_pp of trainer.py:458-461 at pixel i = (b, y, x) from the two occlusion masks:
+//   mean = disp[b] * 0.5 + flip(disp[B + b]) * 0.5;  pp = mean * o_fr + disp[b] * (1 - o_fr);  pp = pp * o_l + flip(disp[B + b]) * (1 - o_l)
+// in torch's operation order (every product and sum rounded on its own).
+__device__ __forceinline__ float pp_blend(const float* __restrict__ disp, int B, int b, long HW, int W, int x, int y, long i, float ofr,
+                                          float ol) {
+#pragma clang fp contract(off)
+  const float d0 = disp[i], df = disp[((long)B + b) * HW + (long)y * W + (W - 1 - x)];
+  const float mean = d0 * 0.5f + df * 0.5f;
+  const float pp = mean * ofr + d0 * (1.0f - ofr);
+  return pp * ol + df * (1.0f - ol);
+}
 __global__ __launch_bounds__(kBlock) void pp_rows_finish_kernel(int B, int H, int W, int rows2, const float* __restrict__ S_l,
                                                                 const float* __restrict__ S_fr, const float* __restrict__ disp,
                                                                 float* __restrict__ out) {
-#pragma clang fp contract(off)
   const long HW = (long)H * W, i = (long)blockIdx.x * kBlock + threadIdx.x;
   if (i >= (long)B * HW) return;
   const int b = (int)(i / HW);
@@ -764,31 +763,19 @@ __global__ __launch_bounds__(kBlock) void pp_rows_finish_kernel(int B, int H, in
   const int y = (int)(p / W), x = (int)(p - (long)y * W);
   const RowTaps r = row_taps(y, H);
   const float ol = chain_o(S_l, B, b, HW, W, x, y, r, rows2), ofr = chain_o(S_fr, B, b, HW, W, x, y, r, rows2);
-  const float d0 = disp[i], df = disp[((long)B + b) * HW + (long)y * W + (W - 1 - x)];
-  const float mean = d0 * 0.5f + df * 0.5f;
-  float pp = mean * ofr + d0 * (1.0f - ofr);
-  pp = pp * ol + df * (1.0f - ol);
-  out[i] = pp;
+  out[i] = pp_blend(disp, B, b, HW, W, x, y, i, ofr, ol);
 }
 
-// disp_pp of trainer.py:458-461 from the two occlusion masks: one pass instead of eight elementwise launches.
-//   mean = disp[b] * 0.5 + flip(disp[B + b]) * 0.5;  pp = mean * o_fr + disp[b] * (1 - o_fr);  pp = pp * o_l + flip(disp[B + b]) * (1 - o_l)
-// in torch's operation order (every product and sum rounded on its own).
+// the blend on its own (the single warps' o_fr / o_l): one pass instead of eight elementwise launches
 __global__ __launch_bounds__(kBlock) void pp_combine_kernel(int B, int H, int W, const float* __restrict__ disp,
                                                             const float* __restrict__ o_fr, const float* __restrict__ o_l,
                                                             float* __restrict__ out) {
-#pragma clang fp contract(off)
   const long HW = (long)H * W, i = (long)blockIdx.x * kBlock + threadIdx.x;
   if (i >= (long)B * HW) return;
   const int b = (int)(i / HW);
   const long p = i - (long)b * HW;
   const int y = (int)(p / W), x = (int)(p - (long)y * W);
-  const float d0 = disp[i], df = disp[((long)B + b) * HW + (long)y * W + (W - 1 - x)];
-  const float ofr = o_fr[i], ol = o_l[i];
-  const float mean = d0 * 0.5f + df * 0.5f;
-  float pp = mean * ofr + d0 * (1.0f - ofr);
-  pp = pp * ol + df * (1.0f - ol);
-  out[i] = pp;
+  out[i] = pp_blend(disp, B, b, HW, W, x, y, i, o_fr[i], o_l[i]);
 }
 
 // pixel pairs: even width, 8-byte aligned output rows; the softmax holds 2 N samples in registers
@@ -879,6 +866,69 @@ static int no_kernel(const char* what, const pd_pp_route& r) {
   return PD_ERR_UNSUPPORTED;
 }
 
+// A route's run-time values as the kernel templates' compile-time constants: f(std::bool_constant<v>{}), and f(std::integral_constant<int,
+// V>{}) for the V of the list that r.nmax (NMAX or NPART) equals — no_kernel() if none does.  A generic lambda's call operator is
+// instantiated once per constant, so a `static` inside it exists once per kernel instantiation.
+template <typename F>
+static int dispatch_bool(bool v, F f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int... V, typename F>
+static int dispatch_nmax(const char* what, const pd_pp_route& r, F f) {
+  int rc = PD_OK;
+  return ((r.nmax == V && ((rc = f(std::integral_constant<int, V>{})), true)) || ...) ? rc : no_kernel(what, r);
+}
+
+// pd_warp_softmax / pd_warp_sum (`cap`: the sum's): the family switch, each family's grid once
+static int launch_warp(int kind, const WarpArgs& a, int B, float cap, float* out, hipStream_t stream) {
+  const bool softmax = kind == PD_PP_KIND_SOFTMAX;
+  const char* what = softmax ? "pd_warp_softmax" : "pd_warp_sum";
+  const pd_pp_route r = warp_route(kind, a, B, out);
+  return dispatch_bool(r.flip, [&](auto flip) -> int {
+    constexpr bool FLIP = decltype(flip)::value;
+    switch (r.family) {
+      case PD_PP_FAMILY_SEG: {
+        const dim3 g((unsigned)(((long)B * a.H * ceil_div(a.W, kSegPix) + kSegWaves - 1) / kSegWaves)), block(kSegWaves * kWave);
+        if (softmax)
+          return dispatch_nmax<32, 52, 64>(what, r, [&](auto nmax) {
+            warp_softmax_seg_kernel<FLIP, decltype(nmax)::value><<<g, block, 0, stream>>>(a, B, out);
+            return check_launch("warp_softmax_seg_kernel");
+          });
+        if (r.nmax != 0) return no_kernel(what, r);
+        warp_sum_seg_kernel<FLIP><<<g, block, 0, stream>>>(a, B, cap, out);
+        return check_launch("warp_sum_seg_kernel");
+      }
+      case PD_PP_FAMILY_ROWS: {
+        const dim3 g(ceil_div(a.W, kWave), a.H, B);
+        if (softmax) warp_softmax_rows_kernel<FLIP><<<g, kWave, 0, stream>>>(a, out);
+        else         warp_sum_rows_kernel<FLIP><<<g, kWave, 0, stream>>>(a, cap, out);
+        return check_launch(softmax ? "warp_softmax_rows_kernel" : "warp_sum_rows_kernel");
+      }
+      case PD_PP_FAMILY_GATHER: {
+        const dim3 g(ceil_div(a.H * a.W, kBlock), B);
+        if (softmax) warp_softmax_kernel<FLIP><<<g, kBlock, 0, stream>>>(a, out);
+        else         warp_sum_kernel<FLIP><<<g, kBlock, 0, stream>>>(a, cap, out);
+        return check_launch(softmax ? "warp_softmax_kernel" : "warp_sum_kernel");
+      }
+      default: return no_kernel(what, r);
+    }
+  });
+}
+
+// A row-chain kernel on its dynamic LDS; `granted`: the caller's static, one per kernel instantiation
+static int launch_chain(void (*kernel)(ChainArgs), LdsGrant& granted, const char* name, const ChainArgs& c, dim3 grid, dim3 block,
+                        size_t lds, hipStream_t stream) {
+  if (int rc = grant_dynamic_lds((const void*)kernel, lds, &granted, name)) return rc;
+  kernel<<<grid, block, lds, stream>>>(c);
+  return check_launch(name);
+}
+
+static int post_process_args(int B, int N, int H, int W, int flags) {   // of pd_post_process and its route query
+  PD_REQUIRE(B > 0 && N > 0 && H > 0 && W > 1, "bad shape");
+  PD_REQUIRE((flags & ~(PD_PP_DISP_DENSE | PD_PP_DISP_ROWS)) == 0, "unknown flags");
+  return PD_OK;
+}
+
 }  // namespace pd
 
 using namespace pd;
@@ -888,39 +938,7 @@ extern "C" int pd_warp_softmax(int B, int N, int H, int W, float sign, int flags
   WarpArgs a;
   if (int rc = warp_args(a, B, N, H, W, sign, flags, planes, disp)) return rc;
   PD_REQUIRE(out && out != planes, "out must be a distinct buffer");
-  const pd_pp_route r = warp_route(PD_PP_KIND_SOFTMAX, a, B, out);
-  switch (r.family) {
-    case PD_PP_FAMILY_SEG: {
-      const int nseg = ceil_div(W, kSegPix);
-      const dim3 g((unsigned)(((long)B * H * nseg + kSegWaves - 1) / kSegWaves));
-#define PD_PP_SOFTMAX_SEG(NMAX)                                                                                             \
-      do {                                                                                                                  \
-        if (r.flip) warp_softmax_seg_kernel<true, NMAX><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out);       \
-        else        warp_softmax_seg_kernel<false, NMAX><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, out);      \
-      } while (0)
-      switch (r.nmax) {
-        case 32: PD_PP_SOFTMAX_SEG(32); break;
-        case 52: PD_PP_SOFTMAX_SEG(52); break;
-        case 64: PD_PP_SOFTMAX_SEG(64); break;
-        default: return no_kernel("pd_warp_softmax", r);
-      }
-#undef PD_PP_SOFTMAX_SEG
-      return check_launch("warp_softmax_seg_kernel");
-    }
-    case PD_PP_FAMILY_ROWS: {
-      dim3 g(ceil_div(W, kWave), H, B);
-      if (r.flip) warp_softmax_rows_kernel<true><<<g, kWave, 0, (hipStream_t)stream>>>(a, out);
-      else        warp_softmax_rows_kernel<false><<<g, kWave, 0, (hipStream_t)stream>>>(a, out);
-      return check_launch("warp_softmax_rows_kernel");
-    }
-    case PD_PP_FAMILY_GATHER: {
-      dim3 grid(ceil_div(H * W, kBlock), B);
-      if (r.flip) warp_softmax_kernel<true><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, out);
-      else        warp_softmax_kernel<false><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, out);
-      return check_launch("warp_softmax_kernel");
-    }
-    default: return no_kernel("pd_warp_softmax", r);
-  }
+  return launch_warp(PD_PP_KIND_SOFTMAX, a, B, 0.0f, out, (hipStream_t)stream);
 }
 
 extern "C" int pd_warp_sum(int B, int N, int H, int W, float sign, int flags, const float* planes, const float* disp,
@@ -928,30 +946,7 @@ extern "C" int pd_warp_sum(int B, int N, int H, int W, float sign, int flags, co
   WarpArgs a;
   if (int rc = warp_args(a, B, N, H, W, sign, flags, planes, disp)) return rc;
   PD_REQUIRE(out, "NULL output");
-  const pd_pp_route r = warp_route(PD_PP_KIND_SUM, a, B, out);
-  switch (r.family) {
-    case PD_PP_FAMILY_SEG: {
-      const int nseg = ceil_div(W, kSegPix);
-      const dim3 g((unsigned)(((long)B * H * nseg + kSegWaves - 1) / kSegWaves));
-      if (r.nmax != 0) return no_kernel("pd_warp_sum", r);
-      if (r.flip) warp_sum_seg_kernel<true><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, cap, out);
-      else        warp_sum_seg_kernel<false><<<g, kSegWaves * kWave, 0, (hipStream_t)stream>>>(a, B, cap, out);
-      return check_launch("warp_sum_seg_kernel");
-    }
-    case PD_PP_FAMILY_ROWS: {
-      dim3 g(ceil_div(W, kWave), H, B);
-      if (r.flip) warp_sum_rows_kernel<true><<<g, kWave, 0, (hipStream_t)stream>>>(a, cap, out);
-      else        warp_sum_rows_kernel<false><<<g, kWave, 0, (hipStream_t)stream>>>(a, cap, out);
-      return check_launch("warp_sum_rows_kernel");
-    }
-    case PD_PP_FAMILY_GATHER: {
-      dim3 grid(ceil_div(H * W, kBlock), B);
-      if (r.flip) warp_sum_kernel<true><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, cap, out);
-      else        warp_sum_kernel<false><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, cap, out);
-      return check_launch("warp_sum_kernel");
-    }
-    default: return no_kernel("pd_warp_sum", r);
-  }
+  return launch_warp(PD_PP_KIND_SUM, a, B, cap, out, (hipStream_t)stream);
 }
 
 extern "C" int pd_warp_route(int kind, int B, int N, int H, int W, int flags, const void* out, pd_pp_route* route) {
@@ -980,8 +975,8 @@ extern "C" size_t pd_post_process_workspace_floats(int B, int N, int H, int W) {
 extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const float* logits, const float* probability,
                                const float* disp, const float* disp_layered, float* workspace, float* disp_pp, float* mask_novel,
                                pd_stream_t stream) {
-  PD_REQUIRE(B > 0 && N > 0 && H > 0 && W > 1, "bad shape");
-  PD_REQUIRE((flags & ~(PD_PP_DISP_DENSE | PD_PP_DISP_ROWS)) == 0, "unknown flags");
+  int rc;
+  if ((rc = post_process_args(B, N, H, W, flags))) return rc;
   PD_REQUIRE(logits && probability && disp && disp_layered && workspace && disp_pp && mask_novel, "NULL pointer");
   const size_t P = (size_t)H * W, img = (size_t)N * P;
   const float* dl_r = disp_layered;                                                              // the image's planes
@@ -990,80 +985,59 @@ extern "C" int pd_post_process(int B, int N, int H, int W, int flags, const floa
   float* planes = workspace;
   float* o_l = workspace + (size_t)B * img;
   float* o_fr = o_l + (size_t)B * P;
-  int rc;
+  const char* what = "pd_post_process";
+  const hipStream_t st = (hipStream_t)stream;
   const pd_pp_route r = post_process_route(B, N, H, W, flags, workspace, disp_pp);
   if (r.family == PD_PP_FAMILY_CHAIN_SPLIT || r.family == PD_PP_FAMILY_CHAIN) {
     ChainArgs c;
     const int rowsf = flags & PD_PP_DISP_ROWS;
-    if ((rc = warp_args(c.w[0], B, N, H, W, +1.0f, rowsf, logits, dl_r))) return rc;
-    if ((rc = warp_args(c.w[1], B, N, H, W, -1.0f, rowsf | PD_PP_FLIP_SRC, logits + (size_t)B * img, dl_l))) return rc;
-    c.disp2[0] = dl_l; c.sign2[0] = -1.0f;
-    c.disp2[1] = dl_r; c.sign2[1] = +1.0f;
-    c.S[0] = workspace; c.S[1] = workspace + (size_t)3 * B * P;   // [3][B,1,H,W] each
-    c.B = B; c.rows2 = r.rows2;
-    const int nseg = ceil_div(W, kSegPix);
-    const dim3 grid((unsigned)(2 * B * H));
-    const size_t chain_lds = r.lds_bytes, split_lds = r.lds_bytes;
-    if (r.family == PD_PP_FAMILY_CHAIN_SPLIT) {   // planes dealt to P = 3 waves per segment
-      const dim3 block3(3 * nseg * kWave);
-#define PD_PP_SPLIT_(NPART, R2, AL)                                                                                                 \
-      do {                                                                                                                        \
-        static LdsGrant granted;                                                                                                  \
-        if ((rc = grant_dynamic_lds((const void*)pp_chain_split_kernel<NPART, 3, R2, AL>, split_lds, &granted, "pp_chain_split_kernel"))) return rc; \
-        pp_chain_split_kernel<NPART, 3, R2, AL><<<grid, block3, split_lds, (hipStream_t)stream>>>(c);                             \
-      } while (0)
-#define PD_PP_SPLIT(NPART)                                                                              \
-      do {                                                                                              \
-        if (r.alias) { if (r.rows2) PD_PP_SPLIT_(NPART, true, true); else PD_PP_SPLIT_(NPART, false, true); } \
-        else         { if (r.rows2) PD_PP_SPLIT_(NPART, true, false); else PD_PP_SPLIT_(NPART, false, false); } \
-      } while (0)
-      switch (r.nmax) {
-        case 11: PD_PP_SPLIT(11); break;
-        case 18: PD_PP_SPLIT(18); break;
-        case 22: PD_PP_SPLIT(22); break;
-        default: return no_kernel("pd_post_process", r);
-      }
-#undef PD_PP_SPLIT_
-#undef PD_PP_SPLIT
-      if ((rc = check_launch("pp_chain_split_kernel"))) return rc;
-      pp_rows_finish_kernel<<<(unsigned)(((long)B * P + kBlock - 1) / kBlock), kBlock, 0, (hipStream_t)stream>>>(B, H, W, c.rows2, c.S[0], c.S[1], disp, disp_pp);
-      if ((rc = check_launch("pp_rows_finish_kernel"))) return rc;
-      return pd_warp_sum(B, N, H, W, +1.0f, flags, probability, dl_r, 1.0f, mask_novel, stream);                         // :463-465
-    }
-    const dim3 block(nseg * kWave);   // one wave per segment
-#define PD_PP_CHAIN_(NMAX, R2)                                                                                               \
-    do {                                                                                                                    \
-      static LdsGrant granted;                                                                                              \
-      if ((rc = grant_dynamic_lds((const void*)pp_chain_kernel<NMAX, R2>, chain_lds, &granted, "pp_chain_kernel"))) return rc;  \
-      pp_chain_kernel<NMAX, R2><<<grid, block, chain_lds, (hipStream_t)stream>>>(c);                                        \
-    } while (0)
-#define PD_PP_CHAIN(NMAX) do { if (c.rows2) PD_PP_CHAIN_(NMAX, true); else PD_PP_CHAIN_(NMAX, false); } while (0)
-    switch (r.nmax) {
-      case 32: PD_PP_CHAIN(32); break;
-      case 52: PD_PP_CHAIN(52); break;
-      case 64: PD_PP_CHAIN(64); break;
-      default: return no_kernel("pd_post_process", r);
-    }
-#undef PD_PP_CHAIN
-#undef PD_PP_CHAIN_
-    if ((rc = check_launch("pp_chain_kernel"))) return rc;
-    pp_rows_finish_kernel<<<(unsigned)(((long)B * P + kBlock - 1) / kBlock), kBlock, 0, (hipStream_t)stream>>>(B, H, W, c.rows2, c.S[0], c.S[1], disp, disp_pp);
+    if ((rc = warp_args(c.side[0].w, B, N, H, W, +1.0f, rowsf, logits, dl_r))) return rc;
+    if ((rc = warp_args(c.side[1].w, B, N, H, W, -1.0f, rowsf | PD_PP_FLIP_SRC, logits + (size_t)B * img, dl_l))) return rc;
+    c.side[0].disp2 = dl_l; c.side[0].sign2 = -1.0f;
+    c.side[1].disp2 = dl_r; c.side[1].sign2 = +1.0f;
+    c.side[0].S = workspace; c.side[1].S = workspace + (size_t)3 * B * P;   // [3][B,1,H,W] each
+    c.B = B;
+    const bool split = r.family == PD_PP_FAMILY_CHAIN_SPLIT;   // planes dealt to P = 3 waves per segment; else one wave per segment
+    const dim3 grid((unsigned)(2 * B * H)), block((split ? 3 : 1) * ceil_div(W, kSegPix) * kWave);
+    rc = dispatch_bool(r.rows2, [&](auto r2) {
+      constexpr bool R2 = decltype(r2)::value;
+      if (!split)
+        return dispatch_nmax<32, 52, 64>(what, r, [&](auto nmax) {
+          static LdsGrant granted;
+          return launch_chain(pp_chain_kernel<decltype(nmax)::value, R2>, granted, "pp_chain_kernel", c, grid, block, r.lds_bytes, st);
+        });
+      return dispatch_bool(r.alias, [&](auto alias) {
+        return dispatch_nmax<11, 18, 22>(what, r, [&](auto npart) -> int {
+          constexpr int NPART = decltype(npart)::value;
+          constexpr bool ALIAS = decltype(alias)::value;
+          // (the statistics fit beside the row buffer of at most 54 planes at any width the split chains take: no shape reaches
+          // these at 160 KiB of LDS, tests/test_post_process_routes.py — they are not instantiated)
+          if constexpr (ALIAS && NPART < 22) return no_kernel(what, r);
+          else {
+            static LdsGrant granted;
+            return launch_chain(pp_chain_split_kernel<NPART, 3, R2, ALIAS>, granted, "pp_chain_split_kernel", c, grid, block, r.lds_bytes, st);
+          }
+        });
+      });
+    });
+    if (rc) return rc;
+    pp_rows_finish_kernel<<<(unsigned)(((long)B * P + kBlock - 1) / kBlock), kBlock, 0, st>>>(B, H, W, r.rows2, c.side[0].S, c.side[1].S, disp, disp_pp);
     if ((rc = check_launch("pp_rows_finish_kernel"))) return rc;
-    return pd_warp_sum(B, N, H, W, +1.0f, flags, probability, dl_r, 1.0f, mask_novel, stream);                           // :463-465
+  } else if (r.family == PD_PP_FAMILY_SINGLE) {
+    if ((rc = pd_warp_softmax(B, N, H, W, +1.0f, flags, logits, dl_r, planes, stream))) return rc;                         // :443-446
+    if ((rc = pd_warp_sum(B, N, H, W, -1.0f, flags, planes, dl_l, 1.0f, o_l, stream))) return rc;                         // :447-449
+    if ((rc = pd_warp_softmax(B, N, H, W, -1.0f, flags | PD_PP_FLIP_SRC, logits + (size_t)B * img, dl_l, planes, stream))) return rc;   // :451-453
+    if ((rc = pd_warp_sum(B, N, H, W, +1.0f, flags, planes, dl_r, 1.0f, o_fr, stream))) return rc;                        // :454-456
+    if ((rc = pd_pp_combine(B, H, W, disp, o_fr, o_l, disp_pp, stream))) return rc;                                        // :458-461
+  } else {
+    return no_kernel(what, r);
   }
-  if (r.family != PD_PP_FAMILY_SINGLE) return no_kernel("pd_post_process", r);
-  if ((rc = pd_warp_softmax(B, N, H, W, +1.0f, flags, logits, dl_r, planes, stream))) return rc;                         // :443-446
-  if ((rc = pd_warp_sum(B, N, H, W, -1.0f, flags, planes, dl_l, 1.0f, o_l, stream))) return rc;                         // :447-449
-  if ((rc = pd_warp_softmax(B, N, H, W, -1.0f, flags | PD_PP_FLIP_SRC, logits + (size_t)B * img, dl_l, planes, stream))) return rc;   // :451-453
-  if ((rc = pd_warp_sum(B, N, H, W, +1.0f, flags, planes, dl_r, 1.0f, o_fr, stream))) return rc;                        // :454-456
-  if ((rc = pd_pp_combine(B, H, W, disp, o_fr, o_l, disp_pp, stream))) return rc;                                        // :458-461
   return pd_warp_sum(B, N, H, W, +1.0f, flags, probability, dl_r, 1.0f, mask_novel, stream);                             // :463-465
 }
 
 extern "C" int pd_post_process_route(int B, int N, int H, int W, int flags, const void* workspace, const void* disp_pp,
                                      pd_pp_route* route) {
-  PD_REQUIRE(B > 0 && N > 0 && H > 0 && W > 1, "bad shape");
-  PD_REQUIRE((flags & ~(PD_PP_DISP_DENSE | PD_PP_DISP_ROWS)) == 0, "unknown flags");
+  if (int rc = post_process_args(B, N, H, W, flags)) return rc;
   PD_REQUIRE(route, "NULL route");
   *route = post_process_route(B, N, H, W, flags, workspace, disp_pp);
   return PD_OK;

@@ -3,7 +3,13 @@ library reads the switch once per process).  python scripts/diag_postprocess.py 
 
 --ab name=path [name=path ...]: A/B of library builds on pd_post_process instead — the libraries are loaded side by side through
 ctypes and called directly, interleaved round by round (--rounds windows of --iters calls each between two device events); per
-library the median and the spread (min .. max) of the windows, and whether each later median lies inside the first one's spread."""
+library the median and the spread (min .. max) of the windows, and whether each later median lies inside the first one's spread
+(--xz K: per-row disparities, PD_PP_DISP_ROWS).
+
+--ab ... --check: every case of tests/test_post_process_routes.py's CASES table through the libraries on the same inputs —
+pd_post_process (disp_pp, mask_novel) and pd_warp_softmax / pd_warp_sum for the four (sign, flip) combinations — compared on the
+raw bits against the first library, which first runs twice and is compared with itself (the kernels have no atomics: a difference
+there is the first library's own); exit 1 on any differing bit."""
 import argparse
 import ctypes
 import json
@@ -16,23 +22,80 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from planedepth_amd import ops  # noqa: E402
 
 
-def ab(a, logits, prob, disp, dl):
+def load_libs(specs):
     from planedepth_amd import _capi as C
-    B, N, H, W = a.batch, a.planes, a.height, a.width
     libs = []
-    for spec in a.ab:
+    for spec in specs:
         name, _, path = spec.partition("=")
         lib = ctypes.CDLL(path or C.LIB_PATH)
         for fn, (res, args) in C.SIGNATURES.items():
             getattr(lib, fn).restype, getattr(lib, fn).argtypes = res, args
         libs.append((name, lib))
+    return libs
+
+
+def check(a):
+    """Every case of the route suite's table through the libraries on the same inputs, every output on the raw bits."""
+    from planedepth_amd import _capi as C
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import test_post_process_routes as T
+    libs, dev = load_libs(a.ab), torch.device("cuda:0")
+    st = C.stream_handle(dev)
+
+    def outputs(lib, c):
+        z = T.inputs(c.name)
+        f = lambda t: t.float().to(dev).contiguous()
+        nan = lambda *shape: torch.full(shape, float("nan"), device=dev)
+        B, N, H, W, fl = c.B, c.N, c.H, c.W, T.FLAG[c.form]
+        logits, prob, disp = f(z["logits"]), f(z["prob"]), f(T.disp_fill(c.name, "real"))
+        compact = f({"plane": z["lv"], "rows": z["rows"], "dense": z["dl"]}[c.form])   # the image's half comes first
+        ws = nan(int(lib.pd_post_process_workspace_floats(B, N, H, W)) + 2)
+        off = (1 if c.ws4 else 0) + (0 if ws.data_ptr() % 8 == 0 else 1)               # 8-byte aligned, or 4 (mod 8): the table's routes
+        out = {"disp_pp": nan(B, 1, H, W), "mask_novel": nan(B, 1, H, W)}
+        rc = lib.pd_post_process(B, N, H, W, fl, C.ptr(logits), C.ptr(prob), C.ptr(disp), C.ptr(compact),
+                                 ctypes.c_void_p(ws.data_ptr() + 4 * off), C.ptr(out["disp_pp"]), C.ptr(out["mask_novel"]), st)
+        assert rc == 0, lib.pd_last_error()
+        for sign, flip in T.WARP_COMBOS:
+            flf = fl | (C.PD_PP_FLIP_SRC if flip else 0)
+            sm, su = nan(B, N, H, W), nan(B, 1, H, W)
+            rc = lib.pd_warp_softmax(B, N, H, W, sign, flf, C.ptr(logits), C.ptr(compact), C.ptr(sm), st)
+            assert rc == 0, lib.pd_last_error()
+            rc = lib.pd_warp_sum(B, N, H, W, sign, flf, C.ptr(prob), C.ptr(compact), 1.0, C.ptr(su), st)
+            assert rc == 0, lib.pd_last_error()
+            out["warp_softmax %+d flip %d" % (sign, flip)], out["warp_sum %+d flip %d" % (sign, flip)] = sm, su
+        torch.cuda.synchronize()
+        return {k: v.view(torch.int32).cpu() for k, v in out.items()}
+
+    report, bad = {}, 0
+    for c in T.CASES:
+        first = outputs(libs[0][1], c)
+        arms = [(libs[0][0] + " again", outputs(libs[0][1], c))] + [(name, outputs(lib, c)) for name, lib in libs[1:]]
+        report[c.name] = {}
+        for name, got in arms:
+            diff = {k: int((got[k] != first[k]).sum()) for k in first}
+            report[c.name][name] = diff
+            bad += sum(diff.values())
+            print("%-16s %-14s vs %s: %d outputs, %d differing words%s" % (c.name, name, libs[0][0], len(diff), sum(diff.values()),
+                  "".join("  %s: %d" % kv for kv in diff.items() if kv[1])))
+    print("%d cases, %d differing 32-bit words in all" % (len(T.CASES), bad))
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump({"libraries": [n for n, _ in libs], "differing_words": report, "total": bad}, fh, indent=1)
+    return 1 if bad else 0
+
+
+def ab(a, logits, prob, disp, dl):
+    from planedepth_amd import _capi as C
+    B, N, H, W = a.batch, a.planes, a.height, a.width
+    libs = load_libs(a.ab)
     st = C.stream_handle(logits.device)
-    lv = dl[:, :, 0, 0].contiguous()                                    # per-plane disparities [2B,N]
+    # per-plane disparities [2B,N]; --xz: per-row ones [2B,N,H] (PD_PP_DISP_ROWS)
+    lv, flags = (dl[:, :, :, 0].contiguous(), C.PD_PP_DISP_ROWS) if a.xz else (dl[:, :, 0, 0].contiguous(), 0)
     ws = torch.empty(max(int(l.pd_post_process_workspace_floats(B, N, H, W)) for _, l in libs), device=logits.device)
     dpp, mn = torch.empty(B, 1, H, W, device=logits.device), torch.empty(B, 1, H, W, device=logits.device)
 
     def call(lib):
-        rc = lib.pd_post_process(B, N, H, W, 0, C.ptr(logits), C.ptr(prob), C.ptr(disp), C.ptr(lv), C.ptr(ws), C.ptr(dpp), C.ptr(mn), st)
+        rc = lib.pd_post_process(B, N, H, W, flags, C.ptr(logits), C.ptr(prob), C.ptr(disp), C.ptr(lv), C.ptr(ws), C.ptr(dpp), C.ptr(mn), st)
         assert rc == 0, lib.pd_last_error()
 
     times = {name: [] for name, _ in libs}
@@ -75,8 +138,13 @@ def main():
     ap.add_argument("--xz", type=int, default=0, help="the last K planes get a disparity that grows with the row (ground planes): a [B,N,H,1] map expanded along x")
     ap.add_argument("--ab", nargs="+", default=None, help="name=path of library builds: A/B of pd_post_process, interleaved in this process")
     ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--check", action="store_true", help="with --ab: compare the libraries' outputs on the raw bits instead (exit 1 on any difference)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.check:
+        if not a.ab:
+            ap.error("--check needs --ab")
+        return check(a)
     B, N, H, W = a.batch, a.planes, a.height, a.width
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(5)
@@ -123,4 +191,4 @@ def main():
         print("%-22s %.4f ms  %7.1f GB/s" % (name, t, bytes_[name] / (t * 1e-3) / 1e9))
 
 
-main()
+sys.exit(main())

@@ -322,7 +322,8 @@ def test_every_reachable_instantiation_is_in_the_table():
     """Every (N, W, form) with N <= 70 and W <= 1030 through the query: the kernel instantiations the fused call can reach
     at 160 KiB are exactly the table's, and so are the warps'.  The two that no shape reaches are the NPART = 11 and NPART = 18
     alias forms of pp_chain_split_kernel: alias needs N (W + 4) 4 + 3 nseg 1024 > 163840, and with N <= 54 (NPART <= 18) and
-    W <= 640 (the split chains' widths: nseg <= 5) the left side is at most 54 * 644 * 4 + 15360 = 154464."""
+    W <= 640 (the split chains' widths: nseg <= 5) the left side is at most 54 * 644 * 4 + 15360 = 154464.  The library does not
+    instantiate these two: a route that asked for one would answer PD_ERR_UNSUPPORTED."""
     assert 54 * (640 + 4) * 4 + 3 * 5 * 1024 == 154464 < LDS < 55 * (640 + 4) * 4 + 3 * 5 * 1024 + 5 * 644 * 4
     lib, r = C.load(), C.PpRoute()
     fused, sm, su = set(), set(), set()
