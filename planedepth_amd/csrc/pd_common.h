@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "planedepth_hip.h"
 
@@ -54,6 +55,14 @@ int grant_dynamic_lds(const void* kernel, size_t bytes, LdsGrant* grant, const c
   } while (0)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// A run-time flag as a kernel template's compile-time constant: f(std::true_type{}) or f(std::false_type{}).  Nest one call per
+// flag.  A generic lambda's call operator is instantiated once per constant, so a `static` inside it exists once per kernel
+// instantiation.
+template <typename F>
+static int dispatch_bool(bool v, F f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // ---- device side -----------------------------------------------------------------------------------------------
 // Workgroup i of a launch runs on XCD i % 8, and every XCD has its own L2.  The pixel-linear gather kernels read a
@@ -352,6 +361,22 @@ __device__ __forceinline__ float half_wave_sums_hi(float a, float b) {
 // atomic in a readlane loop: ~20 instructions per call in the backward's plane loop).
 __device__ __forceinline__ void lds_add(float* p, float v) {
   __builtin_amdgcn_ds_faddf((__attribute__((address_space(3))) float*)(p), v, 0, 0, false);
+}
+
+// Block accumulators of K per-lane values: red[k] += the wave's sum of gk[k].  Two components per DPP reduction (totals in lanes
+// 31 and 63), the odd one out on its own; one LDS atomic per component and wave.
+template <int K>
+__device__ __forceinline__ void reduce_to_lds(float* red, const float (&gk)[K]) {
+  const int ln = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int k = 0; k + 1 < K; k += 2) {
+    const float v = half_wave_sums_hi(gk[k], gk[k + 1]);
+    if ((ln & 31) == 31) lds_add(&red[k + (ln >> 5)], v);
+  }
+  if (K & 1) {
+    const float v = wave_sum_hi(gk[K - 1]);
+    if (ln == kWave - 1) lds_add(&red[K - 1], v);
+  }
 }
 
 // ---- bf16 storage (PD_LOGITS_BF16, PD_TAIL_BF16) ---------------------------------------------------------------------

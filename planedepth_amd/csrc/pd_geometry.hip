@@ -168,16 +168,7 @@ __global__ __launch_bounds__(kBlock) void homography_grid_bwd_kernel(int H, int 
       gk[6] += g2 * fx; gk[7] += g2 * fy; gk[8] += g2;
     }
   }
-  const int lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-  for (int k = 0; k < 8; k += 2) {
-    const float v = half_wave_sums_hi(gk[k], gk[k + 1]);   // totals in lanes 31 and 63
-    if ((lane & 31) == 31) lds_add(&red[k + (lane >> 5)], v);
-  }
-  {
-    const float v = wave_sum_hi(gk[8]);
-    if (lane == kWave - 1) lds_add(&red[8], v);
-  }
+  reduce_to_lds<9>(red, gk);
   __syncthreads();
   if (threadIdx.x < 9) partials[((long)m * gridDim.x + blockIdx.x) * 9 + threadIdx.x] = red[threadIdx.x];
 }

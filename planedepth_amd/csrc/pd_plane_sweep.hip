@@ -139,11 +139,10 @@ __global__ __launch_bounds__(kBlock) void sweep_bwd_kernel(SweepArgs a, BwdOut o
   const PixelCtx c = active ? make_pixel_ctx<MIX>(a, o, b, pix, HW) : zero_pixel_ctx();
   const float iy_disp = (MODE == PD_WARP_DISP) ? normalise_roundtrip((float)y, (float)(a.H - 1)) : 0.0f;
   const CoordNorm cn = make_coord_norm(a.W, a.H);
-  const float gscale_x = (float)(a.W - 1) / 2 * 2.0f / (float)(a.W - 1), gscale_y = (float)(a.H - 1) / 2 * 2.0f / (float)(a.H - 1);
+  const float gscale_x = grid_grad_scale(a.W), gscale_y = grid_grad_scale(a.H);
 
   const bool render = a.flags & PD_RENDER_PROB;
-  const float Rtot = MIX ? -c.A * c.mx : c.gdotr;  // sum_k p_k dL/dp_k, known in closed form
-  float T = 1.0f, prefix = 0.0f;
+  RenderBwd rb = make_render_bwd<MIX>(c);
   uint32_t bits = 0;
   for (int n = 0; n < a.N; ++n) {
     float gk[K];
@@ -173,46 +172,29 @@ __global__ __launch_bounds__(kBlock) void sweep_bwd_kernel(SweepArgs a, BwdOut o
         const float c2 = sample_vg_k(srcb + 2 * HW, tk, d2x, d2y);
         const float s = MIX ? sample_vg_k(a.sigma + pl, tk, dsx, dsy) : 0.0f;
         PlaneGrad pg;
-        if (render) {  // alpha compositing: d prob_k / d alpha_n for k >= n through the transmittance (trainer.py:584-591)
+        if (render) {  // alpha compositing
           const bool last = (n == a.N - 1);
           const float dist = last ? 0.0f : a.dists[((long)b * (a.N - 1) + n) * HW + pix];
-          const float alpha = render_alpha(l, dist, last);
-          const float pn = alpha * T;
-          pg = plane_grad_p<MIX>(c, pn, s, c0, c1, c2);
-          prefix += pg.g_l * pn;
-          const float keep = 1.0f - alpha + 1e-10f;
-          const float g_alpha = pg.g_l * T - (Rtot - prefix) / keep;
-          const float da = (1.0f - alpha);  // d alpha / d (relu(l) * dist)
-          pg.g_l = (!last && l > 0.0f) ? g_alpha * dist * da : 0.0f;
-          if (o.g_dists && !last && !ghost) o.g_dists[((long)b * (a.N - 1) + n) * HW + pix] = g_alpha * fmaxf(l, 0.0f) * da;
-          T *= keep;
+          float g_dist;
+          pg = render_bwd_step<MIX>(rb, c, l, s, dist, last, c0, c1, c2, g_dist);
+          if (o.g_dists && !last && !ghost) o.g_dists[((long)b * (a.N - 1) + n) * HW + pix] = g_dist;
         } else {
           pg = plane_grad<MIX>(c, l, s, c0, c1, c2);
         }
         const float g_l = pg.g_l, g_s = pg.g_s, gc0 = pg.gc0, gc1 = pg.gc1, gc2 = pg.gc2;
         st = t; sg_l = g_l; sg_s = g_s; live = true;
         if (want_plane) {
-          // d loss / d (ix, iy) in pixels, then back through grid_sample's un-normalisation ((size-1)/2) and the
-          // reference's normalisation (*2, /(size-1)) in autograd's order.
+          // d loss / d (ix, iy) in pixels, then grid_grad_scale
           const float gix = g_l * dlx + g_s * dsx + gc0 * d0x + gc1 * d1x + gc2 * d2x;
-          const float gpx = gix * gscale_x;  // (W-1)/2 * 2 / (W-1): gradient side, no bit-exactness at stake
-          if (MODE == PD_WARP_DISP) {
+          const float gpx = gix * gscale_x;
+          if constexpr (MODE == PD_WARP_DISP) {
             gk[0] = gpx * a.sign;
             gd_dense = gk[0];
           } else {
             const float giy = g_l * dly + g_s * dsy + gc0 * d0y + gc1 * d1y + gc2 * d2y;
-            const float gpy = giy * gscale_y;
             // gradient side: a refined reciprocal instead of three IEEE divisions (measured: no time difference — the
             // kernel is bound by the L2's atomic rate, not by VALU — but 30 instructions less)
-            float inv_z = fast_rcp(g.zc);
-            inv_z = fmaf(fmaf(-g.zc, inv_z, 1.0f), inv_z, inv_z);   // one Newton step: ~0.5 ulp
-            const float gp0 = gpx * inv_z, gp1 = gpy * inv_z;
-            const float gz = g.z_clamped ? 0.0f : -(gp0 * g.p0 + gp1 * g.p1) * inv_z;
-
-            const float fx = (float)x, fy = (float)y;
-            gk[0] = gp0 * fx; gk[1] = gp0 * fy; gk[2] = gp0;
-            gk[3] = gp1 * fx; gk[4] = gp1 * fy; gk[5] = gp1;
-            gk[6] = gz * fx;  gk[7] = gz * fy;  gk[8] = gz;
+            homography_grad9(gpx, giy * gscale_y, refined_rcp(g.zc), g.p0, g.p1, g.z_clamped, (float)x, (float)y, gk);
           }
         }
       }
@@ -236,18 +218,7 @@ __global__ __launch_bounds__(kBlock) void sweep_bwd_kernel(SweepArgs a, BwdOut o
       if (MIX && o.g_sigma) bilinear_scatter_wave(o.g_sigma + pl, st, a.W, sg_s, live, sp);
       if (o.g_logits) bilinear_scatter_wave(o.g_logits + pl, st, a.W, sg_l, live, sp);
     }
-    if (reduce_plane) {
-      const int ln = threadIdx.x & (kWave - 1);
-#pragma unroll
-      for (int k = 0; k + 1 < K; k += 2) {  // two components per DPP reduction: totals in lanes 31 and 63
-        const float v = half_wave_sums_hi(gk[k], gk[k + 1]);
-        if ((ln & 31) == 31) lds_add(&red[n * K + k + (ln >> 5)], v);  // LDS atomic, 4 waves
-      }
-      if (K & 1) {
-        const float v = wave_sum_hi(gk[K - 1]);
-        if (ln == kWave - 1) lds_add(&red[n * K + K - 1], v);
-      }
-    }
+    if (reduce_plane) reduce_to_lds<K>(red + n * K, gk);  // LDS atomics, 4 waves
   }
   if (reduce_plane) {
     __syncthreads();
@@ -560,16 +531,26 @@ extern "C" size_t pd_sweep_bwd_workspace_floats(const pd_sweep_desc* d) {
   return m > uni ? m : uni;
 }
 
-#define PD_DISPATCH(KERNEL, mode, mix, grid, block, shmem, stream, ...)                                   \
-  do {                                                                                                     \
-    if ((mode) == PD_WARP_DISP) {                                                                          \
-      if (mix) KERNEL<PD_WARP_DISP, true><<<grid, block, shmem, stream>>>(__VA_ARGS__);                    \
-      else     KERNEL<PD_WARP_DISP, false><<<grid, block, shmem, stream>>>(__VA_ARGS__);                   \
-    } else {                                                                                               \
-      if (mix) KERNEL<PD_WARP_HOMOGRAPHY, true><<<grid, block, shmem, stream>>>(__VA_ARGS__);              \
-      else     KERNEL<PD_WARP_HOMOGRAPHY, false><<<grid, block, shmem, stream>>>(__VA_ARGS__);             \
-    }                                                                                                      \
-  } while (0)
+// The general kernels' <MODE, MIX>: f(std::integral_constant<int, mode>{}, std::bool_constant<mix>{})
+template <typename F>
+static int dispatch_mode_mix(const pd_sweep_desc* d, F f) {
+  return dispatch_bool(d->mode == PD_WARP_DISP, [&](auto disp) {
+    return dispatch_bool((d->flags & PD_MIXTURE) != 0, [&](auto mix) {
+      return f(std::integral_constant<int, decltype(disp)::value ? PD_WARP_DISP : PD_WARP_HOMOGRAPHY>{}, mix);
+    });
+  });
+}
+
+// Checks that several entry points share
+static int refuse_bf16(const pd_sweep_desc* d, const char* entry) {
+  if (!d || !(d->flags & PD_LOGITS_BF16)) return PD_OK;
+  set_error("PD_LOGITS_BF16: not served by %s", entry);
+  return PD_ERR_UNSUPPORTED;
+}
+static int require_render(const pd_sweep_desc* d, const float* dists) {
+  PD_REQUIRE(!(d->flags & PD_RENDER_PROB) || (dists && d->N >= 2), "PD_RENDER_PROB needs dists [B,N-1,H,W] and N >= 2");
+  return PD_OK;
+}
 
 extern "C" int pd_plane_sweep_fwd(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits,
                                   const float* sigma, const float* plane, const float* plane_aux, const float* inv_K3,
@@ -578,7 +559,7 @@ extern "C" int pd_plane_sweep_fwd(const pd_sweep_desc* d, const float* src, cons
   int rc = validate(d, src, logits, sigma, plane, plane_aux, inv_K3, padding_mask);
   if (rc) return rc;
   PD_REQUIRE(tgt && rgb_rec && ph_map && stash, "tgt/rgb_rec/ph_map/stash must not be NULL");
-  PD_REQUIRE(!(d->flags & PD_RENDER_PROB) || (dists && d->N >= 2), "PD_RENDER_PROB needs dists [B,N-1,H,W] and N >= 2");
+  if ((rc = require_render(d, dists))) return rc;
   // the stash always reserves the mask words in disp mode (pd_sweep_stash_floats); they are written when a mask exists
   SweepArgs a = make_args(d, src, tgt, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists);
   if (ph_mean) {  // the kernels add into it: start from zero (an async memset on the same stream, unless the caller did it)
@@ -599,10 +580,11 @@ extern "C" int pd_plane_sweep_fwd(const pd_sweep_desc* d, const float* src, cons
     case FwdFamily::Unsupported: set_error("%s", r.fwd_why); return r.fwd_err;
     case FwdFamily::General: break;
   }
-  dim3 grid(ceil_div(d->H * d->W, kBlock), d->B);
-  PD_DISPATCH(sweep_fwd_kernel, d->mode, (d->flags & PD_MIXTURE) != 0, grid, dim3(kBlock), 0, (hipStream_t)stream, a,
-              rgb_rec, ph_map, stash);
-  return check_launch("sweep_fwd_kernel");
+  const dim3 grid(ceil_div(d->H * d->W, kBlock), d->B);
+  return dispatch_mode_mix(d, [&](auto mode, auto mix) {
+    sweep_fwd_kernel<decltype(mode)::value, decltype(mix)::value><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, rgb_rec, ph_map, stash);
+    return check_launch("sweep_fwd_kernel");
+  });
 }
 
 struct TailIn {
@@ -610,6 +592,16 @@ struct TailIn {
   const char* entry;   // the entry point's name, for messages
   bool rows;           // pd_plane_sweep_bwd_tail_rows
 };
+
+static BwdOut make_bwd_out(const pd_sweep_desc* d, float* g_logits, float* g_sigma, float* g_plane, float* g_dists, float* workspace,
+                           const float* rgb_rec, const float* stash, const float* g_rgb_rec, const float* g_ph_map,
+                           const float* g_ph_mean) {
+  BwdOut o{};
+  o.g_logits = g_logits; o.g_sigma = (d->flags & PD_MIXTURE) ? g_sigma : nullptr; o.g_plane = g_plane; o.partials = workspace;
+  o.g_dists = (d->flags & PD_RENDER_PROB) ? g_dists : nullptr;
+  o.rgb_rec = rgb_rec; o.stash = stash; o.g_rgb_rec = g_rgb_rec; o.g_ph_map = g_ph_map; o.g_ph_mean = g_ph_mean;
+  return o;
+}
 
 static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits,
                           const float* sigma, const float* plane, const float* plane_aux, const float* inv_K3,
@@ -620,7 +612,7 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   int rc = validate(d, src, logits, sigma, plane, plane_aux, inv_K3, padding_mask);
   if (rc) return rc;
   PD_REQUIRE(tgt && rgb_rec && stash, "tgt/rgb_rec/stash must not be NULL");
-  PD_REQUIRE(!(d->flags & PD_RENDER_PROB) || (dists && d->N >= 2), "PD_RENDER_PROB needs dists [B,N-1,H,W] and N >= 2");
+  if ((rc = require_render(d, dists))) return rc;
   const bool dense = (d->flags & (PD_DISP_DENSE | PD_DISP_ROWS)) != 0;
   PD_REQUIRE(!g_plane || dense || workspace, "g_plane needs workspace (pd_sweep_bwd_workspace_floats)");
   PD_REQUIRE(d->impl >= PD_IMPL_AUTO && d->impl <= PD_IMPL_EXACT_ROWS, "unknown impl %d", d->impl);
@@ -635,19 +627,10 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   f.tail_rows = tail != nullptr && tail->rows;
   const SweepRoute r = sweep_route(d, f);
   PD_REQUIRE(!accumulate || r.accumulates, "PD_BWD_ACCUMULATE is not served for this descriptor (pd_sweep_bwd_accumulates)");
-  if (d->flags & PD_LOGITS_BF16) {
-    if (tail) {
-      set_error("PD_LOGITS_BF16: not served by %s", tail->entry);
-      return PD_ERR_UNSUPPORTED;
-    }
+  if (d->flags & PD_LOGITS_BF16)   // (the tail entry points have refused the flag: sweep_bwd_tail)
     PD_REQUIRE(!((reinterpret_cast<uintptr_t>(g_logits) | reinterpret_cast<uintptr_t>(g_sigma)) & 3),
                "PD_LOGITS_BF16: g_logits / g_sigma must be 4-byte aligned");
-  }
-  BwdOut o;
-  o.g_logits = g_logits; o.g_sigma = mix ? g_sigma : nullptr; o.g_plane = g_plane; o.partials = workspace;
-  o.side = nullptr; o.scratch = nullptr;
-  o.g_dists = (d->flags & PD_RENDER_PROB) ? g_dists : nullptr;
-  o.rgb_rec = rgb_rec; o.stash = stash; o.g_rgb_rec = g_rgb_rec; o.g_ph_map = g_ph_map; o.g_ph_mean = g_ph_mean;
+  BwdOut o = make_bwd_out(d, g_logits, g_sigma, g_plane, g_dists, workspace, rgb_rec, stash, g_rgb_rec, g_ph_map, g_ph_mean);
   if (r.rows) PD_REQUIRE(workspace, "the row-shift backward needs workspace (pd_sweep_bwd_workspace_floats)");
   switch (r.bwd) {
     case BwdFamily::Unsupported: set_error("%s", r.bwd_why); return r.bwd_err;
@@ -673,9 +656,10 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
     if (rc) return rc;
     const dim3 grid1(gp.nblk, d->B);
     const size_t shmem1 = (size_t)d->N * 9 * sizeof(float);
-    if (mix) sweep_bwd_kernel<PD_WARP_HOMOGRAPHY, true, true><<<grid1, kBlock, shmem1, stream>>>(ak, o);
-    else     sweep_bwd_kernel<PD_WARP_HOMOGRAPHY, false, true><<<grid1, kBlock, shmem1, stream>>>(ak, o);
-    rc = check_launch("sweep_bwd_kernel (scratch)");
+    rc = dispatch_bool(mix, [&](auto mx) {
+      sweep_bwd_kernel<PD_WARP_HOMOGRAPHY, decltype(mx)::value, true><<<grid1, kBlock, shmem1, stream>>>(ak, o);
+      return check_launch("sweep_bwd_kernel (scratch)");
+    });
     if (rc) return rc;
     rc = gather_bwd_finish(d, ak, o, gp, stream);
     if (rc || !g_plane) return rc;
@@ -689,8 +673,10 @@ static int sweep_bwd_impl(const pd_sweep_desc* d, const float* src, const float*
   if (g_logits && !accumulate) (void)hipMemsetAsync(g_logits, 0, plane_bytes, stream);
   if (g_sigma && !accumulate) (void)hipMemsetAsync(g_sigma, 0, plane_bytes, stream);
   const size_t shmem = (size_t)d->N * K * sizeof(float);
-  PD_DISPATCH(sweep_bwd_kernel, d->mode, mix, grid, dim3(kBlock), shmem, stream, ak, o);
-  rc = check_launch("sweep_bwd_kernel");
+  rc = dispatch_mode_mix(d, [&](auto mode, auto mx) {
+    sweep_bwd_kernel<decltype(mode)::value, decltype(mx)::value><<<grid, kBlock, shmem, stream>>>(ak, o);
+    return check_launch("sweep_bwd_kernel");
+  });
   if (rc) return rc;
   if (g_plane && !dense) rc = reduce_partials(workspace, g_plane, grid.x, d->N * K, d->B, stream);
   return rc;
@@ -706,20 +692,27 @@ extern "C" int pd_plane_sweep_bwd(const pd_sweep_desc* d, const float* src, cons
                         g_ph_map, g_ph_mean, g_logits, g_sigma, g_plane, g_dists, workspace, stream, nullptr);
 }
 
+// The two tail entry points: their checks, then the common path (no homography, no dists; `mask_rows` is NULL for the first)
+static int sweep_bwd_tail(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits, const float* sigma,
+                          const float* plane, const float* mask_rows, const float* rgb_rec, const float* stash,
+                          const float* g_rgb_rec, const float* g_ph_map, const float* g_ph_mean, const TailIn& t,
+                          float* g_raw_logits, float* g_raw_sigma, float* g_plane, float* workspace, pd_stream_t stream) {
+  if (int rc = refuse_bf16(d, t.entry)) return rc;
+  PD_REQUIRE(t.raw_sigma && t.stash && t.disp, "raw_sigma / tail_stash / disp must not be NULL");
+  PD_REQUIRE(!d || (d->flags & PD_MASK_ROWS) || !mask_rows, "mask_rows [B,N,H] goes with PD_MASK_ROWS (no other mask form is served)");
+  return sweep_bwd_impl(d, src, tgt, logits, sigma, plane, nullptr, nullptr, mask_rows, nullptr, rgb_rec, stash, g_rgb_rec,
+                        g_ph_map, g_ph_mean, g_raw_logits, g_raw_sigma, g_plane, nullptr, workspace, stream, &t);
+}
+
 extern "C" int pd_plane_sweep_bwd_tail(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits,
                                        const float* sigma, const float* plane, const float* rgb_rec, const float* stash,
                                        const float* g_rgb_rec, const float* g_ph_map, const float* g_ph_mean,
                                        const float* raw_sigma, const float* tail_stash, const float* disp,
                                        const float* g_disp, const float* g_depth, float* g_raw_logits,
                                        float* g_raw_sigma, float* g_plane, float* workspace, pd_stream_t stream) {
-  if (d && (d->flags & PD_LOGITS_BF16)) {
-    set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_bwd_tail");
-    return PD_ERR_UNSUPPORTED;
-  }
-  PD_REQUIRE(raw_sigma && tail_stash && disp, "raw_sigma / tail_stash / disp must not be NULL");
   const TailIn t = {raw_sigma, tail_stash, disp, g_disp, g_depth, "pd_plane_sweep_bwd_tail", false};
-  return sweep_bwd_impl(d, src, tgt, logits, sigma, plane, nullptr, nullptr, nullptr, nullptr, rgb_rec, stash, g_rgb_rec,
-                        g_ph_map, g_ph_mean, g_raw_logits, g_raw_sigma, g_plane, nullptr, workspace, stream, &t);
+  return sweep_bwd_tail(d, src, tgt, logits, sigma, plane, nullptr, rgb_rec, stash, g_rgb_rec, g_ph_map, g_ph_mean, t, g_raw_logits,
+                        g_raw_sigma, g_plane, workspace, stream);
 }
 
 extern "C" int pd_plane_sweep_bwd_tail_rows(const pd_sweep_desc* d, const float* src, const float* tgt, const float* logits,
@@ -729,25 +722,16 @@ extern "C" int pd_plane_sweep_bwd_tail_rows(const pd_sweep_desc* d, const float*
                                             const float* tail_stash, const float* disp, const float* g_disp,
                                             const float* g_depth, float* g_raw_logits, float* g_raw_sigma, float* g_plane,
                                             float* workspace, pd_stream_t stream) {
-  if (d && (d->flags & PD_LOGITS_BF16)) {
-    set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_bwd_tail_rows");
-    return PD_ERR_UNSUPPORTED;
-  }
-  PD_REQUIRE(raw_sigma && tail_stash && disp, "raw_sigma / tail_stash / disp must not be NULL");
-  PD_REQUIRE(!d || (d->flags & PD_MASK_ROWS) || !mask_rows, "mask_rows [B,N,H] goes with PD_MASK_ROWS (no other mask form is served)");
   const TailIn t = {raw_sigma, tail_stash, disp, g_disp, g_depth, "pd_plane_sweep_bwd_tail_rows", true};
-  return sweep_bwd_impl(d, src, tgt, logits, sigma, plane, nullptr, nullptr, mask_rows, nullptr, rgb_rec, stash, g_rgb_rec,
-                        g_ph_map, g_ph_mean, g_raw_logits, g_raw_sigma, g_plane, nullptr, workspace, stream, &t);
+  return sweep_bwd_tail(d, src, tgt, logits, sigma, plane, mask_rows, rgb_rec, stash, g_rgb_rec, g_ph_map, g_ph_mean, t, g_raw_logits,
+                        g_raw_sigma, g_plane, workspace, stream);
 }
 
 extern "C" int pd_uniform_gather_pair(const pd_sweep_desc* d, const float* plane_a, const float* inv_K3_a, float* workspace_a,
                                       const float* plane_b, const float* inv_K3_b, float* workspace_b, float* g_logits,
                                       float* g_sigma, pd_stream_t stream) {
   PD_REQUIRE(d != nullptr, "desc is NULL");
-  if (d->flags & PD_LOGITS_BF16) {
-    set_error("PD_LOGITS_BF16: not served by pd_uniform_gather_pair");
-    return PD_ERR_UNSUPPORTED;
-  }
+  if (int rc = refuse_bf16(d, "pd_uniform_gather_pair")) return rc;
   PD_REQUIRE(d->mode == PD_WARP_HOMOGRAPHY && (d->flags & PD_HOMO_UNIFORM) && (d->flags & PD_BWD_DEFER_GATHER),
              "pd_uniform_gather_pair takes the descriptor of two PD_HOMO_UNIFORM | PD_BWD_DEFER_GATHER backward calls");
   PD_REQUIRE(d->B > 0 && d->B <= 65535 && d->N > 0 && d->H > 1 && d->W > 1, "bad shape");
@@ -760,16 +744,13 @@ extern "C" int pd_uniform_gather_pair(const pd_sweep_desc* d, const float* plane
 static int validate_pair(const pd_sweep_desc* d, const float* src, const float* logits, const float* sigma,
                          const pd_sweep_view* va, const pd_sweep_view* vb) {
   PD_REQUIRE(d && va && vb, "desc / view is NULL");
-  if (d->flags & PD_LOGITS_BF16) {
-    set_error("PD_LOGITS_BF16: not served by the pair entry points");
-    return PD_ERR_UNSUPPORTED;
-  }
+  if (int rc = refuse_bf16(d, "the pair entry points")) return rc;
   PD_REQUIRE(query_route(d).fwd == FwdFamily::Uniform, "the pair entry points serve PD_HOMO_UNIFORM views");
   for (const pd_sweep_view* v : {va, vb}) {
-    const int rc = validate(d, src, logits, sigma, v->plane, v->plane_aux, v->inv_K3, v->padding_mask);
+    int rc = validate(d, src, logits, sigma, v->plane, v->plane_aux, v->inv_K3, v->padding_mask);
     if (rc) return rc;
     PD_REQUIRE(v->tgt && v->rgb_rec && v->stash, "view: tgt / rgb_rec / stash must not be NULL");
-    PD_REQUIRE(!(d->flags & PD_RENDER_PROB) || (v->dists && d->N >= 2), "PD_RENDER_PROB needs dists [B,N-1,H,W] and N >= 2");
+    if ((rc = require_render(d, v->dists))) return rc;
   }
   return PD_OK;
 }
@@ -800,14 +781,11 @@ extern "C" int pd_uniform_bwd_pair(const pd_sweep_desc* d, const float* src, con
   PD_REQUIRE(!g_logits || !mix || g_sigma, "PD_MIXTURE needs g_sigma next to g_logits");
   SweepArgs a = make_args(d, src, va->tgt, logits, sigma, va->plane, va->plane_aux, va->inv_K3, va->padding_mask, va->dists);
   SweepArgs b = make_args(d, src, vb->tgt, logits, sigma, vb->plane, vb->plane_aux, vb->inv_K3, vb->padding_mask, vb->dists);
-  BwdOut oa{}, ob{};
-  for (int i = 0; i < 2; ++i) {
-    const pd_sweep_view* v = i ? vb : va;
-    BwdOut& o = i ? ob : oa;
-    o.g_logits = nullptr; o.g_sigma = nullptr; o.g_plane = v->g_plane; o.partials = v->workspace; o.side = nullptr; o.scratch = nullptr;
-    o.g_dists = (d->flags & PD_RENDER_PROB) ? v->g_dists : nullptr;
-    o.rgb_rec = v->rgb_rec; o.stash = v->stash; o.g_rgb_rec = v->g_rgb_rec; o.g_ph_map = v->g_ph_map; o.g_ph_mean = v->g_ph_mean;
-  }
+  // (the views' g_logits / g_sigma are the pair gather's)
+  auto out = [&](const pd_sweep_view* v) {
+    return make_bwd_out(d, nullptr, nullptr, v->g_plane, v->g_dists, v->workspace, v->rgb_rec, v->stash, v->g_rgb_rec, v->g_ph_map, v->g_ph_mean);
+  };
+  const BwdOut oa = out(va), ob = out(vb);
   return uniform_bwd_pair(d, a, oa, va->workspace, b, ob, vb->workspace, g_logits, mix ? g_sigma : nullptr, (hipStream_t)stream);
 }
 
@@ -828,16 +806,14 @@ extern "C" int pd_plane_sweep_layers(const pd_sweep_desc* d, const float* src, c
                                      float* sigma_rec, float* pi_rec, pd_stream_t stream) {
   int rc = validate(d, src, logits, sigma, plane, plane_aux, inv_K3, padding_mask);
   if (rc) return rc;
-  PD_REQUIRE(!(d->flags & PD_RENDER_PROB) || (dists && d->N >= 2), "PD_RENDER_PROB needs dists [B,N-1,H,W] and N >= 2");
+  if ((rc = require_render(d, dists))) return rc;
   PD_REQUIRE(!(d->flags & PD_HOMO_UNIFORM), "pd_plane_sweep_layers takes one homography per plane (expand the matrix)");
-  if (d->flags & PD_LOGITS_BF16) {
-    set_error("PD_LOGITS_BF16: not served by pd_plane_sweep_layers");
-    return PD_ERR_UNSUPPORTED;
-  }
+  if ((rc = refuse_bf16(d, "pd_plane_sweep_layers"))) return rc;
   SweepArgs a = make_args(d, src, nullptr, logits, sigma, plane, plane_aux, inv_K3, padding_mask, dists);
   LayersOut o{rgb_rec_layered, logit_rec, probability_rec, sigma_rec, pi_rec};
-  dim3 grid(ceil_div(d->H * d->W, kBlock), d->B);
-  PD_DISPATCH(sweep_layers_kernel, d->mode, (d->flags & PD_MIXTURE) != 0, grid, dim3(kBlock), 0, (hipStream_t)stream, a,
-              o);
-  return check_launch("sweep_layers_kernel");
+  const dim3 grid(ceil_div(d->H * d->W, kBlock), d->B);
+  return dispatch_mode_mix(d, [&](auto mode, auto mix) {
+    sweep_layers_kernel<decltype(mode)::value, decltype(mix)::value><<<grid, kBlock, 0, (hipStream_t)stream>>>(a, o);
+    return check_launch("sweep_layers_kernel");
+  });
 }

@@ -73,16 +73,8 @@ __global__ void gather_prep_kernel(const float* __restrict__ H_t2s, GatherPrep* 
                                    int BN, int W, int H) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= BN) return;
-  const float* h = H_t2s + (long)i * 9;
-  const double a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], k = h[7], l = h[8];
-  const double A = e * l - f * k, Bc = -(d * l - f * g), C = d * k - e * g;
-  const double det = a * A + b * Bc + c * C, inv = 1.0 / det;
   GatherPrep p;
-  p.Hs[0] = (float)(A * inv);  p.Hs[1] = (float)(-(b * l - c * k) * inv); p.Hs[2] = (float)((b * f - c * e) * inv);
-  p.Hs[3] = (float)(Bc * inv); p.Hs[4] = (float)((a * l - c * g) * inv);  p.Hs[5] = (float)(-(a * f - c * d) * inv);
-  p.Hs[6] = (float)(C * inv);  p.Hs[7] = (float)(-(a * k - b * g) * inv); p.Hs[8] = (float)((a * e - b * d) * inv);
-  bool ok = (det == det) && fabs(det) > 1e-30 && fabs(inv) < 1e30;
-  for (int j = 0; j < 9; ++j) ok = ok && (fabsf(p.Hs[j]) < 1e30f) && (p.Hs[j] == p.Hs[j]);
+  bool ok = adjugate_inverse(H_t2s + (long)i * 9, p.Hs);
   float wspread = 1.0f;   // max |w| / min |w| over the grown image
   if (ok) {   // the denominator is affine in the source position: its extremes over the grown image are at the corners
     float wmin = 3.0e38f, wmax = -3.0e38f;
@@ -471,22 +463,19 @@ int gather_bwd_prepare(const pd_sweep_desc* d, const SweepArgs& a, const GatherP
 }
 
 int gather_bwd_finish(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, const GatherPlan& gp, hipStream_t stream) {
-  const bool mix = (d->flags & PD_MIXTURE) != 0;
   const int accumulate = (d->flags & PD_BWD_ACCUMULATE) ? 1 : 0;
   const int tiles_x = ceil_div(d->W, kGatherTileW);
   const dim3 grid2(tiles_x * ceil_div(d->H, kGatherTileH), d->B), grid1(ceil_div(d->H * d->W, kBlock), d->B);
   const GatherPrep* prep = reinterpret_cast<const GatherPrep*>(gp.prep);
   const bool staged = d->impl != PD_IMPL_UNIFORM_DIRECT;   // (the direct-gather form: cross-check, and what large boxes fall back to)
-  if (mix) {
-    if (staged) gather_bwd_pass2_staged_kernel<true><<<grid2, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, o.g_sigma, gp.flags, tiles_x, accumulate);
-    else gather_bwd_pass2_kernel<true><<<grid2, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, o.g_sigma, gp.flags, tiles_x, accumulate);
-    gather_fixup_kernel<true><<<grid1, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, o.g_sigma, gp.flags);
-  } else {
-    if (staged) gather_bwd_pass2_staged_kernel<false><<<grid2, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, nullptr, gp.flags, tiles_x, accumulate);
-    else gather_bwd_pass2_kernel<false><<<grid2, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, nullptr, gp.flags, tiles_x, accumulate);
-    gather_fixup_kernel<false><<<grid1, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, nullptr, gp.flags);
-  }
-  return check_launch("gather_bwd_pass2_kernel / gather_fixup_kernel");
+  return dispatch_bool((d->flags & PD_MIXTURE) != 0, [&](auto mix) {
+    constexpr bool MIX = decltype(mix)::value;
+    float* g_sigma = MIX ? o.g_sigma : nullptr;
+    if (staged) gather_bwd_pass2_staged_kernel<MIX><<<grid2, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, g_sigma, gp.flags, tiles_x, accumulate);
+    else gather_bwd_pass2_kernel<MIX><<<grid2, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, g_sigma, gp.flags, tiles_x, accumulate);
+    gather_fixup_kernel<MIX><<<grid1, kBlock, 0, stream>>>(a, gp.scratch, prep, o.g_logits, g_sigma, gp.flags);
+    return check_launch("gather_bwd_pass2_kernel / gather_fixup_kernel");
+  });
 }
 
 }  // namespace pd

@@ -143,13 +143,6 @@ struct SegCtx {
   bool active;
 };
 
-// PD_RENDER_PROB: what the front-to-back compositing carries from plane to plane of one pixel
-struct RenderBwd {
-  float T = 1.0f;        // transmittance in front of the current plane
-  float prefix = 0.0f;   // sum_{k <= n} p_k dL/dp_k
-  float Rtot = 0.0f;     // sum over all planes of the same, known in closed form from the pixel's stash
-};
-
 template <bool MIX, bool HASMASK, int NROWS, int U, bool RENDER = false>
 __device__ __forceinline__ void bwd_compute(const PlaneGroup<NROWS, U>& g, const SweepArgs& a, const BwdOut& o,
                                             const RowSel& row, const char* __restrict__ lrgb,
@@ -184,20 +177,12 @@ __device__ __forceinline__ void bwd_compute(const PlaneGroup<NROWS, U>& g, const
     const float l = tap_value<NROWS>(tl, w);
     const float s = MIX ? tap_value<NROWS>(ts, w) : 0.0f;
     PlaneGrad pg;
-    if (RENDER) {  // d prob_k / d alpha_n for k >= n through the transmittance (trainer.py:584-591)
+    if (RENDER) {
       const bool last = (n == N - 1);
       const float lm = mk ? l : 0.0f;   // a masked plane samples as all-zero features: alpha = 0, the state passes through
-      const float dist = g.dist[u];
-      const float alpha = render_alpha(lm, dist, last);
-      const float pn = alpha * rb->T;
-      pg = plane_grad_p<MIX>(c, pn, s, c0, c1, c2);
-      rb->prefix += pg.g_l * pn;
-      const float keep = 1.0f - alpha + 1e-10f;
-      const float g_alpha = pg.g_l * rb->T - (rb->Rtot - rb->prefix) / keep;
-      const float da = 1.0f - alpha;   // d alpha / d (relu(l) * dist)
-      pg.g_l = (!last && lm > 0.0f) ? g_alpha * dist * da : 0.0f;
-      if (o.g_dists && !last && sc.active) o.g_dists[((long)b * (N - 1) + n) * HW + sc.pix] = g_alpha * fmaxf(lm, 0.0f) * da;
-      rb->T *= keep;
+      float g_dist;
+      pg = render_bwd_step<MIX>(*rb, c, lm, s, g.dist[u], last, c0, c1, c2, g_dist);
+      if (o.g_dists && !last && sc.active) o.g_dists[((long)b * (N - 1) + n) * HW + sc.pix] = g_dist;
     } else {
       pg = plane_grad<MIX>(c, l, s, c0, c1, c2);
     }
@@ -314,8 +299,7 @@ __device__ __forceinline__ void rowshift_bwd_body(const SweepArgs& a, const BwdO
     sc.last = min(kWave - 1, W - 1 - sc.T0);
     sc.pix = y * W + (sc.active ? sc.xt : 0);
     const PixelCtx c = sc.active ? make_pixel_ctx<MIX>(a, o, b, sc.pix, HW) : zero_pixel_ctx();
-    RenderBwd rb;
-    rb.Rtot = MIX ? -c.A * c.mx : c.gdotr;
+    RenderBwd rb = make_render_bwd<MIX>(c);
     uint32_t bits = 0;
     // same software pipeline as the forward (the mask comes from the stash bits, not from memory)
     PlaneGroup<NROWS, U> g0, g1;

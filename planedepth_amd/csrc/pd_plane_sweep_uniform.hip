@@ -227,25 +227,24 @@ __global__ __launch_bounds__(kBlock) void uniform_fwd_kernel(SweepArgs a, float*
 constexpr int kUniG = 4;
 
 template <bool MIX, bool RENDER = false>
-__global__ __launch_bounds__(kBlock) void uniform_bwd_pass1_kernel(SweepArgs a, BwdOut o, int b0, float* __restrict__ tmp,
+__global__ __launch_bounds__(kBlock) void uniform_bwd_pass1_kernel(SweepArgs a, BwdOut o, float* __restrict__ tmp,
                                                                    float* __restrict__ partials, const float* __restrict__ tw) {
   __shared__ float red[kUniG * 9];
   const int HW = a.H * a.W, N = a.N;
   const int ntiles = gridDim.x;
   const int tile = xcd_banded(blockIdx.x, gridDim.x);
-  const int by = blockIdx.y;
   const int pix = tile * kBlock + threadIdx.x;
-  const int b = b0 + by;
+  const int b = blockIdx.y;
   // (g_l, g_s) of a pixel-plane side by side: one 8-byte store here, one 8-byte load per list entry in pass 2 (pass 2
   // is paced by its number of memory instructions: 0.386 -> see DESIGN.md with the two tensors apart)
-  float* __restrict__ tmp_b = tmp + (long)by * 2 * N * HW;
+  float* __restrict__ tmp_b = tmp + (long)b * 2 * N * HW;
   if (threadIdx.x < kUniG * 9) red[threadIdx.x] = 0.0f;
   __syncthreads();
   const bool want_plane = (o.g_plane != nullptr);
   float gixw[kUniG], giyw[kUniG];
 #pragma unroll
   for (int j = 0; j < kUniG; ++j) gixw[j] = giyw[j] = 0.0f;
-  float gp_scale0 = 0.0f, p0 = 0.0f, p1 = 0.0f, fxx = 0.0f, fyy = 0.0f;
+  float inv_z = 0.0f, p0 = 0.0f, p1 = 0.0f, fxx = 0.0f, fyy = 0.0f;   // (lanes past the image: finite, their gixw / giyw are zero)
   bool zcl = false;
   if (pix < HW) {
     const int y = pix / a.W, x = pix - y * a.W;
@@ -260,8 +259,7 @@ __global__ __launch_bounds__(kBlock) void uniform_bwd_pass1_kernel(SweepArgs a, 
     const float* Rn = a.plane_aux + (long)b * N * 3;
     const float* twb = tw ? tw + (long)b * N * 3 : nullptr;
     constexpr bool render = RENDER;
-    const float Rtot = MIX ? -c.A * c.mx : c.gdotr;   // sum_k p_k dL/dp_k in closed form
-    float T = 1.0f, prefix = 0.0f;
+    RenderBwd rb = make_render_bwd<MIX>(c);
     const unsigned image_bytes = (unsigned)(N * HW) * 4u, plane_bytes = (unsigned)HW * 4u;
     const URsrc rl = image_rsrc(a.logits + (long)b * N * HW, image_bytes);
     const URsrc rsg = image_rsrc(MIX ? a.sigma + (long)b * N * HW : a.logits, MIX ? image_bytes : 0u);
@@ -286,19 +284,12 @@ __global__ __launch_bounds__(kBlock) void uniform_bwd_pass1_kernel(SweepArgs a, 
           if (MIX) s = usample_k(rsg, t, po);
         }
         PlaneGrad pg;
-        if (render) {   // d prob_k / d alpha_n for k >= n through the transmittance (trainer.py:584-591)
+        if (render) {
           const bool last = (n == N - 1);
           const float dist = last ? 0.0f : a.dists[((long)b * (N - 1) + n) * HW + pix];
-          const float alpha = render_alpha(l, dist, last);
-          const float pn = alpha * T;
-          pg = plane_grad_p<MIX>(c, pn, s, s0, s1, s2);
-          prefix += pg.g_l * pn;
-          const float keep = 1.0f - alpha + 1e-10f;
-          const float g_alpha = pg.g_l * T - (Rtot - prefix) / keep;
-          const float da = 1.0f - alpha;
-          pg.g_l = (!last && l > 0.0f) ? g_alpha * dist * da : 0.0f;
-          if (o.g_dists && !last) o.g_dists[((long)b * (N - 1) + n) * HW + pix] = g_alpha * fmaxf(l, 0.0f) * da;
-          T *= keep;
+          float g_dist;
+          pg = render_bwd_step<MIX>(rb, c, l, s, dist, last, s0, s1, s2, g_dist);
+          if (o.g_dists && !last) o.g_dists[((long)b * (N - 1) + n) * HW + pix] = g_dist;
         } else {
           pg = plane_grad<MIX>(c, l, s, s0, s1, s2);
         }
@@ -321,25 +312,15 @@ __global__ __launch_bounds__(kBlock) void uniform_bwd_pass1_kernel(SweepArgs a, 
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, g_l), rtmp, (int)tmp_lane, (int)pt, 0);
       }
     }
-    float inv_z = fast_rcp(u.g.zc);
-    inv_z = fmaf(fmaf(-u.g.zc, inv_z, 1.0f), inv_z, inv_z);
-    gp_scale0 = inv_z; p0 = u.g.p0; p1 = u.g.p1; zcl = u.g.z_clamped; fxx = (float)x; fyy = (float)y;
+    inv_z = refined_rcp(u.g.zc); p0 = u.g.p0; p1 = u.g.p1; zcl = u.g.z_clamped; fxx = (float)x; fyy = (float)y;
   }
   if (want_plane) {   // every lane takes part in the reductions (lanes past the image carry zeros)
-    const float gscale_x = (float)(a.W - 1) / 2 * 2.0f / (float)(a.W - 1), gscale_y = (float)(a.H - 1) / 2 * 2.0f / (float)(a.H - 1);
-    const int ln = threadIdx.x & (kWave - 1);
+    const float gscale_x = grid_grad_scale(a.W), gscale_y = grid_grad_scale(a.H);
 #pragma unroll
     for (int j = 0; j < kUniG; ++j) {
-      const float gp0 = gixw[j] * gscale_x * gp_scale0, gp1 = giyw[j] * gscale_y * gp_scale0;
-      const float gz = zcl ? 0.0f : -(gp0 * p0 + gp1 * p1) * gp_scale0;
-      const float gk[9] = {gp0 * fxx, gp0 * fyy, gp0, gp1 * fxx, gp1 * fyy, gp1, gz * fxx, gz * fyy, gz};
-#pragma unroll
-      for (int k = 0; k + 1 < 9; k += 2) {
-        const float v = half_wave_sums_hi(gk[k], gk[k + 1]);
-        if ((ln & 31) == 31) lds_add(&red[j * 9 + k + (ln >> 5)], v);
-      }
-      const float v8 = wave_sum_hi(gk[8]);
-      if (ln == kWave - 1) lds_add(&red[j * 9 + 8], v8);
+      float gk[9];
+      homography_grad9(gixw[j] * gscale_x, giyw[j] * gscale_y, inv_z, p0, p1, zcl, fxx, fyy, gk);
+      reduce_to_lds<9>(red + j * 9, gk);
     }
     __syncthreads();
     if (threadIdx.x < kUniG * 9)
@@ -358,17 +339,8 @@ struct UniPrep {      // per image: forward homography (source -> target) from a
 __global__ void uniform_prep_kernel(const float* __restrict__ H_t2s, UniPrep* __restrict__ prep, int B) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  const float* h = H_t2s + (long)i * kUniH;
-  const double a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], k = h[7], l = h[8];
-  const double A = e * l - f * k, Bc = -(d * l - f * g), C = d * k - e * g;
-  const double det = a * A + b * Bc + c * C, inv = 1.0 / det;
   UniPrep p;
-  p.Hs[0] = (float)(A * inv);  p.Hs[1] = (float)(-(b * l - c * k) * inv); p.Hs[2] = (float)((b * f - c * e) * inv);
-  p.Hs[3] = (float)(Bc * inv); p.Hs[4] = (float)((a * l - c * g) * inv);  p.Hs[5] = (float)(-(a * f - c * d) * inv);
-  p.Hs[6] = (float)(C * inv);  p.Hs[7] = (float)(-(a * k - b * g) * inv); p.Hs[8] = (float)((a * e - b * d) * inv);
-  bool ok = (det == det) && fabs(det) > 1e-30 && fabs(inv) < 1e30;
-  for (int j = 0; j < 9; ++j) ok = ok && (fabsf(p.Hs[j]) < 1e30f) && (p.Hs[j] == p.Hs[j]);
-  p.ok = ok ? 1.0f : 0.0f;
+  p.ok = adjugate_inverse(H_t2s + (long)i * kUniH, p.Hs) ? 1.0f : 0.0f;
   p.pad[0] = p.pad[1] = 0.0f;   // pad[0] of image 0 doubles as the overflow flag (an int 0)
   prep[i] = p;
 }
@@ -409,6 +381,30 @@ __device__ __forceinline__ UniWindow uni_window(const UniPrep& p, int sx, int sy
   return w;
 }
 
+// Box of a source tile at (xs0, ys0), tw x th pixels: union of its corner pixels' windows (the pre-image of a convex region is
+// convex)
+__device__ __forceinline__ UniWindow tile_box(const UniPrep& p, int xs0, int ys0, int tw, int th, int W, int H) {
+  const UniWindow w0 = uni_window(p, xs0, ys0, W, H), w1 = uni_window(p, xs0 + tw - 1, ys0 + th - 1, W, H);
+  const UniWindow w2 = uni_window(p, xs0 + tw - 1, ys0, W, H), w3 = uni_window(p, xs0, ys0 + th - 1, W, H);
+  UniWindow b;
+  b.x0 = min(min(w0.x0, w1.x0), min(w2.x0, w3.x0)); b.x1 = max(max(w0.x1, w1.x1), max(w2.x1, w3.x1));
+  b.y0 = min(min(w0.y0, w1.y0), min(w2.y0, w3.y0)); b.y1 = max(max(w0.y1, w1.y1), max(w2.y1, w3.y1));
+  return b;
+}
+
+// Gather lists under a wave-uniform bound: the largest list of the wave (a scalar), so a wave pays for its longest lane only.
+// (Unused entries: weight 0, index 0.)
+__device__ __forceinline__ int wave_list_max(int cnt) {
+  int kmax = cnt;
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) kmax = max(kmax, __shfl_xor(kmax, off, kWave));
+  return __builtin_amdgcn_readfirstlane(kmax);
+}
+// Entries a staged gather reads, given the wave's largest list: four for everybody (the regular case, a near-isometric map
+// gives four contributors), the rest wave-bounded — and none for a wave without a single contributor (see
+// uniform_bwd_pass2_staged_kernel).
+__device__ __forceinline__ int wave_list_bound(int kmax) { return kmax == 0 ? 0 : max(kmax, 4); }
+
 // OVERFLOW = false: the main kernel; source pixels with more than kUniK contributors are left alone.
 // OVERFLOW = true:  the follow-up kernel; it repeats the scan, returns at once for everybody else and re-scans the
 //                   candidates per plane for those pixels (strong minification only).  Kept out of the main kernel: with the
@@ -427,7 +423,7 @@ __device__ __forceinline__ PairLS load_ls(const float* __restrict__ tmp_b, long 
 }
 
 template <bool MIX, bool OVERFLOW>
-__global__ __launch_bounds__(kBlock) void uniform_bwd_pass2_kernel(SweepArgs a, int b0, const float* __restrict__ tmp,
+__global__ __launch_bounds__(kBlock) void uniform_bwd_pass2_kernel(SweepArgs a, const float* __restrict__ tmp,
                                                                    const UniPrep* __restrict__ prep,
                                                                    float* __restrict__ g_logits, float* __restrict__ g_sigma,
                                                                    int* __restrict__ overflow_flag, int accumulate,
@@ -435,9 +431,9 @@ __global__ __launch_bounds__(kBlock) void uniform_bwd_pass2_kernel(SweepArgs a, 
   // list_limit (OVERFLOW only): the register slots of the kernel this one follows (kUniK, or kPairK after the pair kernel)
   const int HW = a.H * a.W, N = a.N, W = a.W, H = a.H;
   const int spix = xcd_banded(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
-  const int b = b0 + blockIdx.y;
+  const int b = blockIdx.y;
   if (OVERFLOW && *overflow_flag == 0) return;   // nobody asked for the re-scan: the usual case, no second scan
-  const float* __restrict__ tmp_b = tmp + (long)blockIdx.y * 2 * N * HW;
+  const float* __restrict__ tmp_b = tmp + (long)b * 2 * N * HW;
   if (spix >= HW) return;
   const int sy = spix / W, sx = spix - sy * W;
   const CoordNorm cn = make_coord_norm(W, H);
@@ -487,12 +483,8 @@ __global__ __launch_bounds__(kBlock) void uniform_bwd_pass2_kernel(SweepArgs a, 
     return;
   }
   if (cnt > kUniK) { atomicOr(overflow_flag, 1); return; }   // the follow-up kernel's
-  // Four entries for everybody (a near-isometric map gives four contributors), the rest under a wave-uniform bound:
-  // kmax = the largest list in the wave, so a wave pays for its longest lane only.  (Unused entries: weight 0, index 0.)
-  int kmax = cnt;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) kmax = max(kmax, __shfl_xor(kmax, off, kWave));
-  kmax = __builtin_amdgcn_readfirstlane(kmax);
+  // Four entries for everybody, the rest under the wave-uniform bound
+  const int kmax = wave_list_max(cnt);
 #pragma unroll 2
   for (int n = 0; n < N; ++n) {
     const long base = (long)n * HW;
@@ -544,32 +536,26 @@ constexpr int kStageThreads = kStageW * kStageH;   // one thread per source pixe
 constexpr int kStagePre = (kStageBox * kStageP + kStageThreads - 1) / kStageThreads;   // staged elements per thread and group
 
 template <bool MIX>
-__global__ __launch_bounds__(kStageThreads) void uniform_bwd_pass2_staged_kernel(SweepArgs a, int b0, const float* __restrict__ tmp,
+__global__ __launch_bounds__(kStageThreads) void uniform_bwd_pass2_staged_kernel(SweepArgs a, const float* __restrict__ tmp,
                                                                           const UniPrep* __restrict__ prep,
                                                                           float* __restrict__ g_logits, float* __restrict__ g_sigma,
                                                                           int* __restrict__ overflow_flag, int tiles_x, int accumulate) {
   typedef typename std::conditional<MIX, float2, float>::type Elem;
   __shared__ Elem buf[2][kStageP][kStageBox];
   const int HW = a.H * a.W, N = a.N, W = a.W, H = a.H;
-  const int by = blockIdx.y;
-  const int b = b0 + by, tid = threadIdx.x;
+  const int b = blockIdx.y, tid = threadIdx.x;
   const int blk = xcd_banded(blockIdx.x, gridDim.x);
   const int tyi = blk / tiles_x, txi = blk - tyi * tiles_x;
   const int xs0 = txi * kStageW, ys0 = tyi * kStageH;
   const int tw_ = min(kStageW, W - xs0), th = min(kStageH, H - ys0);
-  const Elem* __restrict__ tmp_b = reinterpret_cast<const Elem*>(tmp + (long)by * 2 * N * HW);
+  const Elem* __restrict__ tmp_b = reinterpret_cast<const Elem*>(tmp + (long)b * 2 * N * HW);
   const CoordNorm cn = make_coord_norm(W, H);
   const float* Hm = a.plane + (long)b * kUniH;
   const float* Ki = a.inv_K3 + (long)b * 9;
   const UniPrep pr = prep[b];
-  int bx0, bx1, by0, by1;   // box of the tile: union of its corner pixels' windows (the pre-image of a convex region is convex)
-  {
-    const UniWindow w0 = uni_window(pr, xs0, ys0, W, H), w1 = uni_window(pr, xs0 + tw_ - 1, ys0 + th - 1, W, H);
-    const UniWindow w2 = uni_window(pr, xs0 + tw_ - 1, ys0, W, H), w3 = uni_window(pr, xs0, ys0 + th - 1, W, H);
-    bx0 = min(min(w0.x0, w1.x0), min(w2.x0, w3.x0)); bx1 = max(max(w0.x1, w1.x1), max(w2.x1, w3.x1));
-    by0 = min(min(w0.y0, w1.y0), min(w2.y0, w3.y0)); by1 = max(max(w0.y1, w1.y1), max(w2.y1, w3.y1));
-  }
-  const int bw = max(bx1 - bx0 + 1, 0), bh = max(by1 - by0 + 1, 0);
+  const UniWindow box = tile_box(pr, xs0, ys0, tw_, th, W, H);
+  const int bx0 = box.x0, by0 = box.y0;
+  const int bw = max(box.x1 - bx0 + 1, 0), bh = max(box.y1 - by0 + 1, 0);
   const int npx = bw * bh;
   const bool staged = npx <= kStageBox;          // workgroup-uniform
   const int lx = tid & (kStageW - 1), ly = tid >> 5;
@@ -598,15 +584,12 @@ __global__ __launch_bounds__(kStageThreads) void uniform_bwd_pass2_staged_kernel
   }
   bool live = has_s;
   if (cnt > kUniK) { atomicOr(overflow_flag, 1); live = false; cnt = 0; }   // the follow-up kernel's pixel
-  int kmax = cnt;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) kmax = max(kmax, __shfl_xor(kmax, off, kWave));
-  kmax = __builtin_amdgcn_readfirstlane(kmax);
+  const int kmax = wave_list_max(cnt);
   // Entries a lane does not use have weight 0 and slot 0.  Slot 0 of the staged box holds a real value as soon as ANY
   // lane of the workgroup has a contributor (contributors lie in the box, so the box is not empty); a wave without a
   // single contributor must not read LDS at all — the box may be empty and the buffer uninitialised, and 0 * garbage is
   // NaN when the garbage is (seen once in ~40 runs of the minification test on fresh boxes).
-  const int kuse = kmax == 0 ? 0 : max(kmax, 4);   // four entries for everybody (the regular case), the rest wave-bounded
+  const int kuse = wave_list_bound(kmax);
   float* gl = (live && g_logits) ? g_logits + (long)b * N * HW + (long)sy * W + sx : nullptr;
   float* gs = (live && MIX && g_sigma) ? g_sigma + (long)b * N * HW + (long)sy * W + sx : nullptr;
 
@@ -753,13 +736,11 @@ __global__ __launch_bounds__(kStageThreads) void uniform_bwd_pass2_pair_kernel(P
 #pragma unroll
   for (int v = 0; v < kPairViews; ++v) {
     const UniPrep pr = pa.prep[v][b];
-    const UniWindow w0 = uni_window(pr, xs0, ys0, W, H), w1 = uni_window(pr, xs0 + tw_ - 1, ys0 + th - 1, W, H);
-    const UniWindow w2 = uni_window(pr, xs0 + tw_ - 1, ys0, W, H), w3 = uni_window(pr, xs0, ys0 + th - 1, W, H);
-    bx0[v] = min(min(w0.x0, w1.x0), min(w2.x0, w3.x0));
-    by0[v] = min(min(w0.y0, w1.y0), min(w2.y0, w3.y0));
-    const int bx1 = max(max(w0.x1, w1.x1), max(w2.x1, w3.x1)), by1 = max(max(w0.y1, w1.y1), max(w2.y1, w3.y1));
-    bw[v] = max(bx1 - bx0[v] + 1, 0);
-    npx[v] = bw[v] * max(by1 - by0[v] + 1, 0);
+    const UniWindow box = tile_box(pr, xs0, ys0, tw_, th, W, H);
+    bx0[v] = box.x0;
+    by0[v] = box.y0;
+    bw[v] = max(box.x1 - box.x0 + 1, 0);
+    npx[v] = bw[v] * max(box.y1 - box.y0 + 1, 0);
     staged = staged && npx[v] <= kStageBox;
     tmp_b[v] = reinterpret_cast<const Elem*>(pa.tmp[v] + (long)b * 2 * N * HW);
   }
@@ -788,11 +769,7 @@ __global__ __launch_bounds__(kStageThreads) void uniform_bwd_pass2_pair_kernel(P
     if (cnt > kPairK) { atomicOr(pa.overflow[v], 1); cnt = 0;   // this view's follow-up kernel adds the pixel's share
 #pragma unroll
       for (int k = 0; k < kPairK; ++k) { idx[v][k] = 0; wgt[v][k] = 0.0f; } }
-    int kmax = cnt;
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) kmax = max(kmax, __shfl_xor(kmax, off, kWave));
-    kmax = __builtin_amdgcn_readfirstlane(kmax);
-    kuse[v] = kmax == 0 ? 0 : max(kmax, 4);   // (a wave without contributors must not read the possibly empty box)
+    kuse[v] = wave_list_bound(wave_list_max(cnt));   // (a wave without contributors must not read the possibly empty box)
   }
   const long s_off = (long)b * N * HW + (long)sy * W + sx;
   float* gl = (has_s && g_logits) ? g_logits + s_off : nullptr;
@@ -899,16 +876,22 @@ size_t uniform_bwd_workspace_floats(const pd_sweep_desc* d) {
          (size_t)d->B * 2 * d->N * d->H * d->W + 8;
 }
 
+// The target-side kernels' <MIX, RENDER>
+template <typename F>
+static int dispatch_mix_render(const pd_sweep_desc* d, F f) {
+  return dispatch_bool((d->flags & PD_MIXTURE) != 0, [&](auto mix) {
+    return dispatch_bool((d->flags & PD_RENDER_PROB) != 0, [&](auto render) { return f(mix, render); });
+  });
+}
+
 template <bool PAIR>
 static int uniform_fwd_launch(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, float* ph_map, float* stash,
                               const UniViewB& vb, hipStream_t stream) {
-  dim3 grid((PAIR ? 2 : 1) * ceil_div(d->H * d->W, kBlock), d->B);
-  const bool mix = (d->flags & PD_MIXTURE) != 0, render = (d->flags & PD_RENDER_PROB) != 0;
-  if (mix) { if (render) uniform_fwd_kernel<true, true, PAIR><<<grid, kBlock, 0, stream>>>(a, rgb_rec, ph_map, stash, vb);
-             else        uniform_fwd_kernel<true, false, PAIR><<<grid, kBlock, 0, stream>>>(a, rgb_rec, ph_map, stash, vb); }
-  else     { if (render) uniform_fwd_kernel<false, true, PAIR><<<grid, kBlock, 0, stream>>>(a, rgb_rec, ph_map, stash, vb);
-             else        uniform_fwd_kernel<false, false, PAIR><<<grid, kBlock, 0, stream>>>(a, rgb_rec, ph_map, stash, vb); }
-  return check_launch("uniform_fwd_kernel");
+  const dim3 grid((PAIR ? 2 : 1) * ceil_div(d->H * d->W, kBlock), d->B);
+  return dispatch_mix_render(d, [&](auto mix, auto render) {
+    uniform_fwd_kernel<decltype(mix)::value, decltype(render)::value, PAIR><<<grid, kBlock, 0, stream>>>(a, rgb_rec, ph_map, stash, vb);
+    return check_launch("uniform_fwd_kernel");
+  });
 }
 int uniform_fwd(const pd_sweep_desc* d, const SweepArgs& a, float* rgb_rec, float* ph_map, float* stash, hipStream_t stream) {
   return uniform_fwd_launch<false>(d, a, rgb_rec, ph_map, stash, UniViewB{}, stream);
@@ -933,55 +916,70 @@ static UniformWs uniform_ws(const pd_sweep_desc* d, float* workspace) {
   return w;
 }
 
-// `tw` = a.padding_mask slot: [B][N][3] translation weights n/d, or NULL (no translation gradient wanted)
-int uniform_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, float* workspace, hipStream_t stream) {
-  const int HW = d->H * d->W, nblk = ceil_div(HW, kBlock);
-  const bool mix = (d->flags & PD_MIXTURE) != 0;
-  const UniformWs w = uniform_ws(d, workspace);
-  float* part_two = w.part_two;
-  UniPrep* prep = w.prep;
-  float* tmp = w.tmp;
+// One view's prepare kernel and first pass; `what` names the first pass in the text a failed launch reports.  `tw` =
+// a.padding_mask slot: [B][N][3] translation weights n/d, or NULL (no translation gradient wanted).
+static int uniform_pass1(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, const UniformWs& w, const char* what,
+                         hipStream_t stream) {
+  uniform_prep_kernel<<<ceil_div(d->B, 64), 64, 0, stream>>>(a.plane, w.prep, d->B);
+  const int rc = check_launch("uniform_prep_kernel");
+  if (rc) return rc;
   const float* tw = a.padding_mask;
   SweepArgs ak = a;
   ak.padding_mask = nullptr;
-  uniform_prep_kernel<<<ceil_div(d->B, 64), 64, 0, stream>>>(a.plane, prep, d->B);
-  int rc = check_launch("uniform_prep_kernel");
-  if (rc) return rc;
-  int* overflow = w.overflow;
+  const dim3 grid(ceil_div(d->H * d->W, kBlock), d->B);
+  return dispatch_mix_render(d, [&](auto mix, auto render) {
+    uniform_bwd_pass1_kernel<decltype(mix)::value, decltype(render)::value><<<grid, kBlock, 0, stream>>>(ak, o, w.tmp, w.part_two, tw);
+    return check_launch(what);
+  });
+}
+
+// what the pass-2 kernels read of a view's arguments: the shape and the two matrices (no translation weights in the mask slot)
+static SweepArgs gather_args(const pd_sweep_desc* d, const float* plane, const float* inv_K3) {
+  SweepArgs a{};
+  a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W; a.flags = d->flags;
+  a.plane = plane; a.inv_K3 = inv_K3;
+  return a;
+}
+
+// The follow-up of a pass 2 that kept `list_limit` entries per source pixel: returns at once unless a list overflowed
+static int uniform_followup(const pd_sweep_desc* d, const SweepArgs& a, const UniformWs& w, float* g_logits, float* g_sigma,
+                            int accumulate, int list_limit, const char* what, hipStream_t stream) {
+  const dim3 grid(ceil_div(d->H * d->W, kBlock), d->B);
+  return dispatch_bool((d->flags & PD_MIXTURE) != 0, [&](auto mix) {
+    uniform_bwd_pass2_kernel<decltype(mix)::value, true><<<grid, kBlock, 0, stream>>>(a, w.tmp, w.prep, g_logits, g_sigma, w.overflow, accumulate, list_limit);
+    return check_launch(what);
+  });
+}
+
+int uniform_bwd(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& o, float* workspace, hipStream_t stream) {
+  const int nblk = ceil_div(d->H * d->W, kBlock);
+  const bool mix = (d->flags & PD_MIXTURE) != 0;
+  const UniformWs w = uniform_ws(d, workspace);
+  const char* what = "uniform_bwd_pass kernels";
   // Measured at 8x49x192x640 (pose_net-like rotations): two-pass 0.27 + 0.38 = 0.65 ms, both passes in one kernel with an
   // LDS hand-over per plane 0.75 ms — sixteen waves meeting at a barrier 49 times cost more than the 770 MB the scratch
   // tensor moves.  The whole batch goes in one launch per pass: 1 / 2 / 4 / 8 images per launch measured 2.16 / 1.83 /
   // 1.42 / 0.99 ms — parallelism beats keeping the scratch in the memory-side cache.
-  const int accumulate = (d->flags & PD_BWD_ACCUMULATE) ? 1 : 0;
-  const bool render = (d->flags & PD_RENDER_PROB) != 0;
-  const bool defer = (d->flags & PD_BWD_DEFER_GATHER) != 0;   // pass 2 is pd_uniform_gather_pair's
-  const dim3 grid(nblk, d->B);
-  const int stiles_x = ceil_div(d->W, kStageW);
-  const dim3 sgrid(stiles_x * ceil_div(d->H, kStageH), d->B);
-  // pass 2 with the scratch staged through LDS unless PD_IMPL_UNIFORM_DIRECT asks for the direct gather (cross-check)
-  const bool staged = d->impl != PD_IMPL_UNIFORM_DIRECT;
-  if (mix) {
-    if (render) uniform_bwd_pass1_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, tmp, part_two, tw);
-    else        uniform_bwd_pass1_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, tmp, part_two, tw);
-    if (defer) { /* the caller gathers: pd_uniform_gather_pair */ }
-    else {
-    if (staged) uniform_bwd_pass2_staged_kernel<true><<<sgrid, kStageThreads, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, o.g_sigma, overflow, stiles_x, accumulate);
-    else uniform_bwd_pass2_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, o.g_sigma, overflow, accumulate);
-    uniform_bwd_pass2_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, o.g_sigma, overflow, accumulate);
-    }
-  } else {
-    if (render) uniform_bwd_pass1_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, tmp, part_two, tw);
-    else        uniform_bwd_pass1_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, tmp, part_two, tw);
-    if (defer) { /* the caller gathers: pd_uniform_gather_pair */ }
-    else {
-    if (staged) uniform_bwd_pass2_staged_kernel<false><<<sgrid, kStageThreads, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, nullptr, overflow, stiles_x, accumulate);
-    else uniform_bwd_pass2_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, nullptr, overflow, accumulate);
-    uniform_bwd_pass2_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, 0, tmp, prep, o.g_logits, nullptr, overflow, accumulate);
-    }
+  int rc = uniform_pass1(d, a, o, w, what, stream);
+  if (rc) return rc;
+  if (!(d->flags & PD_BWD_DEFER_GATHER)) {   // (deferred: pass 2 is pd_uniform_gather_pair's)
+    const int accumulate = (d->flags & PD_BWD_ACCUMULATE) ? 1 : 0;
+    const int stiles_x = ceil_div(d->W, kStageW);
+    const dim3 grid(nblk, d->B), sgrid(stiles_x * ceil_div(d->H, kStageH), d->B);
+    const SweepArgs ag = gather_args(d, a.plane, a.inv_K3);
+    float* g_sigma = mix ? o.g_sigma : nullptr;
+    // pass 2 with the scratch staged through LDS unless PD_IMPL_UNIFORM_DIRECT asks for the direct gather (cross-check)
+    const bool staged = d->impl != PD_IMPL_UNIFORM_DIRECT;
+    rc = dispatch_bool(mix, [&](auto mx) {
+      constexpr bool MIX = decltype(mx)::value;
+      if (staged) uniform_bwd_pass2_staged_kernel<MIX><<<sgrid, kStageThreads, 0, stream>>>(ag, w.tmp, w.prep, o.g_logits, g_sigma, w.overflow, stiles_x, accumulate);
+      else uniform_bwd_pass2_kernel<MIX, false><<<grid, kBlock, 0, stream>>>(ag, w.tmp, w.prep, o.g_logits, g_sigma, w.overflow, accumulate);
+      return check_launch(what);
+    });
+    if (!rc) rc = uniform_followup(d, ag, w, o.g_logits, g_sigma, accumulate, kUniK, what, stream);
   }
-  rc = check_launch("uniform_bwd_pass kernels");
   if (rc || !o.g_plane) return rc;
-  return reduce_partials(part_two, o.g_plane, nblk, kUniG * 9, d->B, stream);
+  return reduce_partials(w.part_two, o.g_plane, nblk, kUniG * 9, d->B, stream);
 }
 
 int uniform_gather_pair(const pd_sweep_desc* d, const float* plane_a, const float* inv_K3_a, float* workspace_a,
@@ -997,20 +995,18 @@ int uniform_gather_pair(const pd_sweep_desc* d, const float* plane_a, const floa
   pa.tmp[0] = wa.tmp; pa.tmp[1] = wb.tmp;
   pa.prep[0] = wa.prep; pa.prep[1] = wb.prep;
   pa.overflow[0] = wa.overflow; pa.overflow[1] = wb.overflow;
+  if (!mix) g_sigma = nullptr;
   const int stiles_x = ceil_div(d->W, kStageW);
-  const dim3 sgrid(stiles_x * ceil_div(d->H, kStageH), d->B), grid(ceil_div(d->H * d->W, kBlock), d->B);
-  if (mix) uniform_bwd_pass2_pair_kernel<true><<<sgrid, kStageThreads, 0, stream>>>(pa, g_logits, g_sigma, stiles_x, accumulate);
-  else     uniform_bwd_pass2_pair_kernel<false><<<sgrid, kStageThreads, 0, stream>>>(pa, g_logits, nullptr, stiles_x, accumulate);
+  const dim3 sgrid(stiles_x * ceil_div(d->H, kStageH), d->B);
+  const char* what = "uniform_bwd_pass2_pair_kernel";
+  int rc = dispatch_bool(mix, [&](auto mx) {
+    uniform_bwd_pass2_pair_kernel<decltype(mx)::value><<<sgrid, kStageThreads, 0, stream>>>(pa, g_logits, g_sigma, stiles_x, accumulate);
+    return check_launch(what);
+  });
   // source pixels with more than kPairK contributors in a view: that view's follow-up adds them (returns at once otherwise)
-  for (int v = 0; v < 2; ++v) {
-    SweepArgs a{};
-    a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W; a.flags = d->flags;
-    a.plane = v ? plane_b : plane_a; a.inv_K3 = v ? inv_K3_b : inv_K3_a;
-    const UniformWs& w = v ? wb : wa;
-    if (mix) uniform_bwd_pass2_kernel<true, true><<<grid, kBlock, 0, stream>>>(a, 0, w.tmp, w.prep, g_logits, g_sigma, w.overflow, 1, kPairK);
-    else     uniform_bwd_pass2_kernel<false, true><<<grid, kBlock, 0, stream>>>(a, 0, w.tmp, w.prep, g_logits, nullptr, w.overflow, 1, kPairK);
-  }
-  return check_launch("uniform_bwd_pass2_pair_kernel");
+  if (!rc) rc = uniform_followup(d, gather_args(d, plane_a, inv_K3_a), wa, g_logits, g_sigma, 1, kPairK, what, stream);
+  if (!rc) rc = uniform_followup(d, gather_args(d, plane_b, inv_K3_b), wb, g_logits, g_sigma, 1, kPairK, what, stream);
+  return rc;
 }
 
 // The whole backward of two plane-uniform views of one source image (pd_uniform_bwd_pair): the first passes, the pair
@@ -1018,27 +1014,11 @@ int uniform_gather_pair(const pd_sweep_desc* d, const float* plane_a, const floa
 int uniform_bwd_pair(const pd_sweep_desc* d, const SweepArgs& a, const BwdOut& oa, float* workspace_a, const SweepArgs& b,
                      const BwdOut& ob, float* workspace_b, float* g_logits, float* g_sigma, hipStream_t stream) {
   const int nblk = ceil_div(d->H * d->W, kBlock);
-  const bool mix = (d->flags & PD_MIXTURE) != 0, render = (d->flags & PD_RENDER_PROB) != 0;
   const UniformWs wa = uniform_ws(d, workspace_a), wb = uniform_ws(d, workspace_b);
-  uniform_prep_kernel<<<ceil_div(d->B, 64), 64, 0, stream>>>(a.plane, wa.prep, d->B);
-  uniform_prep_kernel<<<ceil_div(d->B, 64), 64, 0, stream>>>(b.plane, wb.prep, d->B);
-  int rc = check_launch("uniform_prep_kernel");
-  if (rc) return rc;
   // (both first passes in ONE launch, as the forward does it, was measured: 0.400 ms against 2 x 0.193 — they are paced by
   // their scratch stores, 770 MB for the two views, not by the logits / sigma reads the views could share)
-  for (int v = 0; v < 2 && !rc; ++v) {
-    const SweepArgs& s = v ? b : a;
-    const BwdOut& o = v ? ob : oa;
-    const UniformWs& w = v ? wb : wa;
-    SweepArgs ak = s;
-    ak.padding_mask = nullptr;
-    const dim3 grid(nblk, d->B);
-    if (mix) { if (render) uniform_bwd_pass1_kernel<true, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask);
-               else        uniform_bwd_pass1_kernel<true, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask); }
-    else     { if (render) uniform_bwd_pass1_kernel<false, true><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask);
-               else        uniform_bwd_pass1_kernel<false, false><<<grid, kBlock, 0, stream>>>(ak, o, 0, w.tmp, w.part_two, s.padding_mask); }
-    rc = check_launch("uniform_bwd_pass1_kernel");
-  }
+  int rc = uniform_pass1(d, a, oa, wa, "uniform_bwd_pass1_kernel", stream);
+  if (!rc) rc = uniform_pass1(d, b, ob, wb, "uniform_bwd_pass1_kernel", stream);
   if (rc) return rc;
   if (g_logits) {
     rc = uniform_gather_pair(d, a.plane, a.inv_K3, workspace_a, b.plane, b.inv_K3, workspace_b, g_logits, g_sigma, stream);

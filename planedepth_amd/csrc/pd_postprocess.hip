@@ -866,13 +866,9 @@ static int no_kernel(const char* what, const pd_pp_route& r) {
   return PD_ERR_UNSUPPORTED;
 }
 
-// A route's run-time values as the kernel templates' compile-time constants: f(std::bool_constant<v>{}), and f(std::integral_constant<int,
+// A route's run-time values as the kernel templates' compile-time constants: dispatch_bool (pd_common.h), and f(std::integral_constant<int,
 // V>{}) for the V of the list that r.nmax (NMAX or NPART) equals — no_kernel() if none does.  A generic lambda's call operator is
 // instantiated once per constant, so a `static` inside it exists once per kernel instantiation.
-template <typename F>
-static int dispatch_bool(bool v, F f) {
-  return v ? f(std::true_type{}) : f(std::false_type{});
-}
 template <int... V, typename F>
 static int dispatch_nmax(const char* what, const pd_pp_route& r, F f) {
   int rc = PD_OK;

@@ -255,6 +255,38 @@ __device__ __forceinline__ PlaneGrad plane_grad(const PixelCtx& c, float l, floa
   return g;
 }
 
+// PD_RENDER_PROB: what the front-to-back compositing carries from plane to plane of one pixel
+struct RenderBwd {
+  float T = 1.0f;        // transmittance in front of the current plane
+  float prefix = 0.0f;   // sum_{k <= n} p_k dL/dp_k
+  float Rtot = 0.0f;     // sum over all planes of the same, known in closed form from the pixel's stash
+};
+template <bool MIX>
+__device__ __forceinline__ RenderBwd make_render_bwd(const PixelCtx& c) {
+  RenderBwd rb;
+  rb.Rtot = MIX ? -c.A * c.mx : c.gdotr;
+  return rb;
+}
+
+// One plane of the compositing backward: d prob_k / d alpha_n for k >= n through the transmittance (trainer.py:584-591).
+// `l` is the sampled logit (0 for a masked plane: alpha = 0, the state passes through).  g_dist = d loss / d dists_n; the
+// caller stores it (not for the last plane, which has no distance).
+template <bool MIX>
+__device__ __forceinline__ PlaneGrad render_bwd_step(RenderBwd& rb, const PixelCtx& c, float l, float s, float dist, bool last,
+                                                     float c0, float c1, float c2, float& g_dist) {
+  const float alpha = render_alpha(l, dist, last);
+  const float pn = alpha * rb.T;
+  PlaneGrad pg = plane_grad_p<MIX>(c, pn, s, c0, c1, c2);
+  rb.prefix += pg.g_l * pn;
+  const float keep = 1.0f - alpha + 1e-10f;
+  const float g_alpha = pg.g_l * rb.T - (rb.Rtot - rb.prefix) / keep;
+  const float da = 1.0f - alpha;   // d alpha / d (relu(l) * dist)
+  pg.g_l = (!last && l > 0.0f) ? g_alpha * dist * da : 0.0f;
+  g_dist = g_alpha * fmaxf(l, 0.0f) * da;
+  rb.T *= keep;
+  return pg;
+}
+
 // ---- host side: which kernel family serves a call -----------------------------------------------------------------
 // What the decision may depend on besides the descriptor.
 struct CallFacts {

@@ -1,5 +1,6 @@
 // Per-(pixel, plane) sampling geometry of the general sweep kernels (pd_plane_sweep.hip; the tile kernel that shared it is
-// archived under docs/archive/).
+// archived under docs/archive/), and the geometry pieces they share with the plane-uniform and gather kernels: the gradient
+// of a homography's entries, the inverse matrix of the backward's gathers.
 #pragma once
 #include "pd_sweep.h"
 
@@ -69,6 +70,36 @@ __device__ __forceinline__ PlaneGeom plane_coords(const SweepArgs& a, const Coor
     }
   }
   return g;
+}
+
+// ---- backward: from d loss / d (ix, iy) in pixels to the gradient of a homography's nine entries ------------------------
+// Back through grid_sample's un-normalisation ((size-1)/2) and the reference's normalisation (*2, /(size-1)) in autograd's
+// order (gradient side, no bit-exactness at stake).
+__device__ __forceinline__ float grid_grad_scale(int size) { return (float)(size - 1) / 2 * 2.0f / (float)(size - 1); }
+
+// gpx, gpy: d loss / d (p0 / zc, p1 / zc), i.e. the pixel gradients times grid_grad_scale; inv_z = refined_rcp(zc), handed in
+// (the plane-uniform first pass computes it once per pixel, inside its image guard).
+__device__ __forceinline__ void homography_grad9(float gpx, float gpy, float inv_z, float p0, float p1, bool z_clamped, float fx,
+                                                 float fy, float (&gk)[9]) {
+  const float gp0 = gpx * inv_z, gp1 = gpy * inv_z;
+  const float gz = z_clamped ? 0.0f : -(gp0 * p0 + gp1 * p1) * inv_z;
+  gk[0] = gp0 * fx; gk[1] = gp0 * fy; gk[2] = gp0;
+  gk[3] = gp1 * fx; gk[4] = gp1 * fy; gk[5] = gp1;
+  gk[6] = gz * fx;  gk[7] = gz * fy;  gk[8] = gz;
+}
+
+// Forward homography (source -> target) of a backward's gather: the fp64 adjugate inverse of h[9], rounded to fp32.  False
+// where the matrix is not finite / not invertible.
+__device__ __forceinline__ bool adjugate_inverse(const float* __restrict__ h, float (&Hs)[9]) {
+  const double a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], k = h[7], l = h[8];
+  const double A = e * l - f * k, Bc = -(d * l - f * g), C = d * k - e * g;
+  const double det = a * A + b * Bc + c * C, inv = 1.0 / det;
+  Hs[0] = (float)(A * inv);  Hs[1] = (float)(-(b * l - c * k) * inv); Hs[2] = (float)((b * f - c * e) * inv);
+  Hs[3] = (float)(Bc * inv); Hs[4] = (float)((a * l - c * g) * inv);  Hs[5] = (float)(-(a * f - c * d) * inv);
+  Hs[6] = (float)(C * inv);  Hs[7] = (float)(-(a * k - b * g) * inv); Hs[8] = (float)((a * e - b * d) * inv);
+  bool ok = (det == det) && fabs(det) > 1e-30 && fabs(inv) < 1e30;
+  for (int j = 0; j < 9; ++j) ok = ok && (fabsf(Hs[j]) < 1e30f) && (Hs[j] == Hs[j]);
+  return ok;
 }
 
 // bilinear weight with which target sample (ix, iy) reaches source pixel (sx, sy): torch's own expressions

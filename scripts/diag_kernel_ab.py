@@ -23,6 +23,26 @@ every output tensor is compared on the raw bits.  Two allowances, both reported 
   * g_plane of the cases the row-shift backward serves (render, per-pixel mask, PD_IMPL_ROWS1, odd W): that kernel's assembly is
     byte-identical in both trees and its waves add a row's sums in arrival order, so the tensor is exempt where the first library
     differs from itself in it.
+
+    python scripts/diag_kernel_ab.py --cases homography parent=<path> product
+
+--cases homography: the same comparison for the kernels behind homography_warp and the general path (pd_plane_sweep.hip,
+pd_plane_sweep_uniform.hip, pd_plane_sweep_gather.hip), through pd_plane_sweep_fwd / _bwd, pd_uniform_fwd_pair / pd_uniform_bwd_pair /
+pd_uniform_gather_pair and pd_plane_sweep_layers:
+  * plane-uniform at (B, N, H, W) = (2, 7, 18, 80) — a partial last 256-thread block, partial 32 x 16 tiles on both axes, an odd N for the
+    two-plane staging group — and (1, 5, 6, 96), with the pose draws of tests/test_gpu_parity.py (_f8_pose: ~1 degree, the staged pass 2)
+    and the 3x3 block scaled by 1, 2, 4, 2.6 and 0.45 (lists beyond the 12 / 10 register slots: the follow-up kernel; boxes beyond 1024
+    elements: the workgroup's direct branch); mixture and L1, softmax and render, automask, g_plane with and without translation weights,
+    PD_BWD_ACCUMULATE on and off, PD_IMPL_UNIFORM_DIRECT, the pair entry points and the deferred gather;
+  * one matrix per plane at (2, 7, 8, 80) and (1, 5, 6, 96) (tests/test_gpu_parity.py: _gather_case): the gather backward (PD_IMPL_AUTO, and
+    its direct pass 2) and the scatter backward (PD_IMPL_GENERAL), one plane made irregular (the fix-up kernel), render and accumulate on
+    and off;
+  * disp mode on the general kernels (PD_IMPL_GENERAL): a dense map, a per-pixel mask, N = 33 (a second mask word in the stash);
+  * pd_plane_sweep_layers in its four instantiations.
+Deterministic tensors (rgb_rec, ph_map, the stash, g_dists, g_logits / g_sigma of the plane-uniform and gather backwards, the layer
+tensors) must agree bit for bit.  The order-dependent sums — the scatter backward's g_logits / g_sigma and the fix-up's plane (float
+atomics), g_plane (waves meet in LDS in arrival order), ph_mean (one atomic per workgroup) — get the per-entry allowance above: an entry
+may differ where the first library differs from itself at that entry over its eight runs, and by no more than it does there.
 """
 import argparse
 import ctypes
@@ -46,25 +66,23 @@ def load(path):
     return lib
 
 
-def small_cases(libs, out_path):
-    """Raw-bit comparison of libs[1:] against libs[0] over small shapes that reach every path of the row kernels."""
-    dev = torch.device("cuda:0")
-    st = C.stream_handle(dev)
-    B, H, N = 2, 14, 7
-    g = torch.Generator().manual_seed(20)
-    rnd = lambda *sh: torch.randn(*sh, generator=g).to(dev)
-    uni = lambda *sh: torch.rand(*sh, generator=g).to(dev)
-    IRR = 1                                      # index of the integer-shift plane
-    base = torch.tensor([0.37, 3.0, 200.5, 5000.0, float("nan"), 1.75, 17.25])
-    bits = lambda t: t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-    report, bad, noisy = [], 0, 0
-    kRefRuns = 8                                 # the first library runs every case this often: its own run-to-run difference
+IRR = 1                                          # small cases: index of the integer-shift plane
+kRefRuns = 8                                     # the first library runs every case this often: its own run-to-run difference
                                                  # (a fixed count: a comparison outside the allowance fails, it is not re-sampled)
+bits = lambda t: t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
 
-    def compare(case, runs, rowshift_bwd=False):
+
+class Compare:
+    """Raw-bit comparison of libs[1:] against libs[0], case by case; the report and the counts."""
+
+    def __init__(self, libs):
+        self.libs, self.report, self.bad, self.noisy = libs, [], 0, 0
+
+    def __call__(self, case, runs, rowshift_bwd=False, order_dependent=None):
         """runs: {lib name: [outputs of run 1, run 2, ...]} (dict name -> tensor, or 'rc').  rowshift_bwd: the case's backward is
-        the row-shift backward (pd_plane_sweep_rowshift.hip), not the row-stream one."""
-        nonlocal bad, noisy
+        the row-shift backward (pd_plane_sweep_rowshift.hip), not the row-stream one.  order_dependent (the homography cases):
+        {tensor name: True, or a bool mask} — where the per-entry allowance applies instead of the small cases' irregular-plane rows."""
+        libs = self.libs
         ref_name = libs[0][0]
         ref, again = runs[ref_name][0], runs[ref_name][1:]
         for name, _ in libs[1:]:
@@ -84,7 +102,15 @@ def small_cases(libs, out_path):
                     own_ne = torch.stack([bits(r2[k]) != bits(t) for r2 in again]).any(0)
                     ent.update(max_abs=float(absd(got[k]).nan_to_num(0).max()), reference_run_to_run_differing=int(own_ne.sum()),
                                reference_run_to_run_max_abs=float(own.nan_to_num(0).max()))
-                    if k == "g_plane" and rowshift_bwd:
+                    if order_dependent is not None:
+                        # ORDER-DEPENDENT SUMS of the homography cases: only the tensors (or the part of one) the case names, and there
+                        # only entries at which the first library differs from itself, by no more than it does at that entry.
+                        ent["allowance"] = "order-dependent sum, per entry" if k in order_dependent else "none"
+                        region = torch.zeros_like(ne)
+                        if k in order_dependent:
+                            region |= order_dependent[k] if torch.is_tensor(order_dependent[k]) else torch.ones_like(ne)
+                        allowed = region & own_ne & (absd(got[k]) <= own)      # (a NaN difference compares False)
+                    elif k == "g_plane" and rowshift_bwd:
                         # ROW-SHIFT G_PLANE EXCEPTION.  The row-shift backward's waves add their disparity-gradient sums of a row
                         # in LDS in the order they arrive, so entries of every plane in view differ between two runs of ONE library;
                         # its assembly is byte-identical in both trees (profiles/row_layer_refactor_ab.md §1.1), so the new
@@ -115,12 +141,32 @@ def small_cases(libs, out_path):
                         row["noisy"] = True
                 row["tensors"][k] = ent
             row["ok"] = ok
-            bad += 0 if ok else 1
-            report.append(row)
+            self.bad += 0 if ok else 1
+            self.report.append(row)
             diff = {k: v for k, v in row["tensors"].items() if v["differing"]}
-            noisy += 1 if (ok and row.get("noisy")) else 0
+            self.noisy += 1 if (ok and row.get("noisy")) else 0
             print("%-4s %-58s %-10s rc %d/%d  %s" % (("noisy" if row.get("noisy") else "ok") if ok else "FAIL", case, name, got["rc"], ref["rc"], diff or "0 differing bits in %d tensors" % len(row["tensors"])),
                   flush=True)
+
+    def finish(self, mode, out_path):
+        print("%d comparisons, %d failed, %d differing inside an allowance only (noisy)" % (len(self.report), self.bad, self.noisy))
+        if out_path:
+            with open(out_path, "w") as fh:
+                json.dump({"mode": mode, "libs": [n for n, _ in self.libs], "failed": self.bad, "noisy": self.noisy, "reference_runs": kRefRuns,
+                           "comparisons": self.report}, fh, indent=1)
+        return 1 if self.bad else 0
+
+
+def small_cases(libs, out_path):
+    """Raw-bit comparison of libs[1:] against libs[0] over small shapes that reach every path of the row kernels."""
+    dev = torch.device("cuda:0")
+    st = C.stream_handle(dev)
+    B, H, N = 2, 14, 7
+    g = torch.Generator().manual_seed(20)
+    rnd = lambda *sh: torch.randn(*sh, generator=g).to(dev)
+    uni = lambda *sh: torch.rand(*sh, generator=g).to(dev)
+    base = torch.tensor([0.37, 3.0, 200.5, 5000.0, float("nan"), 1.75, 17.25])
+    compare = Compare(libs)
 
     def fresh(*sh, dtype=torch.float32):   # outputs start from the same pattern in every run: an unwritten element compares equal
         return torch.full(sh, -7.0, device=dev, dtype=dtype)
@@ -232,11 +278,203 @@ def small_cases(libs, out_path):
                     warp_case(W, sign, N, flip, rows)
         pp_case(W, N)
         pp_case(W, 63)
-    print("%d comparisons, %d failed, %d differing inside an allowance only (noisy)" % (len(report), bad, noisy))
-    if out_path:
-        with open(out_path, "w") as fh:
-            json.dump({"mode": "cases small", "libs": [n for n, _ in libs], "failed": bad, "noisy": noisy, "reference_runs": kRefRuns, "comparisons": report}, fh, indent=1)
-    return 1 if bad else 0
+    return compare.finish("cases small", out_path)
+
+
+def homography_cases(libs, out_path):
+    """Raw-bit comparison of libs[1:] against libs[0] over small shapes that reach every branch of the homography-mode and general
+    kernels (the module docstring lists them)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_parity import _f8_pose, _gather_case   # the suite's pose and per-plane-matrix draws
+    from planedepth_amd import ops
+    from planedepth_amd.synthetic import intrinsics
+    dev = torch.device("cuda:0")
+    st = C.stream_handle(dev)
+    compare = Compare(libs)
+    P = lambda t: None if t is None else C.ptr(t)
+    fresh = lambda *sh: torch.full(sh, -7.0, device=dev)   # outputs start from the same pattern in every run
+    ALL = True
+
+    def each_run(fn):
+        """fn(lib) -> outputs; the first library kRefRuns times."""
+        runs = {}
+        for name, lib in libs:
+            runs[name] = []
+            for _ in range(kRefRuns if name == libs[0][0] else 1):
+                out = fn(lib)
+                torch.cuda.synchronize()
+                runs[name].append(out)
+        return runs
+
+    def inputs(B, N, H, W, seed):
+        g = torch.Generator().manual_seed(seed)
+        z = dict(src=torch.rand(B, 3, H, W, generator=g), tgt=torch.rand(B, 3, H, W, generator=g), tgt2=torch.rand(B, 3, H, W, generator=g),
+                 logits=torch.randn(B, N, H, W, generator=g), sigma=0.011 + 0.978 * torch.rand(B, N, H, W, generator=g),
+                 g_rgb=torch.randn(B, 3, H, W, generator=g) * 0.1, g_ph=torch.randn(B, 1, H, W, generator=g) * 0.1,
+                 dists=torch.rand(B, N - 1, H, W, generator=g) * 2.0, distance=0.5 + 5 * torch.rand(B, N, generator=g))
+        z["sigma"][:, :, :, ::9] = 0.005                                  # below the clamp: the gate closes
+        return {k: v.to(dev).contiguous() for k, v in z.items()}
+
+    def sweep(lib, d, z, plane, aux, iK, mask, mix, render, tgt="tgt", ph_mean=True, want_plane=True):
+        """One forward + backward through pd_plane_sweep_fwd / _bwd; every output tensor."""
+        B, N, H, W = d.B, d.N, d.H, d.W
+        k = lib.pd_sweep_stash_floats(ctypes.byref(d)) // (H * W)
+        o = dict(rgb_rec=fresh(B, 3, H, W), ph_map=fresh(B, 1, H, W), ph_mean=fresh(1) if ph_mean else None, stash=fresh(B, max(k, 1), H, W),
+                 g_logits=fresh(B, N, H, W), g_sigma=fresh(B, N, H, W) if mix else None,
+                 g_plane=fresh(*plane.shape) if want_plane else None, g_dists=fresh(B, N - 1, H, W) if render else None)
+        ws = fresh(max(int(lib.pd_sweep_bwd_workspace_floats(ctypes.byref(d))), 1))
+        sg, dd = (P(z["sigma"]) if mix else None), (P(z["dists"]) if render else None)
+        rc = lib.pd_plane_sweep_fwd(ctypes.byref(d), P(z["src"]), P(z[tgt]), P(z["logits"]), sg, P(plane), P(aux), P(iK), P(mask), dd,
+                                    P(o["rgb_rec"]), P(o["ph_map"]), P(o["ph_mean"]), P(o["stash"]), st)
+        if rc == 0:
+            rc = lib.pd_plane_sweep_bwd(ctypes.byref(d), P(z["src"]), P(z[tgt]), P(z["logits"]), sg, P(plane), P(aux), P(iK), P(mask), dd,
+                                        P(o["rgb_rec"]), P(o["stash"]), P(z["g_rgb"]), P(z["g_ph"]), P(z["g_phm"]), P(o["g_logits"]),
+                                        P(o["g_sigma"]), P(o["g_plane"]), P(o["g_dists"]), P(ws), st)
+        o["rc"] = rc
+        o["workspace"] = ws   # (kept alive; the deferred gather reads it)
+        return o
+
+    def drop_ws(runs):
+        for rr in runs.values():
+            for r in rr:
+                r.pop("workspace", None)
+        return runs
+
+    FORMS = [("mix", True, False, False), ("mix_auto", True, True, False), ("l1", False, False, False), ("l1_auto", False, True, False),
+             ("mix_render", True, False, True), ("l1_render_auto", False, True, True)]
+
+    # ---- plane-uniform -------------------------------------------------------------------------------------------------------
+    def uniform_matrices(z, B, N, H, W, rot, zoom, seed):
+        K, inv_K = (t.to(dev) for t in intrinsics(B, H, W))
+        norm = torch.tensor([0.0, 0.0, 1.0])[None, None].repeat(B, N, 1)
+        norm[:, N // 2:] = torch.nn.functional.normalize(torch.tensor([0.0, 1.0, 0.07]), dim=0)   # "xz planes": the facing test differs per plane
+        norm = norm.to(dev)
+        Rt = _f8_pose(B, seed, rot, dev)
+        Rt[:, :2, :3] *= zoom
+        with torch.no_grad():
+            Hm, Rn = ops.homography_matrices_fused(z["distance"], norm, Rt, K, inv_K, C.PD_HMAT_UNIFORM)
+            tw = (norm / z["distance"][..., None]).contiguous()
+        return Hm.contiguous(), Rn.reshape(B * N, 3).contiguous(), inv_K[:, :3, :3].contiguous(), tw
+
+    for (B, N, H, W) in ((2, 7, 18, 80), (1, 5, 6, 96)):
+        z = inputs(B, N, H, W, 900 + W + N)
+        z["g_phm"] = torch.full((1,), 2.0, device=dev)
+        for rot, zoom in ((0.02, 1.0), (0.02, 2.0), (0.02, 4.0), (0.05, 2.6), (0.05, 0.45)):
+            Hm, Rn, iK, tw = uniform_matrices(z, B, N, H, W, rot, zoom, 31 + H)
+            Hm2, Rn2, iK2, tw2 = uniform_matrices(z, B, N, H, W, 0.03 if zoom == 1.0 else 0.02, 1.55 if zoom == 2.6 else 1.0, 32 + H)   # view B
+            for form, mix, automask, render in FORMS:
+                fl = C.PD_HOMO_UNIFORM | (C.PD_MIXTURE if mix else 0) | (C.PD_AUTOMASK if automask else 0) | (C.PD_RENDER_PROB if render else 0)
+                for impl in (C.PD_IMPL_AUTO, C.PD_IMPL_UNIFORM_DIRECT):
+                    for acc in (0, C.PD_BWD_ACCUMULATE):
+                        for weights in (True, False):
+                            d = C.SweepDesc(B, N, H, W, C.PD_WARP_HOMOGRAPHY, fl | acc, 0.0, impl)
+                            runs = each_run(lambda lib: sweep(lib, d, z, Hm, Rn, iK, tw if weights else None, mix, render))
+                            compare("uniform %dx%dx%dx%d rot %.2f zoom %.2f %-14s impl %d acc %d tw %d" % (B, N, H, W, rot, zoom, form, impl, bool(acc), weights),
+                                    drop_ws(runs), order_dependent={"g_plane": ALL, "ph_mean": ALL})
+                # the two views of a step: pd_uniform_fwd_pair + pd_uniform_bwd_pair, and the deferred form (two first passes + pd_uniform_gather_pair)
+                for acc in (0, C.PD_BWD_ACCUMULATE):
+                    d = C.SweepDesc(B, N, H, W, C.PD_WARP_HOMOGRAPHY, fl | acc, 0.0, C.PD_IMPL_AUTO)
+
+                    def pair(lib):
+                        k = lib.pd_sweep_stash_floats(ctypes.byref(d)) // (H * W)
+                        nws = max(int(lib.pd_sweep_bwd_workspace_floats(ctypes.byref(d))), 1)
+                        o, views, keep = {}, [], []
+                        for v, (tgt, hm, rn, ik, w) in enumerate((("tgt", Hm, Rn, iK, tw), ("tgt2", Hm2, Rn2, iK2, tw2))):
+                            t = dict(rgb_rec=fresh(B, 3, H, W), ph_map=fresh(B, 1, H, W), ph_mean=fresh(1), stash=fresh(B, k, H, W),
+                                     g_plane=fresh(B, 4, 3, 3), g_dists=fresh(B, N - 1, H, W) if render else None)
+                            ws = fresh(nws)
+                            keep.append(ws)
+                            views.append(C.sweep_view(tgt=z[tgt], plane=hm, plane_aux=rn, inv_K3=ik, padding_mask=w, dists=z["dists"] if render else None,
+                                                      g_rgb_rec=z["g_rgb"], g_ph_map=z["g_ph"], g_ph_mean=z["g_phm"], workspace=ws, **t))
+                            o.update({"%s%d" % (kk, v): vv for kk, vv in t.items()})
+                        o["g_logits"], o["g_sigma"] = fresh(B, N, H, W), (fresh(B, N, H, W) if mix else None)
+                        sg = P(z["sigma"]) if mix else None
+                        rc = lib.pd_uniform_fwd_pair(ctypes.byref(d), P(z["src"]), P(z["logits"]), sg, ctypes.byref(views[0]), ctypes.byref(views[1]), st)
+                        if rc == 0:
+                            rc = lib.pd_uniform_bwd_pair(ctypes.byref(d), P(z["src"]), P(z["logits"]), sg, ctypes.byref(views[0]), ctypes.byref(views[1]),
+                                                         P(o["g_logits"]), P(o["g_sigma"]), st)
+                        torch.cuda.synchronize()
+                        o["rc"] = rc
+                        return o
+                    compare("uniform pair %dx%dx%dx%d rot %.2f zoom %.2f %-14s acc %d" % (B, N, H, W, rot, zoom, form, bool(acc)), each_run(pair),
+                            order_dependent={"g_plane0": ALL, "g_plane1": ALL, "ph_mean0": ALL, "ph_mean1": ALL})
+
+                    dd = C.SweepDesc(B, N, H, W, C.PD_WARP_HOMOGRAPHY, fl | acc | C.PD_BWD_DEFER_GATHER, 0.0, C.PD_IMPL_AUTO)
+
+                    def deferred(lib):
+                        a = sweep(lib, dd, z, Hm, Rn, iK, tw, mix, render, want_plane=False)
+                        b = sweep(lib, dd, z, Hm2, Rn2, iK2, tw2, mix, render, tgt="tgt2", want_plane=False)
+                        o = {"g_logits": fresh(B, N, H, W), "g_sigma": fresh(B, N, H, W) if mix else None, "g_dists0": a["g_dists"], "g_dists1": b["g_dists"]}
+                        rc = a["rc"] or b["rc"] or lib.pd_uniform_gather_pair(ctypes.byref(dd), P(Hm), P(iK), P(a["workspace"]), P(Hm2), P(iK2), P(b["workspace"]),
+                                                                              P(o["g_logits"]), P(o["g_sigma"]), st)
+                        torch.cuda.synchronize()
+                        o["rc"] = rc
+                        return o
+                    compare("uniform deferred gather %dx%dx%dx%d rot %.2f zoom %.2f %-14s acc %d" % (B, N, H, W, rot, zoom, form, bool(acc)), each_run(deferred),
+                            order_dependent={})
+
+    # ---- one matrix per plane: the gather backward (and its direct pass 2) and the scatter backward -----------------------------------
+    for (B, N, H, W) in ((2, 7, 8, 80), (1, 5, 6, 96)):
+        z = inputs(B, N, H, W, 300 + W + N)
+        z["g_phm"] = torch.full((1,), 3.0, device=dev)
+        _, _, _, _, _, Hm0, Rn0, iK = [t.to(dev).contiguous() for t in _gather_case(B, N, H, W, 300 + W + N)]
+        for irregular in (False, True):
+            Hm, Rn = Hm0.clone(), Rn0.clone()
+            irr = torch.zeros(B, N, H, W, dtype=torch.bool, device=dev)
+            if irregular:   # one plane the gather hands to its atomic fix-up: 16 target pixels per source pixel (_gather_case's first)
+                Hm[0] = torch.tensor([[0.25, 0.0, 0.3 * W], [0.0, 0.25, 0.3 * H], [0.0, 0.0, 1.0]], device=dev)
+                Rn[0] = torch.tensor([0.0, 0.0, 1.0], device=dev)
+                irr[0, 0] = True
+            for form, mix, automask, render in FORMS:
+                fl = (C.PD_MIXTURE if mix else 0) | (C.PD_AUTOMASK if automask else 0) | (C.PD_RENDER_PROB if render else 0)
+                for impl in (C.PD_IMPL_AUTO, C.PD_IMPL_UNIFORM_DIRECT, C.PD_IMPL_GENERAL):
+                    for acc in (0, C.PD_BWD_ACCUMULATE):
+                        d = C.SweepDesc(B, N, H, W, C.PD_WARP_HOMOGRAPHY, fl | acc, 0.0, impl)
+                        runs = each_run(lambda lib: sweep(lib, d, z, Hm, Rn, iK, None, mix, render))
+                        scatter = impl == C.PD_IMPL_GENERAL
+                        od = {"g_plane": ALL, "ph_mean": ALL, "g_logits": ALL if scatter else irr, "g_sigma": ALL if scatter else irr}
+                        compare("planes %dx%dx%dx%d %-14s impl %d acc %d irregular %d" % (B, N, H, W, form, impl, bool(acc), irregular), drop_ws(runs),
+                                order_dependent=od)
+
+    # ---- disp mode on the general kernels: dense map, per-pixel mask, a second mask word ------------------------------------------------
+    B, N, H, W = 2, 33, 8, 80
+    z = inputs(B, N, H, W, 77)
+    z["g_phm"] = torch.full((1,), 1.0, device=dev)
+    g = torch.Generator().manual_seed(78)
+    dense = (torch.rand(B, N, H, W, generator=g) * 30.0 - 4.0).to(dev)
+    mask = (torch.rand(B, N, H, W, generator=g) > 0.2).float().to(dev)
+    planes = (torch.rand(B, N, generator=g) * 30.0).to(dev)
+    for form, mix, automask, render in FORMS:
+        for name, plane, dflag, mk in (("dense+mask", dense, C.PD_DISP_DENSE, mask), ("dense", dense, C.PD_DISP_DENSE, None), ("scalar+mask", planes, 0, mask)):
+            for sign in (1.0, -1.0):
+                fl = dflag | (C.PD_MIXTURE if mix else 0) | (C.PD_AUTOMASK if automask else 0) | (C.PD_RENDER_PROB if render else 0)
+                d = C.SweepDesc(B, N, H, W, C.PD_WARP_DISP, fl, sign, C.PD_IMPL_GENERAL)
+                runs = each_run(lambda lib: sweep(lib, d, z, plane, None, None, mk, mix, render))
+                # (a dense map's g_plane is a per-pixel store: deterministic)
+                od = {"g_logits": ALL, "g_sigma": ALL, "ph_mean": ALL}
+                if not dflag:
+                    od["g_plane"] = ALL
+                compare("disp general %-11s %-14s sign %+d" % (name, form, int(sign)), drop_ws(runs), order_dependent=od)
+
+    # ---- pd_plane_sweep_layers: <disp | homography> x <L1 | mixture>, softmax and render ---------------------------------------------------
+    zh = inputs(2, 7, 8, 80, 387)
+    _, _, _, _, _, Hm, Rn, iK = [t.to(dev).contiguous() for t in _gather_case(2, 7, 8, 80, 387)]
+    for mode, zz, plane, aux, ik, mk, (B, N, H, W) in ((C.PD_WARP_DISP, z, dense, None, None, mask, (2, 33, 8, 80)),
+                                                      (C.PD_WARP_HOMOGRAPHY, zh, Hm, Rn, iK, None, (2, 7, 8, 80))):
+        for mix in (True, False):
+            for render in (False, True):
+                fl = (C.PD_DISP_DENSE if mode == C.PD_WARP_DISP else 0) | (C.PD_MIXTURE if mix else 0) | (C.PD_RENDER_PROB if render else 0)
+                d = C.SweepDesc(B, N, H, W, mode, fl, 1.0, C.PD_IMPL_AUTO)
+
+                def layers(lib):
+                    o = dict(rgb_rec_layered=fresh(B, N, 3, H, W), logit_rec=fresh(B, N, H, W), probability_rec=fresh(B, N, H, W),
+                             sigma_rec=fresh(B, N, H, W) if mix else None, pi_rec=fresh(B, N, H, W) if mix else None)
+                    o["rc"] = lib.pd_plane_sweep_layers(ctypes.byref(d), P(zz["src"]), P(zz["logits"]), P(zz["sigma"]) if mix else None, P(plane), P(aux), P(ik),
+                                                        P(mk), P(zz["dists"]) if render else None, P(o["rgb_rec_layered"]), P(o["logit_rec"]),
+                                                        P(o["probability_rec"]), P(o["sigma_rec"]), P(o["pi_rec"]), st)
+                    return o
+                compare("layers mode %d mix %d render %d" % (mode, mix, render), each_run(layers), order_dependent={})
+    return compare.finish("cases homography", out_path)
 
 
 def main():
@@ -253,7 +491,7 @@ def main():
     ap.add_argument("--fwd_only", action="store_true")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--out", default="")
-    ap.add_argument("--cases", choices=["small"], default=None, help="raw-bit comparison over small shapes instead of timing")
+    ap.add_argument("--cases", choices=["small", "homography"], default=None, help="raw-bit comparison over small shapes instead of timing")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.cases:
@@ -263,7 +501,7 @@ def main():
             path = path or os.path.join(ROOT, "planedepth_amd", "lib", "libplanedepth_hip.so" if name == "product" else "libpd_var_%s.so" % name)
             seen.setdefault(path, load(path))
             named.append((name, seen[path]))
-        sys.exit(small_cases(named, args.out))
+        sys.exit((small_cases if args.cases == "small" else homography_cases)(named, args.out))
     c = survey_fullsize_case(B=args.batch, N=args.planes, H=args.height, W=args.width, seed=1234)
     c = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in c.items()}
     B, N, H, W = c["logits"].shape

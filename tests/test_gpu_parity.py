@@ -2280,6 +2280,7 @@ def _wild_homographies(B, N, H, W, seed):
     return Hm.contiguous(), Rn.contiguous()
 
 
+# (scripts/diag_kernel_ab.py --cases homography imports _gather_case and _f8_pose: keep their names and signatures)
 def _gather_case(B, N, H, W, seed, irregular=False):
     """Inputs of a per-plane homography sweep far from the identity; ``irregular``: some planes the gather backward must
     hand to its atomic fix-up (4x minification, the line at infinity inside the view, a NaN and a singular matrix)."""
@@ -2787,6 +2788,7 @@ def test_on_device_grid_matches_the_reference_pipeline_to_one_ulp():
     assert float((dev["grid"].cpu() - cpu["grid"]).abs().max()) <= 1.2e-7
 
 
+# (also imported by scripts/diag_kernel_ab.py --cases homography)
 def _f8_pose(B, seed, rot=0.02, device="cpu"):
     """Rt as Trainer.predict_poses leaves it for a novel frame without COLMAP (trainer.py:386-400): a rotation
     conjugated by a crop matrix, ZERO translation, Rt[3,3] = 0."""
