@@ -698,6 +698,39 @@ int pd_homography_matrices_bwd(int B, int N, int mode, int rows, const float* di
                                float* g_distance, float* g_norm, float* g_T, pd_stream_t stream);
 
 /*
+ * The pose path in front of pd_homography_matrices_* (pd_pose_tail.hip): the tail of PoseDecoder.forward (pose_net.py:148-155),
+ * transformation_from_parameters' rotation (layers.py:17-92) and the conjugation with Rc (trainer.py:386-400), one launch each way,
+ * evaluated in fp64 (the hw sum included) and rounded once.  Per image b:
+ *   v[0:6]   = scale * mean over hw of x[b, 6 frame + k, :]        axisangle = v[0:3], translation = v[3:6]
+ *   R        = rot_from_axisangle(axisangle), axis = vec / (|vec| + 1e-7) as the reference has it;  invert != 0: R^T
+ *   Rc       = [[1,0,a],[0,1,b],[0,0,f]],  a = -gx0 / (2 0.58), b = -gy0 / (2 1.92),  gx0 = (grid[b,0,0,gW-1] + grid[b,0,0,0]) / 2,
+ *              gy0 = (grid[b,1,gH-1,0] + grid[b,1,0,0]) / 2,  f = (grid[b,0,0,gW-1] - grid[b,0,0,0]) / 2
+ *   Rt_Rc    [B,4,4]: [:3,:3] = Rc R Rc^-1, every other element 0 — [3,3] too (the reference fills a zeros_like)
+ *   x        [B,C,hw] in `dtype` (PD_DTYPE_F32 / PD_DTYPE_BF16) through the ELEMENT strides x_sb (image), x_sc (channel), x_ss
+ *            (position); C = 6 F with frame in [0, F), or C = 3: an axis-angle alone (frame 0; no translation output / gradient).
+ *            An averaged axisangle tensor is hw = 1, scale = 1.
+ *   Rt       COLMAP mode, forward only, given INSTEAD of x (exactly one of the two is non-NULL): [B,4,4] contiguous;
+ *            Rt_Rc[:3,:3] = Rc Rt[:3,:3] Rc^-1, Rt_Rc[:3,3] = Rc Rt[:3,3], row 3 zero; axisangle / translation must be NULL.
+ *   grid     [B,2,gH,gW] fp32 through grid_strides[4] (host array of element strides: image, channel, row, column)
+ * Outputs, each may be NULL: axisangle [B,3], translation [B,3], Rc [B,3,3], Rt_Rc [B,4,4], contiguous fp32.
+ * pd_pose_tail_bwd recomputes from x: g_Rt_Rc [B,4,4] (only [:3,:3] is read), g_axisangle [B,3], g_translation [B,3] — each may be
+ * NULL, not all — -> g_x [B,C,hw] in `dtype` through its own element strides, overwritten in full: channel 6 frame + k gets
+ * scale / hw times its gradient at every position (the translation channels g_translation alone), every other channel exact
+ * zeros.  At vec = 0 the gradient of |vec| is taken as 0 (torch's convention): finite, what the reference's graph yields.  grid and
+ * Rt get no gradient (dataset constants).  One workgroup per image, no float atomics: deterministic.
+ * Refused on the host with PD_ERR_ARG: NULL required pointers, B <= 0, hw <= 0, C neither 3 nor a multiple of 6, frame out of
+ * range, an unknown dtype, gH or gW < 1, C * hw >= 2^31.
+ */
+int pd_pose_tail_fwd(int B, int C, int hw, int frame, int dtype, int invert, double scale, const void* x, int64_t x_sb,
+                     int64_t x_sc, int64_t x_ss, const float* Rt, const float* grid, int gH, int gW,
+                     const int64_t* grid_strides, float* axisangle, float* translation, float* Rc, float* Rt_Rc,
+                     pd_stream_t stream);
+int pd_pose_tail_bwd(int B, int C, int hw, int frame, int dtype, int invert, double scale, const void* x, int64_t x_sb,
+                     int64_t x_sc, int64_t x_ss, const float* grid, int gH, int gW, const int64_t* grid_strides,
+                     const float* g_Rt_Rc, const float* g_axisangle, const float* g_translation, void* g_x, int64_t gx_sb,
+                     int64_t gx_sc, int64_t gx_ss, pd_stream_t stream);
+
+/*
  * Geometry modules.
  *   pd_backproject     BackprojectDepth.forward, layers.py:150-156: depth [B,1,H,W], inv_K [B,4,4] -> cam [B,4,H*W]
  *   pd_backproject_bwd g_cam [B,4,H*W] -> g_depth [B,1,H,W]

@@ -28,7 +28,7 @@ PD_IMPL_AUTO, PD_IMPL_GENERAL, PD_IMPL_FAST_ROWS, PD_IMPL_TILE, PD_IMPL_ROWS1, P
 PD_IMPL_EXACT_ROWS = 6
 PD_EVAL_POST_PROCESS, PD_EVAL_EIGEN, PD_EVAL_MEDIAN, PD_EVAL_TRAINER = 1, 2, 4, 8
 PD_EVAL_TILE = 16384   # GT pixels per tile of pd_depth_eval (enum in the header)
-PD_DTYPE_F32, PD_DTYPE_BF16 = 0, 1   # pd_dtype: the element type of pd_feature_distance_*'s feature tensors
+PD_DTYPE_F32, PD_DTYPE_BF16 = 0, 1   # pd_dtype: the element type of pd_feature_distance_*'s feature tensors and of pd_pose_tail_*'s conv output
 PD_SRC_U8_HWC, PD_SRC_F32_CHW = 0, 1   # pd_src_format: the decoded frames pd_resize_crop_augment reads
 PD_PIPE_GAMMA, PD_PIPE_BRIGHTNESS, PD_PIPE_CHANNEL, PD_PIPE_FLIP = 1, 2, 4, 8   # pd_pipe_flags, per sample
 PD_EMBED_NEURAL, PD_EMBED_FREQUENCY, PD_EMBED_IDENTITY = 0, 1, 2   # pd_embed_kind: what pd_grid_embed_fwd evaluates at a grid point
@@ -140,6 +140,9 @@ SIGNATURES = {
     "pd_masked_photometric_bwd": (_I, [_I] * 4 + [_P] * 9),
     "pd_homography_matrices_fwd": (_I, [_I] * 4 + [_P] * 10),
     "pd_homography_matrices_bwd": (_I, [_I] * 4 + [_P] * 11),
+    "pd_pose_tail_fwd": (_I, [_I] * 6 + [ctypes.c_double, _P, _L, _L, _L, _P, _P, _I, _I, ctypes.POINTER(_L)] + [_P] * 5),
+    "pd_pose_tail_bwd": (_I, [_I] * 6 + [ctypes.c_double, _P, _L, _L, _L, _P, _I, _I, ctypes.POINTER(_L)] + [_P] * 4
+                         + [_L] * 3 + [_P]),
     "pd_backproject": (_I, [_I] * 3 + [_P] * 4),
     "pd_backproject_bwd": (_I, [_I] * 3 + [_P] * 4),
     "pd_project3d": (_I, [_I] * 3 + [_F] + [_P] * 4),

@@ -370,6 +370,51 @@ def patch_trainer_perceptual(trainer_cls):
     return trainer_cls
 
 
+def predict_poses(self, inputs):
+    """Trainer.predict_poses (reference trainer.py:358-402): the same ``outputs`` entries — ``("Rt","r")`` copied from ``inputs``
+    and, per ``f_i`` of ``opt.novel_frame_ids``, ``("axisangle", f_i)``, ``("translation", f_i)`` (not with ``opt.use_colmap``),
+    ``("Rc", f_i)``, ``("Rt", f_i)`` — with the pose encoder and decoder called exactly as the reference calls them (stock
+    convolutions, not part of this package) and everything behind them as ONE launch per frame (ops.pose_matrices), instead of the
+    ~50 operators and the ``torch.inverse`` of layers.py:17-92 + trainer.py:386-400.  A decoder that returns
+    ``planedepth_amd.RawPose(conv_out)`` instead of executing networks/pose_net.py:148-155 has its mean, scale
+    and slices taken in the same launch (ops.pose_tail).  ``self`` only needs ``opt.novel_frame_ids``, ``opt.use_colmap`` and
+    ``models["pose_encoder"]`` / ``models["pose"]``."""
+    from .pose import RawPose
+    outputs = {}
+    outputs[("Rt", "r")] = inputs[("Rt", "r")]
+    grid = inputs["grid"]
+    for f_i in self.opt.novel_frame_ids:
+        if getattr(self.opt, "use_colmap", False):
+            Rt_Rc, Rc = ops.pose_conjugate(inputs[("Rt", f_i)], grid)
+        else:
+            if f_i < 0:
+                pose_inputs = [inputs[("color_aug", f_i)], inputs[("color_aug", "l")]]
+            else:
+                pose_inputs = [inputs[("color_aug", "l")], inputs[("color_aug", f_i)]]
+            pose_inputs = [self.models["pose_encoder"](torch.cat(pose_inputs, 1))]
+            pose = self.models["pose"](pose_inputs, grid)
+            if isinstance(pose, RawPose):
+                axisangle, translation, Rc, Rt_Rc = ops.pose_tail(pose.out, grid, invert=(f_i < 0))
+                if pose.out.shape[1] != 6:   # the reference's [B,F,1,3] of every frame; the matrix is frame 0's (axisangle[:, 0])
+                    rest = [ops.pose_tail(pose.out, grid, frame=k)[:2] for k in range(1, pose.out.shape[1] // 6)]
+                    axisangle = torch.cat([axisangle] + [r[0] for r in rest], 1)
+                    translation = torch.cat([translation] + [r[1] for r in rest], 1)
+            else:
+                axisangle, translation = pose
+                Rt_Rc, Rc = ops.pose_matrices(axisangle[:, 0], grid, invert=(f_i < 0))
+            outputs[("axisangle", f_i)] = axisangle
+            outputs[("translation", f_i)] = translation
+        outputs[("Rc", f_i)] = Rc
+        outputs[("Rt", f_i)] = Rt_Rc
+    return outputs
+
+
+def patch_trainer_poses(trainer_cls):
+    """Opt-in: bind :func:`predict_poses` to a reference ``Trainer`` class (``patch_trainer`` leaves it alone)."""
+    trainer_cls.predict_poses = predict_poses
+    return trainer_cls
+
+
 def patch_trainer(trainer_cls):
     """Bind the fused hot path onto a reference-style Trainer class (drop-in)."""
     trainer_cls.pred_novel_images = pred_novel_images
