@@ -29,21 +29,21 @@ if int(os.environ.get("PD_DEBUG_POISON_MEM", "0")):
     _real_torch = torch
     torch = _PoisonedTorch()
 class _timed:
-    """Record a pair of events around a launch when ops.KERNEL_EVENTS is set (no cost otherwise)."""
+    """Record a pair of events around a launch on ``device`` when ops.KERNEL_EVENTS is set (no cost otherwise)."""
 
-    def __init__(self, kind):
-        self.kind = kind
+    def __init__(self, kind, device):
+        self.kind, self.device = kind, device
 
     def __enter__(self):
         if S.KERNEL_EVENTS is not None:
             self.a = torch.cuda.Event(enable_timing=True)
             self.b = torch.cuda.Event(enable_timing=True)
-            self.a.record()
+            self.a.record(torch.cuda.current_stream(self.device))   # (the launch's stream: C.call switches to the device itself)
         return self
 
     def __exit__(self, *exc):
         if S.KERNEL_EVENTS is not None:
-            self.b.record()
+            self.b.record(torch.cuda.current_stream(self.device))
             S.KERNEL_EVENTS.setdefault(self.kind, []).append((self.a, self.b))
         return False
 

@@ -2,36 +2,20 @@
 
 There is deliberately NO fallback: if the shared library is missing or a symbol is absent, importing the product
 ops raises.  The library is built in-tree by ``__graft_entry__.build()`` (``hipcc --offload-arch=gfx950``).
+
+The header is the one declaration of the boundary: the prototypes (``SIGNATURES``) and the ``PD_*`` constants are read from
+it when this module is imported, and the three struct mirrors below are compared with its members.  Adding an entry point
+means declaring it in the header and defining it; nothing is repeated here.  Launches go through ``call``.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (imported first so the process already holds torch's libamdhip64 — one HIP runtime only)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PD_LIB") or os.path.join(_HERE, "lib", "libplanedepth_hip.so")  # PD_LIB: diagnostics builds
-
-PD_WARP_DISP, PD_WARP_HOMOGRAPHY = 0, 1
-PD_MIXTURE, PD_AUTOMASK, PD_RENDER_PROB, PD_DISP_DENSE, PD_DISP_ROWS, PD_MASK_ROWS, PD_HOMO_UNIFORM = 1, 2, 4, 8, 16, 32, 64
-PD_BWD_ACCUMULATE = 128
-PD_BWD_DEFER_GATHER = 256
-PD_PH_MEAN_ZEROED = 512
-PD_BWD_PLANE_ZEROED = 1024
-PD_LOGITS_BF16 = 2048   # logits / sigma / g_logits / g_sigma hold bf16 (pd_sweep_native_bf16)
-PD_PAD_ZEROS, PD_PAD_BORDER = 0, 1
-PD_TAIL_MIXTURE, PD_TAIL_DISP_DENSE = 1, 2
-PD_TAIL_BF16 = 4   # raw_logits / raw_sigma / logits / sigma and their gradients hold bf16 (both decoder tails)
-PD_TAIL_DISP_ROWS, PD_TAIL_MASK_ROWS = 8, 16   # disp_layered (and its gradient) / padding_mask are [B,N,H] (decoder tail only)
-PD_PP_DISP_DENSE, PD_PP_FLIP_SRC, PD_PP_DISP_ROWS = 1, 2, 4
-PD_HMAT_PLANES, PD_HMAT_UNIFORM, PD_HMAT_STEREO_ROWS = 0, 1, 2
-PD_IMPL_AUTO, PD_IMPL_GENERAL, PD_IMPL_FAST_ROWS, PD_IMPL_TILE, PD_IMPL_ROWS1, PD_IMPL_UNIFORM_DIRECT = 0, 1, 2, 3, 4, 5
-PD_IMPL_EXACT_ROWS = 6
-PD_EVAL_POST_PROCESS, PD_EVAL_EIGEN, PD_EVAL_MEDIAN, PD_EVAL_TRAINER = 1, 2, 4, 8
-PD_EVAL_TILE = 16384   # GT pixels per tile of pd_depth_eval (enum in the header)
-PD_DTYPE_F32, PD_DTYPE_BF16 = 0, 1   # pd_dtype: the element type of pd_feature_distance_*'s feature tensors and of pd_pose_tail_*'s conv output
-PD_SRC_U8_HWC, PD_SRC_F32_CHW = 0, 1   # pd_src_format: the decoded frames pd_resize_crop_augment reads
-PD_PIPE_GAMMA, PD_PIPE_BRIGHTNESS, PD_PIPE_CHANNEL, PD_PIPE_FLIP = 1, 2, 4, 8   # pd_pipe_flags, per sample
-PD_EMBED_NEURAL, PD_EMBED_FREQUENCY, PD_EMBED_IDENTITY = 0, 1, 2   # pd_embed_kind: what pd_grid_embed_fwd evaluates at a grid point
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "planedepth_hip.h")   # the one declaration of the C boundary
 
 
 class SweepDesc(ctypes.Structure):
@@ -56,113 +40,96 @@ def sweep_view(**tensors):
     return v
 
 
-PD_PP_KIND_SOFTMAX, PD_PP_KIND_SUM = 0, 1
-PD_PP_FAMILIES = ("gather", "rows", "seg", "single", "chain", "chain_split")   # pd_pp_family, by value
-
-
 class PpRoute(ctypes.Structure):
     """Mirror of ``pd_pp_route``: the kernel a post-process call is served by (pd_warp_route / pd_post_process_route)."""
     _fields_ = [("family", ctypes.c_int32), ("flip", ctypes.c_int32), ("nmax", ctypes.c_int32), ("rows2", ctypes.c_int32),
                 ("alias", ctypes.c_int32), ("lds_bytes", ctypes.c_uint32)]
 
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_F = ctypes.c_float
-_L = ctypes.c_int64
-_D = ctypes.POINTER(SweepDesc)
+class PlaneDepthHipError(RuntimeError):
+    pass
 
-# name -> (restype, argtypes); must list every symbol include/planedepth_hip.h declares
-SIGNATURES = {
-    "pd_version": (_I, []),
-    "pd_last_error": (ctypes.c_char_p, []),
-    "pd_source_hash": (ctypes.c_char_p, []),
-    "pd_sweep_uses_rowshift": (_I, [_D]),
-    "pd_sweep_native_bf16": (_I, [_D]),
-    "pd_sweep_auto_row_eps": (_F, []),
-    "pd_sweep_bwd_accumulates": (_I, [_D]),
-    "pd_sweep_bwd_plane_adds": (_I, [_D]),
-    "pd_sweep_stash_floats": (ctypes.c_size_t, [_D]),
-    "pd_sweep_bwd_workspace_floats": (ctypes.c_size_t, [_D]),
-    "pd_plane_sweep_fwd": (_I, [_D] + [_P] * 14),
-    "pd_plane_sweep_bwd": (_I, [_D] + [_P] * 20),
-    "pd_plane_sweep_layers": (_I, [_D] + [_P] * 14),
-    "pd_sweep_bwd_tail_fuses": (_I, [_D]),
-    "pd_plane_sweep_bwd_tail": (_I, [_D] + [_P] * 20),
-    "pd_sweep_bwd_tail_rows_fuses": (_I, [_D]),
-    "pd_plane_sweep_bwd_tail_rows": (_I, [_D] + [_P] * 21),
-    "pd_uniform_gather_pair": (_I, [_D] + [_P] * 9),
-    "pd_uniform_fwd_pair": (_I, [_D] + [_P] * 3 + [ctypes.POINTER(SweepView)] * 2 + [_P]),
-    "pd_uniform_bwd_pair": (_I, [_D] + [_P] * 3 + [ctypes.POINTER(SweepView)] * 2 + [_P] * 3),
-    "pd_ssim_fwd": (_I, [_I] * 4 + [_P] * 4),
-    "pd_ssim_bwd": (_I, [_I] * 4 + [_P] * 6),
-    "pd_reproj_loss_fwd": (_I, [_I] * 4 + [_P] * 4),
-    "pd_reproj_loss_bwd": (_I, [_I] * 4 + [_P] * 6),
-    "pd_mixture_nll_fwd": (_I, [_I] * 5 + [_P] * 5),
-    "pd_mixture_nll_bwd": (_I, [_I] * 5 + [_P] * 8),
-    "pd_decoder_tail_bwd_workspace_floats": (ctypes.c_size_t, [_I] * 4),
-    "pd_decoder_tail_fwd": (_I, [_I] * 5 + [_P] * 10),
-    "pd_decoder_tail_layers": (_I, [_I] * 5 + [_P] * 7),
-    "pd_decoder_tail_bwd": (_I, [_I] * 5 + [_P] * 15),
-    "pd_plade_tail_fwd": (_I, [_I] * 5 + [_P] * 11),
-    "pd_plade_tail_layers": (_I, [_I] * 5 + [_P] * 8),
-    "pd_plade_tail_bwd": (_I, [_I] * 5 + [_P] * 16),
-    "pd_decoder_tail_infer": (_I, [_I] * 5 + [_P] * 11),
-    "pd_plade_tail_infer": (_I, [_I] * 5 + [_P] * 11),
-    "pd_smooth_loss_fwd": (_I, [_I] * 4 + [_P, _L, _L, _P, _L, _L, _L, _F, _P, _P]),
-    "pd_smooth_loss_bwd": (_I, [_I] * 4 + [_P, _L, _L, _P, _L, _L, _L, _F, _P, _P, _P]),
-    "pd_smooth_loss_bwd_padded": (_I, [_I] * 5 + [_P, _L, _L, _P, _L, _L, _L, _F, _P, _P, _P]),
-    "pd_warp_softmax": (_I, [_I] * 4 + [_F, _I, _P, _P, _P, _P]),
-    "pd_warp_sum": (_I, [_I] * 4 + [_F, _I, _P, _P, _F, _P, _P]),
-    "pd_post_process_workspace_floats": (ctypes.c_size_t, [_I] * 4),
-    "pd_post_process": (_I, [_I] * 5 + [_P] * 8),
-    "pd_warp_route": (_I, [_I] * 6 + [_P, ctypes.POINTER(PpRoute)]),
-    "pd_post_process_route": (_I, [_I] * 5 + [_P, _P, ctypes.POINTER(PpRoute)]),
-    "pd_pp_combine": (_I, [_I] * 3 + [_P] * 5),
-    "pd_cat_flip": (_I, [_I] * 4 + [_P, _P, _I, _P, _P]),
-    "pd_plane_levels_fwd": (_I, [_I, _I, _F, _F, _F, _P, _P, _P, _P]),
-    "pd_plane_levels_bwd": (_I, [_I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
-    "pd_plane_geometry_fwd": (_I, [_I] * 6 + [_F] * 4 + [_P] * 7),
-    "pd_plane_geometry_bwd": (_I, [_I] * 6 + [_F] * 4 + [_P] * 7),
-    "pd_crop_grid": (_I, [_I] * 3 + [_P, _P, _P]),
-    "pd_resize_crop_augment": (_I, [_I] * 7 + [_P] * 8),
-    "pd_resize_crop_nearest": (_I, [_I] * 5 + [_P] * 6),
-    "pd_grid_embed_fwd": (_I, [_I] * 7 + [_P] * 5),
-    "pd_grid_embed_bwd_workspace_floats": (ctypes.c_size_t, [_I] * 3 + [_P]),
-    "pd_grid_embed_bwd": (_I, [_I] * 5 + [_P] * 7),
-    "pd_selftest_division": (_I, [_F, _I, _F, _F, _P, _P]),
-    "pd_experiments": (_I, []),
-    "pd_build_flags": (_I, []),
-    "pd_debug_gather_flags": (_I, [_D, _P, _P, _P]),
-    "pd_debug_poison_lds": (_I, [_P]),
-    "pd_debug_count_lds_nans": (_I, [_P, _P]),
-    "pd_masked_photometric_fwd": (_I, [_I] * 4 + [_P] * 9),
-    "pd_masked_photometric_bwd": (_I, [_I] * 4 + [_P] * 9),
-    "pd_homography_matrices_fwd": (_I, [_I] * 4 + [_P] * 10),
-    "pd_homography_matrices_bwd": (_I, [_I] * 4 + [_P] * 11),
-    "pd_pose_tail_fwd": (_I, [_I] * 6 + [ctypes.c_double, _P, _L, _L, _L, _P, _P, _I, _I, ctypes.POINTER(_L)] + [_P] * 5),
-    "pd_pose_tail_bwd": (_I, [_I] * 6 + [ctypes.c_double, _P, _L, _L, _L, _P, _I, _I, ctypes.POINTER(_L)] + [_P] * 4
-                         + [_L] * 3 + [_P]),
-    "pd_backproject": (_I, [_I] * 3 + [_P] * 4),
-    "pd_backproject_bwd": (_I, [_I] * 3 + [_P] * 4),
-    "pd_project3d": (_I, [_I] * 3 + [_F] + [_P] * 4),
-    "pd_project3d_bwd": (_I, [_I] * 3 + [_F] + [_P] * 7),
-    "pd_homography_grid": (_I, [_I] * 3 + [_P] * 6),
-    "pd_homography_grid_bwd": (_I, [_I] * 3 + [_P] * 5),
-    "pd_grid_sample_fwd": (_I, [_I] * 7 + [_P] * 4),
-    "pd_grid_sample_bwd": (_I, [_I] * 7 + [_P] * 6),
-    "pd_depth_eval_workspace_bytes": (ctypes.c_size_t, [_I] * 3),
-    "pd_depth_eval": (_I, [_I] * 5 + [_F, _F, _P, _P, _I] + [_P] * 8),
-    "pd_depth_eval_resize": (_I, [_I] * 5 + [_P] * 4),
-    "pd_feature_distance_fwd": (_I, [_I] * 5 + [_P] * 6 + [_I, _P]),
-    "pd_feature_distance_bwd": (_I, [_I] * 5 + [_P] * 6),
-}
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "int32_t": ctypes.c_int32,
+            "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "pd_stream_t": ctypes.c_void_p}
+_DATA = ("void", "float", "int", "int32_t", "int64_t", "uint8_t")   # pointees of a data pointer: c_void_p
+_MIRRORS = {"pd_sweep_desc": SweepDesc, "pd_sweep_view": SweepView, "pd_pp_route": PpRoute}
+
+
+def _ctype(text, decl, result=False):
+    """The ctypes type of one parameter (or of the result) of ``decl``; a type outside the header's vocabulary raises."""
+    m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*\w*", text.strip())
+    base, star = m.groups() if m else (None, None)
+    if not star and base in _SCALARS:
+        return _SCALARS[base]
+    if star and base in _MIRRORS:
+        return ctypes.POINTER(_MIRRORS[base])
+    if star and base in _DATA and not result:
+        return ctypes.c_void_p
+    if star and base == "char" and result:
+        return ctypes.c_char_p
+    raise PlaneDepthHipError("%s: no ctypes mapping for `%s` in `%s`" % (HEADER_PATH, text.strip(), decl))
+
+
+def _parse_header():
+    """(constants, prototypes) of the header: every ``PD_X = n`` of every enum, and name -> (restype, argtypes) for every
+    ``ret pd_name(params);``.  The struct mirrors are compared with the header's members on the way."""
+    try:
+        with open(HEADER_PATH) as f:
+            text = f.read()
+    except OSError as e:
+        raise PlaneDepthHipError("planedepth_amd: cannot read the C header %s (%s); the prototypes and constants are derived "
+                                 "from it and there is no fallback table" % (HEADER_PATH, e))
+    text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", " ", text, flags=re.S | re.M)   # comments, preprocessor lines
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    constants, members = {}, {}
+
+    def enum(m):
+        for item in filter(None, (i.strip() for i in m.group(1).split(","))):
+            kv = re.fullmatch(r"(PD_\w+)\s*=\s*(-?\d+)", item)
+            if not kv:
+                raise PlaneDepthHipError("%s: cannot read the enum value `%s` (decimal literals only)" % (HEADER_PATH, item))
+            constants[kv.group(1)] = int(kv.group(2))
+        return ""
+
+    def struct(m):
+        members[m.group(1)] = re.findall(r"(\w+)\s*[,;]", m.group(2))
+        return ""
+    text = re.sub(r"\benum\b\s*\w*\s*\{([^}]*)\}\s*;", enum, text)
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{([^}]*)\}\s*\1\s*;", struct, text)
+    text = re.sub(r"\btypedef\s+void\s*\*\s*pd_stream_t\s*;", "", text)
+    for c_name, mirror in _MIRRORS.items():
+        if members.get(c_name) != [f[0] for f in mirror._fields_]:
+            raise PlaneDepthHipError("%s: %s has the members %s, its mirror %s has %s" % (
+                HEADER_PATH, c_name, members.get(c_name), mirror.__name__, [f[0] for f in mirror._fields_]))
+    prototypes = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(.+?)\b(pd_\w+) ?\(([^()]*)\)", decl)
+        if not m:
+            raise PlaneDepthHipError("%s: cannot read the declaration `%s`" % (HEADER_PATH, decl))
+        ret, name, params = m.groups()
+        params = [] if params.strip() == "void" else params.split(",")
+        prototypes[name] = (_ctype(ret, decl, result=True), [_ctype(p, decl) for p in params])
+    return constants, prototypes
+
+
+# Everything the header declares, derived from it: the PD_* enum values as module attributes, and
+# SIGNATURES: name -> (restype, argtypes).  A new entry point is declared in the header and defined; nothing is added here.
+_CONSTANTS, SIGNATURES = _parse_header()
+globals().update(_CONSTANTS)
+PD_PP_FAMILIES = tuple(k[len("PD_PP_FAMILY_"):].lower()   # pd_pp_family, by value
+                       for k in sorted((k for k in _CONSTANTS if k.startswith("PD_PP_FAMILY_")), key=_CONSTANTS.get))
 
 _lib = None
 
 
-class PlaneDepthHipError(RuntimeError):
-    pass
+def bind(lib):
+    """Attach the header's prototypes to a loaded library (``load`` does; so do scripts that side-load another build)."""
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+    return lib
 
 
 def load():
@@ -174,13 +141,8 @@ def load():
         raise PlaneDepthHipError(
             "planedepth_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU or PyTorch fallback for the hot path." % LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    _lib = bind(ctypes.CDLL(LIB_PATH))
+    return _lib
 
 
 def check(rc, what):
@@ -243,6 +205,22 @@ def stream_handle(device=None):
     if POISON_LDS:   # a kernel that reads shared memory it never wrote then produces NaNs instead of luck
         load().pd_debug_poison_lds(h)
     return h
+
+
+def call(name, device, *args):
+    """Launch the stream-taking entry point ``name`` on torch's current stream of ``device``: ``args`` are the header's
+    parameters without the trailing ``pd_stream_t``.  A tensor passes its ``data_ptr()``, None is NULL, everything else
+    (numbers, ``byref(...)``, ctypes arrays) goes through as it is.  A wrong argument count is a TypeError before anything
+    touches the device; a refusal by the library raises PlaneDepthHipError with its message.  Contiguity, dtypes and
+    keeping temporaries alive until the launch are the caller's business."""
+    fn = getattr(load(), name)
+    if len(args) + 1 != len(fn.argtypes):
+        raise TypeError("%s takes %d arguments before its stream, got %d" % (name, len(fn.argtypes) - 1, len(args)))
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    with on_device(device):
+        rc = fn(*args, stream_handle(device))
+    if rc:
+        check(rc, name)
 
 
 def require_gpu_tensor(name, t, shape=None, dtype=torch.float32):

@@ -35,12 +35,9 @@ def _split(flat, B, E, sizes):
 
 
 def _launch_fwd(grid, sizes, kind, E, multires, params):
-    lib = C.load()
     B, _, H, W = (int(s) for s in grid.shape)
     flat = torch.empty(B * E * sum(h * w for h, w in sizes), device=grid.device, dtype=torch.float32)
-    with C.on_device(grid.device):
-        C.check(lib.pd_grid_embed_fwd(B, H, W, kind, E, multires, len(sizes), _sizes_array(sizes), C.ptr(grid), C.ptr(params),
-                                      C.ptr(flat), C.stream_handle(grid.device)), "pd_grid_embed_fwd")
+    C.call("pd_grid_embed_fwd", grid.device, B, H, W, kind, E, multires, len(sizes), _sizes_array(sizes), grid, params, flat)
     return flat
 
 
@@ -73,9 +70,7 @@ class _GridEmbedding(torch.autograd.Function):
         arr = _sizes_array(sizes)
         ws = torch.empty(int(lib.pd_grid_embed_bwd_workspace_floats(B, E, len(sizes), arr)), device=dev, dtype=torch.float32)
         g_params = torch.empty_like(params)
-        with C.on_device(dev):
-            C.check(lib.pd_grid_embed_bwd(B, H, W, E, len(sizes), arr, C.ptr(grid), C.ptr(params), C.ptr(g_out), C.ptr(g_params),
-                                          C.ptr(ws), C.stream_handle(dev)), "pd_grid_embed_bwd")
+        C.call("pd_grid_embed_bwd", dev, B, H, W, E, len(sizes), arr, grid, params, g_out, g_params, ws)
         cuts = (0, 2 * HIDDEN, 3 * HIDDEN, 3 * HIDDEN + E * HIDDEN, 3 * HIDDEN + E * HIDDEN + E)
         grads = tuple(g_params[cuts[k]:cuts[k + 1]].view(ctx.shapes[k]).to(ctx.dtypes[k]) if ctx.needs_input_grad[2 + k] else None
                       for k in range(4))

@@ -14,29 +14,23 @@ from .sweep import homography_matrices, homography_matrices_fused
 class _Backproject(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, inv_K):
-        lib = C.load()
         B, _, H, W = depth.shape
         C.require_gpu_tensor("depth", depth, (B, 1, H, W))
         C.require_gpu_tensor("inv_K", inv_K, (B, 4, 4))
         depth, inv_K = depth.contiguous(), inv_K.contiguous()
         cam = torch.empty(B, 4, H * W, device=depth.device, dtype=torch.float32)
-        with C.on_device(depth.device):
-            C.check(lib.pd_backproject(B, H, W, C.ptr(depth), C.ptr(inv_K), C.ptr(cam), C.stream_handle(depth.device)),
-                    "pd_backproject")
+        C.call("pd_backproject", depth.device, B, H, W, depth, inv_K, cam)
         ctx.save_for_backward(inv_K)
         ctx.hw = (H, W)
         return cam
 
     @staticmethod
     def backward(ctx, g_cam):
-        lib = C.load()
         (inv_K,) = ctx.saved_tensors
         H, W = ctx.hw
         B = inv_K.shape[0]
         g_depth = torch.empty(B, 1, H, W, device=g_cam.device, dtype=torch.float32)
-        with C.on_device(g_cam.device):
-            C.check(lib.pd_backproject_bwd(B, H, W, C.ptr(inv_K), C.ptr(g_cam.contiguous()), C.ptr(g_depth),
-                                           C.stream_handle(g_cam.device)), "pd_backproject_bwd")
+        C.call("pd_backproject_bwd", g_cam.device, B, H, W, inv_K, g_cam.contiguous(), g_depth)
         return g_depth, None
 
 
@@ -48,31 +42,25 @@ def backproject_depth(depth, inv_K):
 class _Project3D(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cam, P, H, W, eps):
-        lib = C.load()
         B = cam.shape[0]
         C.require_gpu_tensor("points", cam, (B, 4, H * W))
         C.require_gpu_tensor("P", P, (B, 3, 4))
         cam, P = cam.contiguous(), P.contiguous()
         grid = torch.empty(B, H, W, 2, device=cam.device, dtype=torch.float32)
-        with C.on_device(cam.device):
-            C.check(lib.pd_project3d(B, H, W, eps, C.ptr(cam), C.ptr(P), C.ptr(grid), C.stream_handle(cam.device)),
-                    "pd_project3d")
+        C.call("pd_project3d", cam.device, B, H, W, eps, cam, P, grid)
         ctx.save_for_backward(cam, P)
         ctx.cfg = (H, W, eps)
         return grid
 
     @staticmethod
     def backward(ctx, g_grid):
-        lib = C.load()
         cam, P = ctx.saved_tensors
         H, W, eps = ctx.cfg
         B = cam.shape[0]
         g_cam = torch.empty_like(cam) if ctx.needs_input_grad[0] else None
         g_P = torch.empty_like(P) if ctx.needs_input_grad[1] else None
         ws = torch.empty(12 * B * ((H * W + 255) // 256), device=cam.device, dtype=torch.float32) if g_P is not None else None
-        with C.on_device(cam.device):
-            C.check(lib.pd_project3d_bwd(B, H, W, eps, C.ptr(cam), C.ptr(P), C.ptr(g_grid.contiguous()), C.ptr(g_cam),
-                                         C.ptr(g_P), C.ptr(ws), C.stream_handle(cam.device)), "pd_project3d_bwd")
+        C.call("pd_project3d_bwd", cam.device, B, H, W, eps, cam, P, g_grid.contiguous(), g_cam, g_P, ws)
         return g_cam, g_P, None, None, None
 
 
@@ -85,7 +73,6 @@ def project_3d(points, K, T, height, width, eps=1e-7):
 class _HomographyGrid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, H_t2s, Rn, inv_K3, H, W):
-        lib = C.load()
         M = H_t2s.shape[0]
         C.require_gpu_tensor("H_t2s", H_t2s, (M, 3, 3))
         C.require_gpu_tensor("Rn", Rn, (M, 3))
@@ -93,9 +80,7 @@ class _HomographyGrid(torch.autograd.Function):
         H_t2s, Rn, inv_K3 = H_t2s.contiguous(), Rn.contiguous(), inv_K3.contiguous()
         grid = torch.empty(M, H, W, 2, device=H_t2s.device, dtype=torch.float32)
         mask = torch.empty(M, H, W, device=H_t2s.device, dtype=torch.uint8)
-        with C.on_device(H_t2s.device):
-            C.check(lib.pd_homography_grid(M, H, W, C.ptr(H_t2s), C.ptr(Rn), C.ptr(inv_K3), C.ptr(grid), C.ptr(mask),
-                                           C.stream_handle(H_t2s.device)), "pd_homography_grid")
+        C.call("pd_homography_grid", H_t2s.device, M, H, W, H_t2s, Rn, inv_K3, grid, mask)
         ctx.save_for_backward(H_t2s)
         ctx.hw = (H, W)
         ctx.mark_non_differentiable(mask)
@@ -103,15 +88,12 @@ class _HomographyGrid(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_grid, _g_mask):
-        lib = C.load()
         (H_t2s,) = ctx.saved_tensors
         H, W = ctx.hw
         M = H_t2s.shape[0]
         g_H = torch.empty_like(H_t2s)
         ws = torch.empty(9 * M * ((H * W + 255) // 256), device=H_t2s.device, dtype=torch.float32)
-        with C.on_device(H_t2s.device):
-            C.check(lib.pd_homography_grid_bwd(M, H, W, C.ptr(H_t2s), C.ptr(g_grid.contiguous()), C.ptr(g_H), C.ptr(ws),
-                                               C.stream_handle(H_t2s.device)), "pd_homography_grid_bwd")
+        C.call("pd_homography_grid_bwd", H_t2s.device, M, H, W, H_t2s, g_grid.contiguous(), g_H, ws)
         return g_H, None, None, None, None
 
 
@@ -129,23 +111,19 @@ def homography_grid(d, n, T, K, inv_K, height, width):
 class _GridSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, grid, padding_mode):
-        lib = C.load()
         M, Cc, Hi, Wi = inp.shape
         _, Ho, Wo, two = grid.shape
         C.require_gpu_tensor("input", inp)
         C.require_gpu_tensor("grid", grid, (M, Ho, Wo, 2))
         inp, grid = inp.contiguous(), grid.contiguous()
         out = torch.empty(M, Cc, Ho, Wo, device=inp.device, dtype=torch.float32)
-        with C.on_device(inp.device):
-            C.check(lib.pd_grid_sample_fwd(M, Cc, Hi, Wi, Ho, Wo, padding_mode, C.ptr(inp), C.ptr(grid), C.ptr(out),
-                                           C.stream_handle(inp.device)), "pd_grid_sample_fwd")
+        C.call("pd_grid_sample_fwd", inp.device, M, Cc, Hi, Wi, Ho, Wo, padding_mode, inp, grid, out)
         ctx.save_for_backward(inp, grid)
         ctx.padding_mode = padding_mode
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = C.load()
         inp, grid = ctx.saved_tensors
         M, Cc, Hi, Wi = inp.shape
         _, Ho, Wo, _ = grid.shape
@@ -153,10 +131,8 @@ class _GridSample(torch.autograd.Function):
         g_grid = torch.empty_like(grid) if ctx.needs_input_grad[1] else None
         if g_in is None and g_grid is None:
             return None, None, None
-        with C.on_device(inp.device):
-            C.check(lib.pd_grid_sample_bwd(M, Cc, Hi, Wi, Ho, Wo, ctx.padding_mode, C.ptr(inp), C.ptr(grid),
-                                           C.ptr(g_out.contiguous()), C.ptr(g_in), C.ptr(g_grid),
-                                           C.stream_handle(inp.device)), "pd_grid_sample_bwd")
+        C.call("pd_grid_sample_bwd", inp.device, M, Cc, Hi, Wi, Ho, Wo, ctx.padding_mode, inp, grid, g_out.contiguous(), g_in,
+               g_grid)
         return g_in, g_grid, None
 
 

@@ -16,29 +16,24 @@ from ._buffers import torch, _timed, _desc, _contig, _zero_scalar, _zero_block, 
 class _SSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y):
-        lib = C.load()
         C.require_gpu_tensor("x", x)
         C.require_gpu_tensor("y", y, x.shape)
         x, y = x.contiguous(), y.contiguous()
         B, Cc, H, W = x.shape
         out = torch.empty_like(x)
-        with C.on_device(x.device):
-            C.check(lib.pd_ssim_fwd(B, Cc, H, W, C.ptr(x), C.ptr(y), C.ptr(out), C.stream_handle(x.device)), "pd_ssim_fwd")
+        C.call("pd_ssim_fwd", x.device, B, Cc, H, W, x, y, out)
         ctx.save_for_backward(x, y)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = C.load()
         x, y = ctx.saved_tensors
         B, Cc, H, W = x.shape
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
         if gx is None and gy is None:
             return None, None
-        with C.on_device(x.device):
-            C.check(lib.pd_ssim_bwd(B, Cc, H, W, C.ptr(x), C.ptr(y), C.ptr(g.contiguous()), C.ptr(gx), C.ptr(gy),
-                                    C.stream_handle(x.device)), "pd_ssim_bwd")
+        C.call("pd_ssim_bwd", x.device, B, Cc, H, W, x, y, g.contiguous(), gx, gy)
         return gx, gy
 
 
@@ -50,7 +45,6 @@ def ssim(x, y):
 class _ReprojLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, use_ssim):
-        lib = C.load()
         B, Cc, H, W = pred.shape
         if Cc != 3:
             raise ValueError("compute_reprojection_loss expects 3-channel images")
@@ -58,23 +52,18 @@ class _ReprojLoss(torch.autograd.Function):
         C.require_gpu_tensor("target", target, pred.shape)
         pred, target = pred.contiguous(), target.contiguous()
         loss = torch.empty(B, 1, H, W, device=pred.device, dtype=torch.float32)
-        with C.on_device(pred.device):
-            C.check(lib.pd_reproj_loss_fwd(B, H, W, int(use_ssim), C.ptr(pred), C.ptr(target), C.ptr(loss),
-                                           C.stream_handle(pred.device)), "pd_reproj_loss_fwd")
+        C.call("pd_reproj_loss_fwd", pred.device, B, H, W, int(use_ssim), pred, target, loss)
         ctx.save_for_backward(pred, target)
         ctx.use_ssim = int(use_ssim)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        lib = C.load()
         pred, target = ctx.saved_tensors
         B, _, H, W = pred.shape
         gp = torch.empty_like(pred)
         gt = torch.empty_like(target) if ctx.needs_input_grad[1] else None
-        with C.on_device(pred.device):
-            C.check(lib.pd_reproj_loss_bwd(B, H, W, ctx.use_ssim, C.ptr(pred), C.ptr(target), C.ptr(g.contiguous()),
-                                           C.ptr(gp), C.ptr(gt), C.stream_handle(pred.device)), "pd_reproj_loss_bwd")
+        C.call("pd_reproj_loss_bwd", pred.device, B, H, W, ctx.use_ssim, pred, target, g.contiguous(), gp, gt)
         return gp, gt, None
 
 
@@ -86,23 +75,19 @@ def reprojection_loss(pred, target, use_ssim=True):
 class _MixtureNLL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, error, sigma, pi, laplacian):
-        lib = C.load()
         C.require_gpu_tensor("error", error)
         B, N, H, W = error.shape
         error, sigma, pi = (t.expand(B, N, H, W).contiguous() for t in (error, sigma, pi))
         C.require_gpu_tensor("sigma", sigma)
         C.require_gpu_tensor("pi", pi)
         out = torch.empty(B, 1, H, W, device=error.device, dtype=torch.float32)
-        with C.on_device(error.device):
-            C.check(lib.pd_mixture_nll_fwd(B, N, H, W, int(laplacian), C.ptr(error), C.ptr(sigma), C.ptr(pi), C.ptr(out),
-                                           C.stream_handle(error.device)), "pd_mixture_nll_fwd")
+        C.call("pd_mixture_nll_fwd", error.device, B, N, H, W, int(laplacian), error, sigma, pi, out)
         ctx.save_for_backward(error, sigma, pi)
         ctx.lap = int(laplacian)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = C.load()
         error, sigma, pi = ctx.saved_tensors
         B, N, H, W = error.shape
         ge = torch.empty_like(error) if ctx.needs_input_grad[0] else None
@@ -110,10 +95,7 @@ class _MixtureNLL(torch.autograd.Function):
         gp = torch.empty_like(pi) if ctx.needs_input_grad[2] else None
         if ge is None and gs is None and gp is None:
             return None, None, None, None
-        with C.on_device(error.device):
-            C.check(lib.pd_mixture_nll_bwd(B, N, H, W, ctx.lap, C.ptr(error), C.ptr(sigma), C.ptr(pi),
-                                           C.ptr(g.contiguous()), C.ptr(ge), C.ptr(gs), C.ptr(gp),
-                                           C.stream_handle(error.device)), "pd_mixture_nll_bwd")
+        C.call("pd_mixture_nll_bwd", error.device, B, N, H, W, ctx.lap, error, sigma, pi, g.contiguous(), ge, gs, gp)
         return ge, gs, gp, None
 
 
@@ -130,7 +112,6 @@ def multimodal_loss(error, sigma, pi, dist="gaussian"):
 class _MaskedPhotometric(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb_rec, ph_map, target, source, mask):
-        lib = C.load()
         B, _, H, W = rgb_rec.shape
         dev = rgb_rec.device
         mix = ph_map is not None
@@ -145,17 +126,13 @@ class _MaskedPhotometric(torch.autograd.Function):
         pred = torch.empty_like(rgb_rec)
         partials = torch.empty(B * ((H * W + 255) // 256), device=dev)
         mean = torch.empty(1, device=dev)
-        with C.on_device(dev):
-            C.check(lib.pd_masked_photometric_fwd(B, H, W, int(mix), C.ptr(rgb_rec), C.ptr(target), C.ptr(source),
-                                                  C.ptr(mask), C.ptr(pm), C.ptr(pred), C.ptr(partials), C.ptr(mean),
-                                                  C.stream_handle(dev)), "pd_masked_photometric_fwd")
+        C.call("pd_masked_photometric_fwd", dev, B, H, W, int(mix), rgb_rec, target, source, mask, pm, pred, partials, mean)
         ctx.save_for_backward(rgb_rec, target, source, mask)
         ctx.mix = mix
         return pred, mean.reshape(())
 
     @staticmethod
     def backward(ctx, g_pred, g_mean):
-        lib = C.load()
         rgb_rec, target, source, mask = ctx.saved_tensors
         B, _, H, W = rgb_rec.shape
         dev = rgb_rec.device
@@ -164,10 +141,8 @@ class _MaskedPhotometric(torch.autograd.Function):
         g_rgb = torch.empty_like(rgb_rec) if ctx.needs_input_grad[0] else None
         g_ph = torch.empty(B, 1, H, W, device=dev) if (ctx.mix and ctx.needs_input_grad[1]) else None
         if g_rgb is not None or g_ph is not None:
-            with C.on_device(dev):
-                C.check(lib.pd_masked_photometric_bwd(B, H, W, int(ctx.mix), C.ptr(rgb_rec), C.ptr(target), C.ptr(source),
-                                                      C.ptr(mask), C.ptr(g_mean), C.ptr(g_pred), C.ptr(g_rgb),
-                                                      C.ptr(g_ph), C.stream_handle(dev)), "pd_masked_photometric_bwd")
+            C.call("pd_masked_photometric_bwd", dev, B, H, W, int(ctx.mix), rgb_rec, target, source, mask, g_mean, g_pred,
+                   g_rgb, g_ph)
         return g_rgb, g_ph, None, None, None
 
 
@@ -190,46 +165,37 @@ class _FeatureDistance(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, levels, has_source, *args):
-        lib = C.load()
         preds, targets = args[:levels], args[levels:2 * levels]
         sources = args[2 * levels:] if has_source else (None,) * levels
         dev = preds[0].device
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         saved = []
-        with C.on_device(dev):
-            stream = C.stream_handle(dev)
-            for i, (p, t, s) in enumerate(zip(preds, targets, sources)):
-                p, t, s = _contig(p.detach()), _contig(t), _contig(s)   # channels-last or sliced features are copied
-                B, Cc, h, w = p.shape
-                sel = torch.empty(B, h, w, device=dev, dtype=torch.uint8)
-                partials = torch.empty(B * ((h * w + 63) // 64), device=dev, dtype=torch.float32)
-                C.check(lib.pd_feature_distance_fwd(B, Cc, h, w, _FEATURE_DTYPES[p.dtype], C.ptr(p), C.ptr(t), C.ptr(s),
-                                                    C.ptr(sel), C.ptr(partials), C.ptr(loss), int(i > 0), stream),
-                        "pd_feature_distance_fwd")
-                saved += [p, t, sel]
+        for i, (p, t, s) in enumerate(zip(preds, targets, sources)):
+            p, t, s = _contig(p.detach()), _contig(t), _contig(s)   # channels-last or sliced features are copied
+            B, Cc, h, w = p.shape
+            sel = torch.empty(B, h, w, device=dev, dtype=torch.uint8)
+            partials = torch.empty(B * ((h * w + 63) // 64), device=dev, dtype=torch.float32)
+            C.call("pd_feature_distance_fwd", dev, B, Cc, h, w, _FEATURE_DTYPES[p.dtype], p, t, s, sel, partials, loss, int(i > 0))
+            saved += [p, t, sel]
         ctx.save_for_backward(*saved)
         ctx.levels = levels
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g_loss):
-        lib = C.load()
         saved = ctx.saved_tensors
         dev = saved[0].device
         g_loss = g_loss.reshape(1).contiguous().float()
         grads = []
-        with C.on_device(dev):
-            stream = C.stream_handle(dev)
-            for i in range(ctx.levels):
-                p, t, sel = saved[3 * i:3 * i + 3]
-                if not ctx.needs_input_grad[2 + i]:
-                    grads.append(None)
-                    continue
-                B, Cc, h, w = p.shape
-                g = torch.empty_like(p)
-                C.check(lib.pd_feature_distance_bwd(B, Cc, h, w, _FEATURE_DTYPES[p.dtype], C.ptr(p), C.ptr(t), C.ptr(sel),
-                                                    C.ptr(g_loss), C.ptr(g), stream), "pd_feature_distance_bwd")
-                grads.append(g)
+        for i in range(ctx.levels):
+            p, t, sel = saved[3 * i:3 * i + 3]
+            if not ctx.needs_input_grad[2 + i]:
+                grads.append(None)
+                continue
+            B, Cc, h, w = p.shape
+            g = torch.empty_like(p)
+            C.call("pd_feature_distance_bwd", dev, B, Cc, h, w, _FEATURE_DTYPES[p.dtype], p, t, sel, g_loss, g)
+            grads.append(g)
         return (None, None) + tuple(grads) + (None,) * (len(ctx.needs_input_grad) - 2 - ctx.levels)
 
 
@@ -291,7 +257,6 @@ def _row_strided(name, t):
 class _SmoothLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, disp, img, gamma, x0):
-        lib = C.load()
         B, Cn, H, Wf = img.shape
         if tuple(disp.shape) != (B, 1, H, Wf):
             raise ValueError("disp must be [B,1,H,W] matching img, got %s vs %s" % (tuple(disp.shape), tuple(img.shape)))
@@ -300,28 +265,23 @@ class _SmoothLoss(torch.autograd.Function):
         out = torch.empty(1, device=disp.device, dtype=torch.float32)
         # the crop [..., x0:] is an offset on the two base pointers: same strides, W - x0 columns
         dptr, iptr = ctypes.c_void_p(disp.data_ptr() + 4 * x0), ctypes.c_void_p(img.data_ptr() + 4 * x0)
-        with C.on_device(disp.device):
-            C.check(lib.pd_smooth_loss_fwd(B, Cn, H, W, dptr, disp.stride(0), disp.stride(2), iptr,
-                                           img.stride(0), img.stride(1), img.stride(2), float(gamma), C.ptr(out),
-                                           C.stream_handle(disp.device)), "pd_smooth_loss_fwd")
+        C.call("pd_smooth_loss_fwd", disp.device, B, Cn, H, W, dptr, disp.stride(0), disp.stride(2), iptr, img.stride(0),
+               img.stride(1), img.stride(2), float(gamma), out)
         ctx.save_for_backward(disp, img)
         ctx.gamma, ctx.x0 = float(gamma), int(x0)
         return out.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        lib = C.load()
         disp, img = ctx.saved_tensors
         B, Cn, H, Wf = img.shape
         x0 = ctx.x0
         g_disp = torch.empty(B, 1, H, Wf, device=disp.device, dtype=torch.float32)
         g = g.reshape(1).contiguous().float()
         dptr, iptr = ctypes.c_void_p(disp.data_ptr() + 4 * x0), ctypes.c_void_p(img.data_ptr() + 4 * x0)
-        with C.on_device(disp.device):
-            # one kernel writes the whole [B,1,H,W] gradient, zeros in the cropped-away columns included
-            C.check(lib.pd_smooth_loss_bwd_padded(B, Cn, H, Wf - x0, x0, dptr, disp.stride(0), disp.stride(2), iptr,
-                                                  img.stride(0), img.stride(1), img.stride(2), ctx.gamma, C.ptr(g),
-                                                  C.ptr(g_disp), C.stream_handle(disp.device)), "pd_smooth_loss_bwd_padded")
+        # one kernel writes the whole [B,1,H,W] gradient, zeros in the cropped-away columns included
+        C.call("pd_smooth_loss_bwd_padded", disp.device, B, Cn, H, Wf - x0, x0, dptr, disp.stride(0), disp.stride(2), iptr,
+               img.stride(0), img.stride(1), img.stride(2), ctx.gamma, g, g_disp)
         return g_disp, None, None, None
 
 

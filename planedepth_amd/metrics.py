@@ -145,10 +145,8 @@ def _launch(M, h, w, flags, max_tiles, disp_num, scale_factor, pred, grid, grid_
     lib = C.load()
     ws = torch.empty(lib.pd_depth_eval_workspace_bytes(M, max_tiles, flags), dtype=torch.uint8, device=device)
     metrics, ratio, medians, counts = _outputs(S, device)
-    with C.on_device(device):
-        C.check(lib.pd_depth_eval(M, h, w, flags, max_tiles, float(np.float32(disp_num)), float(np.float32(scale_factor)),
-                                  C.ptr(pred), C.ptr(grid), grid_w, C.ptr(gt), C.ptr(meta), C.ptr(ws), C.ptr(metrics),
-                                  C.ptr(ratio), C.ptr(medians), C.ptr(counts), C.stream_handle(device)), "pd_depth_eval")
+    C.call("pd_depth_eval", device, M, h, w, flags, max_tiles, float(np.float32(disp_num)), float(np.float32(scale_factor)),
+           pred, grid, grid_w, gt, meta, ws, metrics, ratio, medians, counts)
     return DepthEval(metrics, ratio, medians, counts)
 
 
@@ -194,10 +192,8 @@ def resize_disp(pred_disp, gt_depths, *, post_process=False):
     pred = _pred_maps(pred_disp, len(packed), post_process)
     _, h, w = pred.shape
     out = torch.empty_like(packed.data)
-    with C.on_device(pred.device):
-        C.check(C.load().pd_depth_eval_resize(len(packed), h, w, C.PD_EVAL_POST_PROCESS if post_process else 0, packed.max_hw,
-                                              C.ptr(pred), C.ptr(packed.meta), C.ptr(out), C.stream_handle(pred.device)),
-                "pd_depth_eval_resize")
+    C.call("pd_depth_eval_resize", pred.device, len(packed), h, w, C.PD_EVAL_POST_PROCESS if post_process else 0, packed.max_hw,
+           pred, packed.meta, out)
     return [out[o:o + hh * ww].view(hh, ww) for o, (hh, ww) in zip(packed.offsets, packed.shapes)]
 
 

@@ -66,7 +66,6 @@ def resize_crop_augment(src, src_hw, crop, flags, aug, height, width):
     (full_w, full_h, w0, h0) as ``ops.crop_grid`` takes it; ``flags`` ``[B]`` int32 (gamma 1, brightness 2, channel 4, flip 8);
     ``aug`` ``[B,V,5]`` float32 (gamma, brightness, c0, c1, c2).  Parameter tensors on the CPU are range-checked (``ValueError``
     before any launch) and uploaded; on the GPU they are trusted.  -> ``(color, color_aug)``, each ``[B,V,3,height,width]``."""
-    lib = C.load()
     if not torch.is_tensor(src):
         raise TypeError("src must be a tensor")
     if src.dtype == torch.uint8:
@@ -93,10 +92,8 @@ def resize_crop_augment(src, src_hw, crop, flags, aug, height, width):
         src_hw, crop, flags, aug = _on(dev, src_hw), _on(dev, crop), _on(dev, flags), _on(dev, aug)
         color = torch.empty(B, V, 3, height, width, device=dev, dtype=torch.float32)
         color_aug = torch.empty_like(color)
-        with C.on_device(dev):
-            C.check(lib.pd_resize_crop_augment(B, V, h_max, w_max, height, width, fmt, C.ptr(src), C.ptr(src_hw), C.ptr(crop),
-                                               C.ptr(flags), C.ptr(aug), C.ptr(color), C.ptr(color_aug), C.stream_handle(dev)),
-                    "pd_resize_crop_augment")
+        C.call("pd_resize_crop_augment", dev, B, V, h_max, w_max, height, width, fmt, src, src_hw, crop, flags, aug, color,
+               color_aug)
     return color, color_aug
 
 
@@ -104,7 +101,6 @@ def resize_crop_depth(depth, src_hw, crop, flags, height, width):
     """The ``depth_gt`` branch of the same transforms (``pd_resize_crop_nearest``): float32 ``[B,1,Hd,Wd]`` with its own ``src_hw``
     -> ``[B,1,height,width]``, torch's legacy ``nearest`` resize to the crop's full size, the same window, the same flip bit.  A
     selection of source elements: bit-exact."""
-    lib = C.load()
     if not torch.is_tensor(depth):
         raise TypeError("depth must be a tensor")
     if depth.dim() != 4 or depth.shape[1] != 1:
@@ -121,9 +117,7 @@ def resize_crop_depth(depth, src_hw, crop, flags, height, width):
         depth = depth.contiguous()
         src_hw, crop, flags = _on(dev, src_hw), _on(dev, crop), _on(dev, flags)
         out = torch.empty(B, 1, height, width, device=dev, dtype=torch.float32)
-        with C.on_device(dev):
-            C.check(lib.pd_resize_crop_nearest(B, h_d, w_d, height, width, C.ptr(depth), C.ptr(src_hw), C.ptr(crop), C.ptr(flags),
-                                               C.ptr(out), C.stream_handle(dev)), "pd_resize_crop_nearest")
+        C.call("pd_resize_crop_nearest", dev, B, h_d, w_d, height, width, depth, src_hw, crop, flags, out)
     return out
 
 

@@ -73,7 +73,6 @@ class _PoseTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, grid, invert, frame, scale):
-        lib = C.load()
         dev = x.device
         in_dtype = x.dtype
         x = x.detach()
@@ -90,9 +89,8 @@ class _PoseTail(torch.autograd.Function):
         Rt_Rc = torch.empty(B, 4, 4, device=dev)
         dtype = C.PD_DTYPE_BF16 if x.dtype == torch.bfloat16 else C.PD_DTYPE_F32
         gH, gW, gs = _grid_args(grid)
-        with C.on_device(dev):
-            C.check(lib.pd_pose_tail_fwd(B, Cn, hw, frame, dtype, int(invert), scale, C.ptr(x), sb, sc, ss, None, C.ptr(grid), gH, gW,
-                                         gs, C.ptr(aa), C.ptr(tr), C.ptr(Rc), C.ptr(Rt_Rc), C.stream_handle(dev)), "pd_pose_tail_fwd")
+        C.call("pd_pose_tail_fwd", dev, B, Cn, hw, frame, dtype, int(invert), scale, x, sb, sc, ss, None, grid, gH, gW, gs, aa,
+               tr, Rc, Rt_Rc)
         ctx.save_for_backward(x, grid)
         ctx.args = (invert, frame, scale, dtype, in_dtype)
         ctx.set_materialize_grads(False)   # (an output nobody used stays None: a NULL pointer, not a zero-fill launch)
@@ -103,7 +101,6 @@ class _PoseTail(torch.autograd.Function):
     def backward(ctx, g_aa, g_tr, _g_Rc, g_Rt_Rc):
         if (g_aa is None and g_tr is None and g_Rt_Rc is None) or not ctx.needs_input_grad[0]:
             return None, None, None, None, None
-        lib = C.load()
         x, grid = ctx.saved_tensors
         invert, frame, scale, dtype, in_dtype = ctx.args
         dev = x.device
@@ -115,10 +112,8 @@ class _PoseTail(torch.autograd.Function):
             g_x = torch.empty(x.shape, device=dev, dtype=x.dtype)
         _, _, gsb, gsc, gss = _layout(g_x)
         gH, gW, gs = _grid_args(grid)
-        with C.on_device(dev):
-            C.check(lib.pd_pose_tail_bwd(B, Cn, hw, frame, dtype, int(invert), scale, C.ptr(x), sb, sc, ss, C.ptr(grid), gH, gW, gs,
-                                         C.ptr(g_Rt_Rc), C.ptr(g_aa), C.ptr(g_tr), C.ptr(g_x), gsb, gsc, gss,
-                                         C.stream_handle(dev)), "pd_pose_tail_bwd")
+        C.call("pd_pose_tail_bwd", dev, B, Cn, hw, frame, dtype, int(invert), scale, x, sb, sc, ss, grid, gH, gW, gs, g_Rt_Rc,
+               g_aa, g_tr, g_x, gsb, gsc, gss)
         return (g_x if g_x.dtype == in_dtype else g_x.to(in_dtype)), None, None, None, None
 
 
@@ -180,14 +175,12 @@ def pose_conjugate(Rt, grid):
     _check_grid(grid, B)
     _require_gpu_float("Rt", Rt)
     grid = _gpu_grid(grid)
-    lib = C.load()
     dev = Rt.device
     with torch.no_grad():
         Rt = Rt.float().contiguous()
         Rc = torch.empty(B, 3, 3, device=dev)
         Rt_Rc = torch.empty(B, 4, 4, device=dev)
         gH, gW, gs = _grid_args(grid)
-        with C.on_device(dev):
-            C.check(lib.pd_pose_tail_fwd(B, 0, 0, 0, C.PD_DTYPE_F32, 0, 1.0, None, 0, 0, 0, C.ptr(Rt), C.ptr(grid), gH, gW, gs, None,
-                                         None, C.ptr(Rc), C.ptr(Rt_Rc), C.stream_handle(dev)), "pd_pose_tail_fwd")
+        C.call("pd_pose_tail_fwd", dev, B, 0, 0, 0, C.PD_DTYPE_F32, 0, 1.0, None, 0, 0, 0, Rt, grid, gH, gW, gs, None, None, Rc,
+               Rt_Rc)
     return Rt_Rc, Rc

@@ -46,40 +46,33 @@ def post_process_route(B, N, H, W, flags=0, workspace_ptr=0, disp_pp_ptr=0):
 
 def warp_softmax(planes, disp_layered, sign, flip_src=False, row_uniform=False):
     """softmax over the planes of ``planes`` sampled at x + sign * disp (trainer.py:443-446 / 451-453)."""
-    lib = C.load()
     C.require_gpu_tensor("planes", planes)
     B, N, H, W = planes.shape
     with torch.no_grad():
         planes = planes.detach().contiguous()
         disp, flags = _pp_disp(disp_layered.detach(), B, N, H, W, row_uniform)
         out = torch.empty_like(planes)
-        with C.on_device(planes.device):
-            C.check(lib.pd_warp_softmax(B, N, H, W, float(sign), flags | (C.PD_PP_FLIP_SRC if flip_src else 0),
-                                        C.ptr(planes), C.ptr(disp), C.ptr(out), C.stream_handle(planes.device)),
-                    "pd_warp_softmax")
+        C.call("pd_warp_softmax", planes.device, B, N, H, W, float(sign), flags | (C.PD_PP_FLIP_SRC if flip_src else 0), planes,
+               disp, out)
     return out
 
 
 def warp_sum(planes, disp_layered, sign, cap=1.0, flip_src=False, row_uniform=False):
     """min(cap, sum over the planes of ``planes`` sampled at x + sign * disp) (trainer.py:447-449, 454-456, 463-465)."""
-    lib = C.load()
     C.require_gpu_tensor("planes", planes)
     B, N, H, W = planes.shape
     with torch.no_grad():
         planes = planes.detach().contiguous()
         disp, flags = _pp_disp(disp_layered.detach(), B, N, H, W, row_uniform)
         out = torch.empty(B, 1, H, W, device=planes.device, dtype=torch.float32)
-        with C.on_device(planes.device):
-            C.check(lib.pd_warp_sum(B, N, H, W, float(sign), flags | (C.PD_PP_FLIP_SRC if flip_src else 0),
-                                    C.ptr(planes), C.ptr(disp), float(cap), C.ptr(out),
-                                    C.stream_handle(planes.device)), "pd_warp_sum")
+        C.call("pd_warp_sum", planes.device, B, N, H, W, float(sign), flags | (C.PD_PP_FLIP_SRC if flip_src else 0), planes,
+               disp, float(cap), out)
     return out
 
 
 def pp_combine(disp, o_fr, o_l):
     """disp_pp of trainer.py:458-461 in one launch: ``disp`` [2B,1,H,W] (image, mirrored image), the occlusion masks
     ``o_fr`` / ``o_l`` [B,1,H,W] -> mean-of-both where o_fr says so, the mirrored pass's disparity where o_l is 0."""
-    lib = C.load()
     C.require_gpu_tensor("disp", disp)
     B2, _, H, W = disp.shape
     B = B2 // 2
@@ -88,9 +81,7 @@ def pp_combine(disp, o_fr, o_l):
     with torch.no_grad():
         disp, o_fr, o_l = (_contig(t.detach()) for t in (disp, o_fr, o_l))
         out = torch.empty(B, 1, H, W, device=disp.device, dtype=torch.float32)
-        with C.on_device(disp.device):
-            C.check(lib.pd_pp_combine(B, H, W, C.ptr(disp), C.ptr(o_fr), C.ptr(o_l), C.ptr(out), C.stream_handle(disp.device)),
-                    "pd_pp_combine")
+        C.call("pd_pp_combine", disp.device, B, H, W, disp, o_fr, o_l, out)
     return out
 
 
@@ -117,9 +108,7 @@ def post_process_disp(logits, probability, disp, disp_layered, row_uniform=False
         ws = torch.empty(lib.pd_post_process_workspace_floats(B, N, H, W), device=dev, dtype=torch.float32)
         disp_pp = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
         mask_novel = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
-        with C.on_device(dev):
-            C.check(lib.pd_post_process(B, N, H, W, flags, C.ptr(logits), C.ptr(prob), C.ptr(disp), C.ptr(dl), C.ptr(ws),
-                                        C.ptr(disp_pp), C.ptr(mask_novel), C.stream_handle(dev)), "pd_post_process")
+        C.call("pd_post_process", dev, B, N, H, W, flags, logits, prob, disp, dl, ws, disp_pp, mask_novel)
     return disp_pp, mask_novel
 
 
@@ -144,16 +133,13 @@ def post_process_disp_stepwise(logits, probability, disp, disp_layered, row_unif
 # ---------------------------------------------------------------------------------------------------------------------
 def cat_flip(own, other, negate_c0=False):
     """cat([own, other.flip(-1)], dim=0) in one kernel (trainer.py:253-262); ``negate_c0`` for the grid tensor."""
-    lib = C.load()
     C.require_gpu_tensor("own", own)
     C.require_gpu_tensor("other", other, tuple(own.shape))
     B, Cn, H, W = own.shape
     with torch.no_grad():
         own, other = own.contiguous(), other.contiguous()
         out = torch.empty(2 * B, Cn, H, W, device=own.device, dtype=torch.float32)
-        with C.on_device(own.device):
-            C.check(lib.pd_cat_flip(B, Cn, H, W, C.ptr(own), C.ptr(other), int(bool(negate_c0)), C.ptr(out),
-                                    C.stream_handle(own.device)), "pd_cat_flip")
+        C.call("pd_cat_flip", own.device, B, Cn, H, W, own, other, int(bool(negate_c0)), out)
     return out
 
 
@@ -162,14 +148,11 @@ def crop_grid(params, height, width):
     (datasets/pair_transforms.py:27-37: the RandomResizeCrop grid; Resize is full = (W, H), origin 0) — the reference's
     ``torch.linspace`` / ``meshgrid`` / crop to one ulp (torch's vectorised linspace itself differs in the last bit between
     host CPUs: tests/test_gpu_parity.py::test_on_device_grid_matches_the_reference_pipeline_to_one_ulp)."""
-    lib = C.load()
     C.require_gpu_tensor("params", params, dtype=torch.int32)
     if params.dim() != 2 or params.shape[1] != 4:
         raise ValueError("params must be [B,4] int32 (full_w, full_h, w0, h0), got %s" % (tuple(params.shape),))
     B = params.shape[0]
     params = params.contiguous()
     grid = torch.empty(B, 2, int(height), int(width), device=params.device, dtype=torch.float32)
-    with C.on_device(params.device):
-        C.check(lib.pd_crop_grid(B, int(height), int(width), C.ptr(params), C.ptr(grid), C.stream_handle(params.device)),
-                "pd_crop_grid")
+    C.call("pd_crop_grid", params.device, B, int(height), int(width), params, grid)
     return grid

@@ -121,11 +121,9 @@ def _sweep_forward(*call):
     lib = C.load()
     d, _, s, ph_map, ph_mean = _forward_view(lib, SweepCall(*call))
     dev = s.logits.device
-    with C.on_device(dev), _timed("fwd"):
-        rc = lib.pd_plane_sweep_fwd(ctypes.byref(d), C.ptr(s.src), C.ptr(s.tgt), C.ptr(s.logits), C.ptr(s.sigma),
-                                    C.ptr(s.plane), C.ptr(s.plane_aux), C.ptr(s.inv_K3), C.ptr(s.padding_mask), C.ptr(s.dists),
-                                    C.ptr(s.rgb_rec), C.ptr(ph_map), C.ptr(ph_mean), C.ptr(s.stash), C.stream_handle(dev))
-    C.check(rc, "pd_plane_sweep_fwd")
+    with _timed("fwd", dev):
+        C.call("pd_plane_sweep_fwd", dev, ctypes.byref(d), s.src, s.tgt, s.logits, s.sigma, s.plane, s.plane_aux, s.inv_K3,
+               s.padding_mask, s.dists, s.rgb_rec, ph_map, ph_mean, s.stash)
     return (s.rgb_rec, ph_map, ph_mean), s
 
 
@@ -140,10 +138,9 @@ def _sweep_forward_pair(call_a, call_b):
                           ph_map=ph_map, ph_mean=ph_mean, stash=s.stash)
              for s, ph_map, ph_mean in ((sa, ph_map_a, ph_mean_a), (sb, ph_map_b, ph_mean_b))]
     dev = sa.logits.device
-    with C.on_device(dev), _timed("fwd"):
-        rc = lib.pd_uniform_fwd_pair(ctypes.byref(d), C.ptr(sa.src), C.ptr(sa.logits), C.ptr(sa.sigma), ctypes.byref(views[0]),
-                                     ctypes.byref(views[1]), C.stream_handle(dev))
-    C.check(rc, "pd_uniform_fwd_pair")
+    with _timed("fwd", dev):
+        C.call("pd_uniform_fwd_pair", dev, ctypes.byref(d), sa.src, sa.logits, sa.sigma, ctypes.byref(views[0]),
+               ctypes.byref(views[1]))
     return ((sa.rgb_rec, ph_map_a, ph_mean_a), sa), ((sb.rgb_rec, ph_map_b, ph_mean_b), sb)
 
 
@@ -174,11 +171,9 @@ def _sweep_backward_pair(view_a, view_b, cfg, need_a, need_b, g_logits, g_sigma,
         keep.append((g_rgb_rec, g_ph_map, g_ph_mean, ws))   # alive until the call is enqueued
         if S.DEBUG_WORKSPACE is not None:
             S.DEBUG_WORKSPACE.append((d, ws))
-    with C.on_device(dev), _timed("bwd"):
-        rc = lib.pd_uniform_bwd_pair(ctypes.byref(d), C.ptr(first.src), C.ptr(first.logits), C.ptr(first.sigma),
-                                     ctypes.byref(views[0]), ctypes.byref(views[1]), C.ptr(g_logits),
-                                     C.ptr(g_sigma if mix else None), C.stream_handle(dev))
-    C.check(rc, "pd_uniform_bwd_pair")
+    with _timed("bwd", dev):
+        C.call("pd_uniform_bwd_pair", dev, ctypes.byref(d), first.src, first.logits, first.sigma, ctypes.byref(views[0]),
+               ctypes.byref(views[1]), g_logits, g_sigma if mix else None)
     del keep
     return outs
 
@@ -210,13 +205,10 @@ def _sweep_backward(saved, cfg, grads, need, into=None, accumulate=False):
     g_dists = torch.empty_like(s.dists) if (s.dists is not None and need_dists) else None
     ws = _workspace(lib, d, dev)
     g_rgb_rec, g_ph_map, g_ph_mean = _contig(g_rgb_rec), _contig(g_ph_map), _scalar_grad(g_ph_mean)
-    with C.on_device(dev), _timed("bwd"):
-        rc = lib.pd_plane_sweep_bwd(ctypes.byref(d), C.ptr(s.src), C.ptr(s.tgt), C.ptr(s.logits), C.ptr(s.sigma),
-                                    C.ptr(s.plane), C.ptr(s.plane_aux), C.ptr(s.inv_K3), C.ptr(s.padding_mask), C.ptr(s.dists),
-                                    C.ptr(s.rgb_rec), C.ptr(s.stash), C.ptr(g_rgb_rec), C.ptr(g_ph_map), C.ptr(g_ph_mean),
-                                    C.ptr(g_logits), C.ptr(g_sigma if mix else None), C.ptr(g_plane), C.ptr(g_dists),
-                                    C.ptr(ws), C.stream_handle(dev))
-    C.check(rc, "pd_plane_sweep_bwd")
+    with _timed("bwd", dev):
+        C.call("pd_plane_sweep_bwd", dev, ctypes.byref(d), s.src, s.tgt, s.logits, s.sigma, s.plane, s.plane_aux, s.inv_K3,
+               s.padding_mask, s.dists, s.rgb_rec, s.stash, g_rgb_rec, g_ph_map, g_ph_mean, g_logits,
+               g_sigma if mix else None, g_plane, g_dists, ws)
     if S.DEBUG_WORKSPACE is not None:
         S.DEBUG_WORKSPACE.append((d, ws))
     return g_logits, (g_sigma if mix else None), g_plane, g_dists
@@ -242,18 +234,14 @@ def _sweep_backward_tail(saved, cfg, grads, need, link):
     ws = _workspace(lib, d, dev)
     g_rgb_rec, g_ph_map, gd, gz = map(_contig, (g_rgb_rec, g_ph_map, g_disp, g_depth))
     g_ph_mean = _scalar_grad(g_ph_mean)
-    tail_args = (C.ptr(s.rgb_rec), C.ptr(s.stash), C.ptr(g_rgb_rec), C.ptr(g_ph_map), C.ptr(g_ph_mean), C.ptr(link.raw_sigma),
-                 C.ptr(link.stash), C.ptr(link.disp), C.ptr(gd), C.ptr(gz), C.ptr(gl), C.ptr(gs), C.ptr(g_plane), C.ptr(ws),
-                 C.stream_handle(dev))
-    head = (ctypes.byref(d), C.ptr(s.src), C.ptr(s.tgt), C.ptr(s.logits), C.ptr(s.sigma), C.ptr(s.plane))
-    with C.on_device(dev), _timed("bwd"):
+    tail_args = (s.rgb_rec, s.stash, g_rgb_rec, g_ph_map, g_ph_mean, link.raw_sigma, link.stash, link.disp, gd, gz, gl, gs,
+                 g_plane, ws)
+    head = (ctypes.byref(d), s.src, s.tgt, s.logits, s.sigma, s.plane)
+    with _timed("bwd", dev):
         if flags & (C.PD_DISP_ROWS | C.PD_MASK_ROWS):   # (plane_sweep_disp checked: the sweep's row mask IS the tail's)
-            name = "pd_plane_sweep_bwd_tail_rows"
-            rc = lib.pd_plane_sweep_bwd_tail_rows(*head, C.ptr(s.padding_mask), *tail_args)
+            C.call("pd_plane_sweep_bwd_tail_rows", dev, *head, s.padding_mask, *tail_args)
         else:
-            name = "pd_plane_sweep_bwd_tail"
-            rc = lib.pd_plane_sweep_bwd_tail(*head, *tail_args)
-    C.check(rc, name)
+            C.call("pd_plane_sweep_bwd_tail", dev, *head, *tail_args)
     link.applied = {"disp": g_disp, "depth": g_depth}   # until the tail's node of this pass has consumed it
     link.fused_passes += 1
     return gl, gs, g_plane
@@ -684,7 +672,6 @@ class _HomographyMatrices(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, distance, norm, T, K, inv_K, mode, rows):
-        lib = C.load()
         B, N = distance.shape
         dev = distance.device
         distance, norm, T, K, inv_K = (_contig(t.detach().float()) for t in (distance, norm, T, K, inv_K))
@@ -697,10 +684,7 @@ class _HomographyMatrices(torch.autograd.Function):
             shift, mask = torch.empty(B, N, rows, device=dev), torch.empty(B, N, rows, device=dev)
         else:
             Hm = torch.empty(B, 4 if mode == C.PD_HMAT_UNIFORM else N, 3, 3, device=dev)
-        with C.on_device(dev):
-            C.check(lib.pd_homography_matrices_fwd(B, N, mode, rows, C.ptr(distance), C.ptr(norm), C.ptr(T), C.ptr(K),
-                                                   C.ptr(inv_K), C.ptr(Hm), C.ptr(Rn), C.ptr(shift), C.ptr(mask),
-                                                   C.stream_handle(dev)), "pd_homography_matrices_fwd")
+        C.call("pd_homography_matrices_fwd", dev, B, N, mode, rows, distance, norm, T, K, inv_K, Hm, Rn, shift, mask)
         ctx.save_for_backward(distance, norm, T, K, inv_K)
         ctx.mode, ctx.rows = mode, rows
         ctx.set_materialize_grads(False)   # (else autograd zero-fills gradients for the non-differentiable Rn / mask: two launches)
@@ -712,7 +696,6 @@ class _HomographyMatrices(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_first, *_):
-        lib = C.load()
         distance, norm, T, K, inv_K = ctx.saved_tensors
         B, N = distance.shape
         dev = distance.device
@@ -727,11 +710,8 @@ class _HomographyMatrices(torch.autograd.Function):
         gd = torch.empty(B, N, device=dev) if need_d else None
         gn = torch.empty(B, N, 3, device=dev) if need_n else None
         gT = torch.empty(B, 4, 4, device=dev) if need_T else None
-        with C.on_device(dev):
-            C.check(lib.pd_homography_matrices_bwd(B, N, ctx.mode, ctx.rows, C.ptr(distance), C.ptr(norm), C.ptr(T),
-                                                   C.ptr(K), C.ptr(inv_K), C.ptr(None if stereo else g_first),
-                                                   C.ptr(g_first if stereo else None), C.ptr(gd), C.ptr(gn), C.ptr(gT),
-                                                   C.stream_handle(dev)), "pd_homography_matrices_bwd")
+        C.call("pd_homography_matrices_bwd", dev, B, N, ctx.mode, ctx.rows, distance, norm, T, K, inv_K,
+               None if stereo else g_first, g_first if stereo else None, gd, gn, gT)
         return gd, gn, gT, None, None, None, None
 
 
@@ -825,7 +805,6 @@ def plane_sweep_layers(src, logits, sigma, *, disp_layered=None, padding_mask=No
                        homography=None, use_mixture_loss=True, render_probability=False, dists=None,
                        want=("rgb_rec_layered", "logit_rec", "probability_rec", "sigma_rec", "pi_rec")):
     """Materialise the per-plane tensors the reference keeps in ``outputs`` (trainer.py:582-602).  No gradients."""
-    lib = C.load()
     B, N, H, W = logits.shape
     with torch.no_grad():
         logits, sigma, _ = _storage_route(logits, sigma, use_mixture_loss, None)   # (the layers kernel reads fp32 only)
@@ -849,13 +828,8 @@ def plane_sweep_layers(src, logits, sigma, *, disp_layered=None, padding_mask=No
                 continue
             out[k] = torch.empty(shapes[k], device=dev, dtype=torch.float32)
         d = _desc(B, N, H, W, mode, flags, sign)
-        with C.on_device(dev):
-            rc = lib.pd_plane_sweep_layers(ctypes.byref(d), C.ptr(src.contiguous()), C.ptr(logits.contiguous()),
-                                           C.ptr(_contig(sigma) if use_mixture_loss else None), C.ptr(plane),
-                                           C.ptr(aux), C.ptr(k3), C.ptr(padding_mask),
-                                           C.ptr(dists.contiguous() if render_probability else None),
-                                           C.ptr(out.get("rgb_rec_layered")), C.ptr(out.get("logit_rec")),
-                                           C.ptr(out.get("probability_rec")), C.ptr(out.get("sigma_rec")),
-                                           C.ptr(out.get("pi_rec")), C.stream_handle(dev))
-        C.check(rc, "pd_plane_sweep_layers")
+        C.call("pd_plane_sweep_layers", dev, ctypes.byref(d), src.contiguous(), logits.contiguous(),
+               _contig(sigma) if use_mixture_loss else None, plane, aux, k3, padding_mask,
+               dists.contiguous() if render_probability else None, out.get("rgb_rec_layered"), out.get("logit_rec"),
+               out.get("probability_rec"), out.get("sigma_rec"), out.get("pi_rec"))
     return out

@@ -82,14 +82,11 @@ def _layers_of(entry, N, flags, operands, stash):
     dev = operands[0].device
 
     def layers(want_pi=True, want_probability=True):
-        lib = C.load()
         with torch.no_grad():
             pi = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_pi else None
             prob = torch.empty(B, N, H, W, device=dev, dtype=torch.float32) if want_probability else None
             ins = [None if t is None else _contig(t.detach()) for t in operands]
-            with C.on_device(dev):
-                C.check(getattr(lib, entry)(B, N, H, W, flags, *map(C.ptr, ins), C.ptr(stash), C.ptr(pi), C.ptr(prob),
-                                            C.stream_handle(dev)), entry)
+            C.call(entry, dev, B, N, H, W, flags, *ins, stash, pi, prob)
         return pi, prob
 
     layers.stash = stash
@@ -130,7 +127,6 @@ class _DecoderTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw_logits, raw_sigma, disp_layered, padding_mask, flags, link=None):
-        lib = C.load()
         B, N, H, W = raw_logits.shape
         mix = bool(flags & C.PD_TAIL_MIXTURE)
         ctx.link = link
@@ -142,10 +138,9 @@ class _DecoderTail(torch.autograd.Function):
         logits = new(B, N, H, W, dtype=st) if padding_mask is not None else None
         sigma = new(B, N, H, W, dtype=st) if mix else None
         disp, depth, stash = new(B, 1, H, W), new(B, 1, H, W), new(B, 2, H, W)
-        with C.on_device(dev), _timed("tail_fwd"):
-            C.check(lib.pd_decoder_tail_fwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(padding_mask),
-                                            C.ptr(disp_layered), C.ptr(logits), C.ptr(sigma), C.ptr(disp), C.ptr(depth),
-                                            C.ptr(stash), C.stream_handle(dev)), "pd_decoder_tail_fwd")
+        with _timed("tail_fwd", dev):
+            C.call("pd_decoder_tail_fwd", dev, B, N, H, W, flags, raw_logits, raw_sigma, padding_mask, disp_layered, logits,
+                   sigma, disp, depth, stash)
         ctx.save_for_backward(raw_logits, raw_sigma, disp_layered, padding_mask, stash, disp)
         ctx.flags = flags
         ctx.mark_non_differentiable(stash)
@@ -198,12 +193,9 @@ class _DecoderTail(torch.autograd.Function):
         g_raw_logits, g_raw_sigma, g_dl, ws = _grad_buffers(lib, needs, raw_logits, raw_sigma, disp_layered, N,
                                                             flags & (C.PD_TAIL_DISP_DENSE | C.PD_TAIL_DISP_ROWS))
         g_logits, g_sigma, g_disp, g_depth = _upstream(mix, raw_logits.dtype, g_logits, g_sigma, g_disp, g_depth)
-        with C.on_device(raw_logits.device), _timed("tail_bwd"):
-            C.check(lib.pd_decoder_tail_bwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(padding_mask),
-                                            C.ptr(disp_layered), C.ptr(stash), C.ptr(disp), C.ptr(g_logits),
-                                            C.ptr(g_sigma), C.ptr(g_disp), C.ptr(g_depth), C.ptr(g_raw_logits),
-                                            C.ptr(g_raw_sigma), C.ptr(g_dl), C.ptr(ws),
-                                            C.stream_handle(raw_logits.device)), "pd_decoder_tail_bwd")
+        with _timed("tail_bwd", raw_logits.device):
+            C.call("pd_decoder_tail_bwd", raw_logits.device, B, N, H, W, flags, raw_logits, raw_sigma, padding_mask,
+                   disp_layered, stash, disp, g_logits, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_dl, ws)
         if extra is not None:
             if g_raw_logits is not None and extra[0] is not None:
                 g_raw_logits += extra[0]
@@ -263,7 +255,6 @@ class _PladeTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw_logits, raw_sigma, disp_layered, ray_norm, flags):
-        lib = C.load()
         B, Nm1, H, W = raw_logits.shape
         N = Nm1 + 1
         mix = bool(flags & C.PD_TAIL_MIXTURE)
@@ -274,10 +265,9 @@ class _PladeTail(torch.autograd.Function):
         logits, dists = new(B, N, H, W, dtype=st), new(B, N - 1, H, W)
         sigma = new(B, N, H, W, dtype=st) if mix else None
         disp, depth, stash = new(B, 1, H, W), new(B, 1, H, W), new(B, 1, H, W)
-        with C.on_device(dev), _timed("plade_fwd"):
-            C.check(lib.pd_plade_tail_fwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(disp_layered),
-                                          C.ptr(ray_norm), C.ptr(logits), C.ptr(dists), C.ptr(sigma), C.ptr(disp), C.ptr(depth),
-                                          C.ptr(stash), C.stream_handle(dev)), "pd_plade_tail_fwd")
+        with _timed("plade_fwd", dev):
+            C.call("pd_plade_tail_fwd", dev, B, N, H, W, flags, raw_logits, raw_sigma, disp_layered, ray_norm, logits, dists,
+                   sigma, disp, depth, stash)
         ctx.save_for_backward(raw_logits, raw_sigma, disp_layered, ray_norm, stash, disp)
         ctx.flags = flags
         ctx.mark_non_differentiable(stash)
@@ -300,11 +290,8 @@ class _PladeTail(torch.autograd.Function):
                                                             flags & C.PD_TAIL_DISP_DENSE)
         g_logits, g_sigma, g_dists, g_disp, g_depth = _upstream(bool(flags & C.PD_TAIL_MIXTURE), raw_logits.dtype, g_logits,
                                                                 g_sigma, g_dists, g_disp, g_depth)
-        with C.on_device(raw_logits.device):
-            C.check(lib.pd_plade_tail_bwd(B, N, H, W, flags, C.ptr(raw_logits), C.ptr(raw_sigma), C.ptr(disp_layered),
-                                          C.ptr(ray_norm), C.ptr(stash), C.ptr(disp), C.ptr(g_logits), C.ptr(g_dists),
-                                          C.ptr(g_sigma), C.ptr(g_disp), C.ptr(g_depth), C.ptr(g_raw_logits), C.ptr(g_raw_sigma),
-                                          C.ptr(g_dl), C.ptr(ws), C.stream_handle(raw_logits.device)), "pd_plade_tail_bwd")
+        C.call("pd_plade_tail_bwd", raw_logits.device, B, N, H, W, flags, raw_logits, raw_sigma, disp_layered, ray_norm, stash,
+               disp, g_logits, g_dists, g_sigma, g_disp, g_depth, g_raw_logits, g_raw_sigma, g_dl, ws)
         return g_raw_logits, g_raw_sigma, g_dl, None, None
 
 
@@ -406,11 +393,8 @@ def decoder_tail_inference(raw_logits, raw_sigma, padding_mask, disp_layered, us
                                   "padding_mask", padding_mask)
         dev = rl.device
         disp, depth, conf, index, best, stash = _infer_outputs(B, H, W, dev, want, 2)
-        lib = C.load()
-        with C.on_device(dev), _timed("tail_infer"):
-            C.check(lib.pd_decoder_tail_infer(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(pm), C.ptr(dl), C.ptr(disp),
-                                              C.ptr(depth), C.ptr(conf), C.ptr(index), C.ptr(best), C.ptr(stash),
-                                              C.stream_handle(dev)), "pd_decoder_tail_infer")
+        with _timed("tail_infer", dev):
+            C.call("pd_decoder_tail_infer", dev, B, N, H, W, flags, rl, rs, pm, dl, disp, depth, conf, index, best, stash)
     layers = _layers_of("pd_decoder_tail_layers", N, flags, (rl, rs, pm), stash) if stash is not None else None
     return InferenceTail(disp, depth, conf, index, best, layers)
 
@@ -434,11 +418,8 @@ def plade_tail_inference(raw_logits, raw_sigma, disp_layered, ray_norm=None, use
                                    "ray_norm", ray_norm.detach())
         dev = rl.device
         disp, depth, conf, index, best, stash = _infer_outputs(B, H, W, dev, want, 1)
-        lib = C.load()
-        with C.on_device(dev), _timed("plade_infer"):
-            C.check(lib.pd_plade_tail_infer(B, N, H, W, flags, C.ptr(rl), C.ptr(rs), C.ptr(dl), C.ptr(ray), C.ptr(disp),
-                                            C.ptr(depth), C.ptr(conf), C.ptr(index), C.ptr(best), C.ptr(stash),
-                                            C.stream_handle(dev)), "pd_plade_tail_infer")
+        with _timed("plade_infer", dev):
+            C.call("pd_plade_tail_infer", dev, B, N, H, W, flags, rl, rs, dl, ray, disp, depth, conf, index, best, stash)
     layers = _layers_of("pd_plade_tail_layers", N, flags, (rl, rs, dl, ray), stash) if stash is not None else None
     return InferenceTail(disp, depth, conf, index, best, layers)
 
@@ -451,27 +432,21 @@ class _PlaneLevels(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, levels, no_levels, disp_min, disp_max, dist_num):
-        lib = C.load()
         C.require_gpu_tensor("levels", levels)
         levels = _contig(levels)
         disp, distance = torch.empty_like(levels), torch.empty_like(levels)
-        with C.on_device(levels.device):
-            C.check(lib.pd_plane_levels_fwd(levels.numel(), int(no_levels), float(disp_min), float(disp_max), float(dist_num),
-                                            C.ptr(levels), C.ptr(disp), C.ptr(distance), C.stream_handle(levels.device)),
-                    "pd_plane_levels_fwd")
+        C.call("pd_plane_levels_fwd", levels.device, levels.numel(), int(no_levels), float(disp_min), float(disp_max),
+               float(dist_num), levels, disp, distance)
         ctx.save_for_backward(disp)
         ctx.cfg = (int(no_levels), float(disp_min), float(disp_max), float(dist_num))
         return disp, distance
 
     @staticmethod
     def backward(ctx, g_disp, g_distance):
-        lib = C.load()
         disp, = ctx.saved_tensors
         g = torch.empty_like(disp)
         g_disp, g_distance = _contig(g_disp), _contig(g_distance)
-        with C.on_device(disp.device):
-            C.check(lib.pd_plane_levels_bwd(disp.numel(), *ctx.cfg, C.ptr(disp), C.ptr(g_disp), C.ptr(g_distance), C.ptr(g),
-                                            C.stream_handle(disp.device)), "pd_plane_levels_bwd")
+        C.call("pd_plane_levels_bwd", disp.device, disp.numel(), *ctx.cfg, disp, g_disp, g_distance, g)
         return g, None, None, None, None
 
 
@@ -494,7 +469,6 @@ class _PlaneGeometry(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, grid, residual, cfg):
-        lib = C.load()
         no_levels, xz_levels = cfg[0], cfg[1]
         B, _, H, W = grid.shape
         N = no_levels + xz_levels
@@ -502,10 +476,9 @@ class _PlaneGeometry(torch.autograd.Function):
         dev = grid.device
         new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
         disp_rows, mask_rows, distance, norm = new(B, N, H), new(B, N, H), new(B, N), new(B, N, 3)
-        with C.on_device(dev), _timed("plane_geometry_fwd"):
-            C.check(lib.pd_plane_geometry_fwd(B, no_levels, xz_levels, H, W, 0, *cfg[2:], C.ptr(residual), C.ptr(grid),
-                                              C.ptr(disp_rows), C.ptr(mask_rows), C.ptr(distance), C.ptr(norm),
-                                              C.stream_handle(dev)), "pd_plane_geometry_fwd")
+        with _timed("plane_geometry_fwd", dev):
+            C.call("pd_plane_geometry_fwd", dev, B, no_levels, xz_levels, H, W, 0, *cfg[2:], residual, grid, disp_rows,
+                   mask_rows, distance, norm)
         ctx.save_for_backward(grid, residual, disp_rows)
         ctx.cfg = cfg
         ctx.mark_non_differentiable(mask_rows, norm)
@@ -514,17 +487,15 @@ class _PlaneGeometry(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rows, _g_mask, g_distance, _g_norm):
-        lib = C.load()
         grid, residual, disp_rows = ctx.saved_tensors
         if residual is None or not ctx.needs_input_grad[1] or (g_rows is None and g_distance is None):
             return None, None, None
         B, _, H, W = grid.shape
         g_rows, g_distance = _contig(g_rows), _contig(g_distance)
         g_residual = torch.empty_like(residual)
-        with C.on_device(grid.device), _timed("plane_geometry_bwd"):
-            C.check(lib.pd_plane_geometry_bwd(B, ctx.cfg[0], ctx.cfg[1], H, W, 0, *ctx.cfg[2:], C.ptr(residual), C.ptr(grid),
-                                              C.ptr(disp_rows), C.ptr(g_rows), C.ptr(g_distance), C.ptr(g_residual),
-                                              C.stream_handle(grid.device)), "pd_plane_geometry_bwd")
+        with _timed("plane_geometry_bwd", grid.device):
+            C.call("pd_plane_geometry_bwd", grid.device, B, ctx.cfg[0], ctx.cfg[1], H, W, 0, *ctx.cfg[2:], residual, grid,
+                   disp_rows, g_rows, g_distance, g_residual)
         return None, g_residual, None
 
 

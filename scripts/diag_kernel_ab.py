@@ -59,11 +59,7 @@ from planedepth_amd.synthetic import survey_fullsize_case  # noqa: E402
 
 
 def load(path):
-    lib = ctypes.CDLL(path)
-    for name, (res, args) in C.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    return lib
+    return C.bind(ctypes.CDLL(path))
 
 
 IRR = 1                                          # small cases: index of the integer-shift plane

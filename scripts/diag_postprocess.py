@@ -27,10 +27,7 @@ def load_libs(specs):
     libs = []
     for spec in specs:
         name, _, path = spec.partition("=")
-        lib = ctypes.CDLL(path or C.LIB_PATH)
-        for fn, (res, args) in C.SIGNATURES.items():
-            getattr(lib, fn).restype, getattr(lib, fn).argtypes = res, args
-        libs.append((name, lib))
+        libs.append((name, C.bind(ctypes.CDLL(path or C.LIB_PATH))))
     return libs
 
 

@@ -36,11 +36,7 @@ BWD_SETS = ("all", "g_disp->g_raw_logits", "->g_disp_layered")
 
 
 def load(path):
-    lib = ctypes.CDLL(path)
-    for name, (res, args) in C.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    return lib
+    return C.bind(ctypes.CDLL(path))
 
 
 def bits(t):

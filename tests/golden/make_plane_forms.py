@@ -13,8 +13,8 @@ How each consumer is captured on the CPU:
   sweep       ``plane_sweep_disp(..., defer=True)`` returns the SweepCall after the capability queries only;
   tail, plade ``tails._DecoderTail`` / ``tails._PladeTail`` are replaced by a stand-in whose ``apply`` notes its arguments, fills the
               link fields the real forward fills and returns tensors of the right shapes;
-  layers      ``plane_sweep_layers`` with ``pd_plane_sweep_layers`` replaced by a stub that notes its arguments (``C.ptr`` hands
-              the tensors through);
+  layers      ``plane_sweep_layers`` with ``C.call`` replaced by a stub that notes the arguments of its one launch,
+              ``pd_plane_sweep_layers``;
   pp          ``ops._pp_disp`` under ``torch.no_grad()`` on the detached map, as the three post-process operators call it.
 
 The grid, at 2x5x6x16: both ``ops.SWEEP_IMPL = PD_IMPL_AUTO`` (the row kernels serve the shape) and ``PD_IMPL_GENERAL`` (they do
@@ -162,21 +162,21 @@ def run_plade(ops, tails, map_kind):
     return dict(flags=seen["flags"], form=form_of(seen["flags"], "tail"), plane=describe(seen["plane"], rows))
 
 
-def run_layers(ops, lib, map_kind, mask_kind):
+def run_layers(ops, C, map_kind, mask_kind):
     disp_layered, rows = make_map(map_kind, ops)
     mask, mask_rows = make_mask(mask_kind, ops)
     seen = {}
 
-    def stub(d, src, logits, sigma, plane, aux, k3, padding_mask, *rest):
+    def stub(name, device, d, src, logits, sigma, plane, aux, k3, padding_mask, *rest):
+        assert name == "pd_plane_sweep_layers", name
         seen.update(flags=int(d._obj.flags), plane=plane, mask=padding_mask)
-        return 0
-    real = lib.pd_plane_sweep_layers
-    lib.pd_plane_sweep_layers = stub
+    real = C.call
+    C.call = stub
     try:
         ops.plane_sweep_layers(torch.rand(B, 3, H, W), torch.rand(B, N, H, W), torch.rand(B, N, H, W), disp_layered=disp_layered,
                                padding_mask=mask, want=("logit_rec",))
     finally:
-        lib.pd_plane_sweep_layers = real
+        C.call = real
     return dict(flags=seen["flags"], form=form_of(seen["flags"], "sweep"), plane=describe(seen["plane"], rows),
                 mask=describe(seen["mask"], mask_rows))
 
@@ -222,8 +222,8 @@ def evaluate():
     for name, want in (("auto", 1), ("general", 0)):   # the table covers the row kernels serving the shape AND not serving it
         got = lib.pd_sweep_uses_rowshift(ctypes.byref(C.SweepDesc(B, N, H, W, C.PD_WARP_DISP, 0, 1.0, impls[name])))
         assert got == want, (name, got)
-    saved = (_state.SWEEP_IMPL, tails._DecoderTail, tails._PladeTail, C.ptr, C.stream_handle)
-    tails._DecoderTail, tails._PladeTail, C.ptr, C.stream_handle = _Recorder, _PladeRecorder, (lambda t: t), (lambda dev=None: None)
+    saved = (_state.SWEEP_IMPL, tails._DecoderTail, tails._PladeTail)
+    tails._DecoderTail, tails._PladeTail = _Recorder, _PladeRecorder
     out = {}
     try:
         for case in grid():
@@ -236,7 +236,7 @@ def evaluate():
                     (dl, rows), (mask, mask_rows) = make_map(m, ops), make_mask(k, ops)
                     r = run_sweep(ops, torch.rand(B, N, H, W), torch.rand(B, N, H, W), dl, rows, mask, mask_rows, ru)
                 elif kind == "layers":
-                    r = run_layers(ops, lib, *rest)
+                    r = run_layers(ops, C, *rest)
                 elif kind == "tail":
                     r = run_tail(ops, tails, *rest)
                 elif kind == "tail+sweep":
@@ -252,7 +252,7 @@ def evaluate():
                 r = dict(raises=type(e).__name__, text=str(e))
             out["/".join(map(str, case))] = r
     finally:
-        _state.SWEEP_IMPL, tails._DecoderTail, tails._PladeTail, C.ptr, C.stream_handle = saved
+        _state.SWEEP_IMPL, tails._DecoderTail, tails._PladeTail = saved
     return out
 
 

@@ -2,10 +2,8 @@
 on pd_sweep_native_bf16, the query names the native set, and every refusal happens in argument validation — nothing
 launches, so none of this needs a GPU."""
 import ctypes
-import os
-import re
 
-from conftest import ROOT
+import capi_header
 from planedepth_amd import _capi as C
 
 NULL_FWD = [None] * 14
@@ -21,10 +19,8 @@ def native(d):
 
 
 def test_header_capi_and_library_agree_on_the_flag_and_query():
-    text = open(os.path.join(ROOT, "include", "planedepth_hip.h")).read()
-    m = re.search(r"\bPD_LOGITS_BF16\s*=\s*(\d+)", text)
-    assert m and int(m.group(1)) == C.PD_LOGITS_BF16 == 2048
-    assert re.search(r"int\s+pd_sweep_native_bf16\s*\(\s*const\s+pd_sweep_desc\s*\*", text)
+    assert capi_header.constant("PD_LOGITS_BF16") == C.PD_LOGITS_BF16 == 2048
+    assert capi_header.prototype("pd_sweep_native_bf16") == ("int", ["const pd_sweep_desc* d"])
     assert C.SIGNATURES["pd_sweep_native_bf16"] == (ctypes.c_int, [ctypes.POINTER(C.SweepDesc)])
     assert hasattr(C.load(), "pd_sweep_native_bf16")
     assert ctypes.sizeof(C.SweepDesc) == 32

@@ -1,20 +1,12 @@
 """CPU-side checks of PD_TAIL_BF16 at the boundary: the Python constant is the header's, and both decoder tails accept the
 flag in their argument validation (which needs no GPU) while unknown bits are still refused."""
-import os
-import re
-
-from conftest import ROOT
+import capi_header
 from planedepth_amd import _capi as C
 
 
-def _tail_flags_enum():
-    text = open(os.path.join(ROOT, "include", "planedepth_hip.h")).read()
-    body = re.search(r"enum\s+pd_tail_flags\s*\{([^}]*)\}", text).group(1)
-    return {k: int(v, 0) for k, v in re.findall(r"(PD_TAIL_[A-Z0-9_]+)\s*=\s*(\w+)", body)}
-
-
 def test_flag_constant_is_the_headers():
-    enum = _tail_flags_enum()
+    enum = capi_header.enum("pd_tail_flags")
+    assert len(enum) == 5 and all(k.startswith("PD_TAIL_") for k in enum)
     assert enum["PD_TAIL_BF16"] == C.PD_TAIL_BF16 == 4
     assert enum["PD_TAIL_MIXTURE"] == C.PD_TAIL_MIXTURE and enum["PD_TAIL_DISP_DENSE"] == C.PD_TAIL_DISP_DENSE
     bits = list(enum.values())

@@ -2,29 +2,28 @@
 without touching a GPU, and the Python operators refuse CPU tensors instead of falling back."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
+import capi_header
 from planedepth_amd import _capi as C
 from planedepth_amd import ops
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "planedepth_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(pd_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_library_exports_every_declared_symbol():
     lib = C.load()
-    names = declared_symbols()
+    names = capi_header.symbols()
     assert len(names) >= 19
     for n in names:
         assert hasattr(lib, n), n
         assert n in C.SIGNATURES, "ctypes prototype missing for " + n
+        ret, _ = capi_header.prototype(n)
+        res, args = C.SIGNATURES[n]
+        assert res is capi_header.RETURNS[ret], n
+        assert capi_header.ctypes_kinds(args) == capi_header.kinds(n), n
+        fn = getattr(lib, n)
+        assert fn.restype is res and list(fn.argtypes) == args, n   # what load() bound is the table
     assert sorted(C.SIGNATURES) == names
     assert lib.pd_version() >= 100
     import planedepth_amd
@@ -32,6 +31,50 @@ def test_library_exports_every_declared_symbol():
     assert lib.pd_version() == major * 1000 + minor * 100 + patch * 10, (lib.pd_version(), planedepth_amd.__version__)
     # no experiments, no timing-ablation / trace builds exist any more: both queries are fixed at 0
     assert lib.pd_build_flags() == 0 and lib.pd_experiments() == 0
+
+
+def test_every_header_constant_is_a_module_attribute():
+    consts = capi_header.constants()
+    assert len(consts) >= 62
+    for name, value in consts.items():
+        assert getattr(C, name) == value, name
+    families = capi_header.enum("pd_pp_family")
+    assert C.PD_PP_FAMILIES == tuple(k[len("PD_PP_FAMILY_"):].lower() for k in sorted(families, key=families.get))
+    assert C.PD_PP_FAMILIES == ("gather", "rows", "seg", "single", "chain", "chain_split")
+
+
+def test_struct_mirrors_have_the_headers_members():
+    for c_name, mirror in (("pd_sweep_desc", C.SweepDesc), ("pd_sweep_view", C.SweepView), ("pd_pp_route", C.PpRoute)):
+        assert [f[0] for f in mirror._fields_] == capi_header.struct_members(c_name), c_name
+    assert ctypes.sizeof(C.SweepDesc) == 32
+    assert ctypes.sizeof(C.SweepView) == 16 * 8
+    assert ctypes.sizeof(C.PpRoute) == 24
+
+
+@pytest.mark.parametrize("old, new, names", [
+    ("int pd_version(void);", "int pd_new(unsigned long n, pd_stream_t stream);", ("unsigned long n", "pd_new")),   # never c_void_p
+    ("int pd_version(void);", "int pd_new(pd_sweep_desc d);", ("pd_sweep_desc d", "pd_new")),
+    ("PD_TAIL_BF16 = 4", "PD_TAIL_BF16 = 0x4", ("PD_TAIL_BF16",)),
+    ("int32_t flip, nmax, rows2, alias;", "int32_t flip, rows2, nmax, alias;", ("pd_pp_route", "PpRoute")),
+    (None, None, ("planedepth_hip.h",)),   # no header at all: there is no fallback table
+])
+def test_header_the_binding_cannot_map_is_refused(old, new, names, tmp_path, monkeypatch):
+    path = tmp_path / "planedepth_hip.h"
+    if old is not None:
+        assert old in capi_header.text()
+        path.write_text(capi_header.text().replace(old, new))
+    monkeypatch.setattr(C, "HEADER_PATH", str(path))
+    with pytest.raises(C.PlaneDepthHipError) as e:
+        C._parse_header()
+    assert str(path) in str(e.value) and all(n in str(e.value) for n in names)
+
+
+def test_call_checks_the_argument_count_before_the_device():
+    initialised = torch.cuda.is_initialized()   # (an earlier GPU test of the same process may have done it)
+    with pytest.raises(TypeError, match="pd_ssim_fwd") as e:
+        C.call("pd_ssim_fwd", torch.device("cuda:0"), 1, 3)
+    assert "7" in str(e.value) and "2" in str(e.value)   # both counts: the header's seven before the stream, the two given
+    assert torch.cuda.is_initialized() == initialised
 
 
 def test_desc_layout_and_host_queries():
@@ -209,3 +252,37 @@ def test_per_source_compiler_flags_name_real_sources_and_enter_the_source_hash(m
     assert entry.source_hash() != before
     monkeypatch.undo()
     assert entry.source_hash() == before
+
+
+def _ssim_through_call(dev, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    x, y = torch.rand(1, 3, 8, 8, generator=g).to(dev), torch.rand(1, 3, 8, 8, generator=g).to(dev)
+    out = torch.empty_like(x)
+    C.call("pd_ssim_fwd", dev, 1, 3, 8, 8, x, y, out)
+    return x, y, out
+
+
+@pytest.mark.gpu
+def test_call_raises_the_librarys_refusal():
+    dev = torch.device("cuda:0")
+    with pytest.raises(C.PlaneDepthHipError) as e:
+        C.call("pd_ssim_fwd", dev, 0, 3, 8, 8, None, None, None)   # B = 0: refused in validation, nothing launches
+    assert "pd_ssim_fwd" in str(e.value)
+    assert C.load().pd_last_error().decode() in str(e.value) and C.load().pd_last_error()
+
+
+@pytest.mark.gpu
+def test_call_launches_what_the_operator_launches():
+    x, y, out = _ssim_through_call(torch.device("cuda:0"))
+    assert torch.equal(out, ops.ssim(x, y))
+
+
+@pytest.mark.gpu
+def test_call_switches_to_the_tensors_device_and_back():
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs a second GPU: %d visible" % torch.cuda.device_count())
+    torch.cuda.set_device(0)
+    _, _, here = _ssim_through_call(torch.device("cuda:0"))
+    _, _, there = _ssim_through_call(torch.device("cuda:1"))
+    assert torch.cuda.current_device() == 0
+    assert there.device.index == 1 and torch.equal(there.cpu(), here.cpu())

@@ -11,7 +11,6 @@ import copy
 import ctypes
 import functools
 import os
-import re
 import sys
 
 import numpy as np
@@ -19,7 +18,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import GOLDEN, ROOT
+import capi_header
+from conftest import GOLDEN
 from embedding_cases import (DECODER_LEVELS, HIDDEN, LEVELS, SMALL, WORKLOAD, allowance, crop_grids, epconv_module, fixture_weights,
                              level_gradients, load_fixture, make_weights, negative_shares, pyramid_and_gradients_fp64, pyramid_fp64,
                              torch_pyramid)
@@ -103,21 +103,16 @@ def test_per_element_inputs_keep_both_elu_branches_live(shape):
 
 
 def test_header_capi_and_library_agree():
-    text = open(os.path.join(ROOT, "include", "planedepth_hip.h")).read()
     for name, value in (("PD_EMBED_NEURAL", 0), ("PD_EMBED_FREQUENCY", 1), ("PD_EMBED_IDENTITY", 2)):
-        m = re.search(r"\b%s\s*=\s*(\d+)" % name, text)
-        assert m and int(m.group(1)) == getattr(C, name) == value, name
+        assert capi_header.constant(name) == getattr(C, name) == value, name
     assert embedding.KINDS == {"neural": 0, "frequency": 1, "identity": 2}
     lib = C.load()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name, ret in (("pd_grid_embed_fwd", "int"), ("pd_grid_embed_bwd", "int"), ("pd_grid_embed_bwd_workspace_floats", "size_t")):
-        m = re.search(r"%s\s+%s\s*\(([^)]*)\)" % (ret, name), code)
-        assert m, name
-        params = [p.strip() for p in m.group(1).split(",")]
-        kinds = ["P" if "*" in p or "pd_stream_t" in p else "F" if p.startswith("float") else "I" for p in params]
+    for name, ret, kinds in (("pd_grid_embed_fwd", "int", "IIIIIIIPPPPP"), ("pd_grid_embed_bwd", "int", "IIIIIPPPPPPP"),
+                             ("pd_grid_embed_bwd_workspace_floats", "size_t", "IIIP")):
+        assert capi_header.prototype(name)[0] == ret
         res, args = C.SIGNATURES[name]
         assert res is (ctypes.c_int if ret == "int" else ctypes.c_size_t)
-        assert kinds == [{ctypes.c_void_p: "P", ctypes.c_float: "F", ctypes.c_int: "I"}[a] for a in args], name
+        assert capi_header.kinds(name) == capi_header.ctypes_kinds(args) == list(kinds), name
         assert hasattr(lib, name)
     import planedepth_amd
     assert lib.pd_version() == 290 and planedepth_amd.__version__ == "0.2.9"

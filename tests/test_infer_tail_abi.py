@@ -2,13 +2,11 @@
 header, the ctypes table and the library agree; every refusal happens in argument validation, with text — nothing launches, so
 none of this needs a GPU; the operators and ``predict`` refuse CPU tensors and, with gradients enabled, inputs that require grad."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
+import capi_header
 import planedepth_amd
 from planedepth_amd import _capi as C
 from planedepth_amd import decoder_tail as DT
@@ -31,14 +29,9 @@ def _plade(B=2, N=5, H=8, W=16, flags=C.PD_TAIL_MIXTURE, raw_logits=PTR, raw_sig
 
 
 def test_header_capi_and_library_agree():
-    text = open(os.path.join(ROOT, "include", "planedepth_hip.h")).read()
     lib = C.load()
     for name, fwd, inputs in (("pd_decoder_tail_infer", "pd_decoder_tail_fwd", 4), ("pd_plade_tail_infer", "pd_plade_tail_fwd", 4)):
-        m = re.search(r"int\s+%s\s*\(([^;]*)\)\s*;" % name, text)
-        assert m, name
-        args = [" ".join(a.split()) for a in m.group(1).split(",")]
-        f = re.search(r"int\s+%s\s*\(([^;]*)\)\s*;" % fwd, text)
-        fwd_args = [" ".join(a.split()) for a in f.group(1).split(",")]
+        args, fwd_args = capi_header.params(name), capi_header.params(fwd)
         assert args[:5 + inputs] == fwd_args[:5 + inputs]          # B, N, H, W, flags and the forward's input tensors
         assert args[5 + inputs:] == ["float* disp", "float* depth", "float* confidence", "int* plane_index", "float* disp_best",
                                      "float* stash", "pd_stream_t stream"]

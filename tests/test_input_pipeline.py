@@ -9,14 +9,14 @@ extents and the stream."""
 import ctypes
 import os
 import random
-import re
 import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT
+import capi_header
+from conftest import GOLDEN
 from pipeline_cases import (BRIGHTNESS, CHANNEL, FLIP, GAMMA, ULP1, augment, keys_of, load_fixture, logged_params, padded,
                             resize_crop_fp64, resize_crop_nearest, torch_color_fp32, torch_nearest_fp32)
 from planedepth_amd import _capi as C
@@ -151,22 +151,15 @@ def test_operators_check_types_and_refuse_cpu_frames():
 
 
 def test_header_capi_and_library_agree():
-    text = open(os.path.join(ROOT, "include", "planedepth_hip.h")).read()
     for name, value in (("PD_SRC_U8_HWC", 0), ("PD_SRC_F32_CHW", 1), ("PD_PIPE_GAMMA", 1), ("PD_PIPE_BRIGHTNESS", 2),
                         ("PD_PIPE_CHANNEL", 4), ("PD_PIPE_FLIP", 8)):
-        m = re.search(r"\b%s\s*=\s*(\d+)" % name, text)
-        assert m and int(m.group(1)) == getattr(C, name) == value, name
+        assert capi_header.constant(name) == getattr(C, name) == value, name
     assert (GAMMA, BRIGHTNESS, CHANNEL, FLIP) == (C.PD_PIPE_GAMMA, C.PD_PIPE_BRIGHTNESS, C.PD_PIPE_CHANNEL, C.PD_PIPE_FLIP)
     lib = C.load()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in ("pd_resize_crop_augment", "pd_resize_crop_nearest"):
-        m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-        assert m, name
-        params = [p.strip() for p in m.group(1).split(",")]
-        kinds = ["P" if "*" in p or "pd_stream_t" in p else "F" if p.startswith("float") else "I" for p in params]
+    for name, kinds in (("pd_resize_crop_augment", "IIIIIIIPPPPPPPP"), ("pd_resize_crop_nearest", "IIIIIPPPPPP")):
         res, args = C.SIGNATURES[name]
         assert res is ctypes.c_int
-        assert kinds == [{ctypes.c_void_p: "P", ctypes.c_float: "F", ctypes.c_int: "I"}[a] for a in args], name
+        assert capi_header.kinds(name) == capi_header.ctypes_kinds(args) == list(kinds), name
         assert hasattr(lib, name)
 
 

@@ -2,13 +2,11 @@
 on PD_TAIL_DISP_ROWS / PD_TAIL_MASK_ROWS, every refusal happens in argument validation (nothing launches, no GPU needed), and the
 Python operators exist and refuse CPU tensors."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
+import capi_header
 from planedepth_amd import _capi as C
 from planedepth_amd import decoder_tail, ops
 
@@ -16,25 +14,14 @@ GEOM = dict(no_levels=4, xz_levels=3, disp_min=2.0, disp_max=300.0, xz_min=0.185
 P = ctypes.c_void_p(16)   # a non-NULL pointer that is never dereferenced: every call below is refused in validation
 
 
-def header():
-    return open(os.path.join(ROOT, "include", "planedepth_hip.h")).read()
-
-
 def test_header_capi_and_library_agree():
-    text = header()
     for name, value in (("PD_TAIL_DISP_ROWS", 8), ("PD_TAIL_MASK_ROWS", 16)):
-        m = re.search(r"\b%s\s*=\s*(\d+)" % name, text)
-        assert m and int(m.group(1)) == getattr(C, name) == value
+        assert capi_header.constant(name) == getattr(C, name) == value
     lib = C.load()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for name in ("pd_plane_geometry_fwd", "pd_plane_geometry_bwd"):
-        m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-        assert m, name
-        params = [p.strip() for p in m.group(1).split(",")]
-        kinds = ["P" if "*" in p or "pd_stream_t" in p else "F" if p.startswith("float") else "I" for p in params]
         res, args = C.SIGNATURES[name]
         assert res is ctypes.c_int
-        assert kinds == [{ctypes.c_void_p: "P", ctypes.c_float: "F", ctypes.c_int: "I"}[a] for a in args], name
+        assert capi_header.kinds(name) == capi_header.ctypes_kinds(args) == list("IIIIIIFFFFPPPPPPP"), name
         assert hasattr(lib, name)
 
 

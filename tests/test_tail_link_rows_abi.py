@@ -3,12 +3,10 @@ ctypes table and the library agree, the query names the served set, pd_sweep_bwd
 refusal happens in argument validation — nothing launches, so none of this needs a GPU."""
 import ctypes
 import itertools
-import os
-import re
 
 import pytest
 
-from conftest import ROOT
+import capi_header
 from planedepth_amd import _capi as C
 
 ROW_FORMS = (0, C.PD_DISP_ROWS, C.PD_MASK_ROWS, C.PD_DISP_ROWS | C.PD_MASK_ROWS)
@@ -24,13 +22,8 @@ def rows_fuses(d):
 
 
 def test_header_capi_and_library_agree():
-    text = open(os.path.join(ROOT, "include", "planedepth_hip.h")).read()
-    assert re.search(r"int\s+pd_sweep_bwd_tail_rows_fuses\s*\(\s*const\s+pd_sweep_desc\s*\*", text)
-    m = re.search(r"int\s+pd_plane_sweep_bwd_tail_rows\s*\(([^;]*)\)\s*;", text)
-    assert m
-    args = [a.strip() for a in m.group(1).split(",")]
-    old = re.search(r"int\s+pd_plane_sweep_bwd_tail\s*\(([^;]*)\)\s*;", text)
-    old_args = [a.strip() for a in old.group(1).split(",")]
+    assert capi_header.prototype("pd_sweep_bwd_tail_rows_fuses") == ("int", ["const pd_sweep_desc* d"])
+    args, old_args = capi_header.params("pd_plane_sweep_bwd_tail_rows"), capi_header.params("pd_plane_sweep_bwd_tail")
     assert len(args) == len(old_args) + 1 == 22                      # the existing argument list + mask_rows
     assert [a for a in args if a != "const float* mask_rows"] == old_args
     assert C.SIGNATURES["pd_sweep_bwd_tail_rows_fuses"] == (ctypes.c_int, [ctypes.POINTER(C.SweepDesc)])
