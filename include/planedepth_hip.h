@@ -424,6 +424,41 @@ int pd_plade_tail_infer(int B, int N, int H, int W, int flags, const float* raw_
                         int* plane_index, float* disp_best, float* stash, pd_stream_t stream);
 
 /*
+ * Novel views at inference: what the network IS — a layered view synthesiser — as one forward-only entry, in the style of the
+ * inference tails above.  From the decoder's conv outputs and the source image to V rendered views in one launch: the tail of
+ * DepthDecoder.forward (depth_decoder.py:256-291) followed by pred_novel_images (trainer.py:540-603, disp_warp) with the
+ * disparity scaled per view by a baseline factor s (any finite float): +1 is the reference's target "r", -1 its target "l", 0
+ * the source camera, 0.5 half the rig's baseline.  Per view:
+ *   logits = logits_in * mask; sigma = clamp(sigmoid(sigma_in), .01, 1)      (the tail step, on the SOURCE rows' mask)
+ *   per plane n, at px = x + fl(s * d_n) (fp32, the reference's coordinate chain), bilinear, zeros padding, times mask_n of the
+ *   TARGET row: colour_n, logit_n, sigma_n and ones_n (a ones image);  an out-of-view tap enters the softmax with logit 0
+ *   p = softmax_N(logit); with PD_TAIL_MIXTURE p = (p / clamp(sigma, .01, 1)) / sum_N
+ *   rgb = sum_N p colour;  coverage = sum_N p ones  (the share of the composite that came from inside the source image: 1 in
+ *   the interior, towards 0 where the view looks past the image's edge);  disp = sum_N p d  (the rig's disparity in the NEW view)
+ * Nothing [B,N,H,W]-sized is written, there is no workspace, and logits_in / sigma_in are read from memory once per launch
+ * whatever V is (a workgroup owns a target row, stages each plane's source row in LDS once and serves every view's taps from it).
+ * A view's results do not depend on V or on the other views of its launch, bit for bit.
+ * Flags: pd_tail_flags (PD_TAIL_MIXTURE, PD_TAIL_BF16: logits_in / sigma_in hold bf16 and widen exactly, every output is fp32;
+ * PD_TAIL_DISP_ROWS: disp_layered is [B,N,H]; PD_TAIL_MASK_ROWS: mask_rows is [B,N,H]) ORed with pd_render_flags:
+ *   PD_RENDER_TAIL_APPLIED   logits_in / sigma_in are `logits` / `sigma` as a tail already wrote them (pd_decoder_tail_fwd, the
+ *                            stock DepthDecoder, FalNet): the tail step is skipped, the sampled features still take the mask
+ * baselines is a HOST array of V floats, copied into the launch arguments (nothing of it is read after the call returns).
+ * rgb [B,V,3,H,W] is required; coverage and disp [B,V,1,H,W] may be NULL and are skipped then.  Every element of an output
+ * that is given is written.
+ * Refused before anything touches the device, naming the argument or flag: V outside 1..PD_RENDER_MAX_VIEWS; a non-finite
+ * baseline; PD_TAIL_MASK_ROWS with a NULL mask_rows, or mask_rows without the flag; sigma_in NULL with PD_TAIL_MIXTURE;
+ * N*H*W >= 2^31; H or W below 2; a pointer that is not aligned to its element (4 bytes; 2 for bf16).  PD_ERR_UNSUPPORTED:
+ * PD_TAIL_DISP_DENSE (dense disparities or masks: yz planes), and a row wider than the staged-row layout takes (2048 pixels).
+ * --render_probability (the PladeNet tail) and homography_warp views have no form here.
+ * Forward only.
+ */
+enum { PD_RENDER_MAX_VIEWS = 4 };
+enum pd_render_flags { PD_RENDER_TAIL_APPLIED = 256 };
+int pd_render_views(int B, int N, int H, int W, int V, int flags, const float* logits_in, const float* sigma_in,
+                    const float* mask_rows, const float* disp_layered, const float* image, const float* baselines, float* rgb,
+                    float* coverage, float* disp, pd_stream_t stream);
+
+/*
  * get_smooth_loss_disp (layers.py:243-256; trainer.py:768):
  *   out[0] = mean_x |d(x)-d(x+1)| exp(-gamma mean_c|I(x)-I(x+1)|) + the same along y.
  * disp [B,1,H,W], img [B,C,H,W]; both may be crops of wider tensors: unit column stride, the other strides (in floats)

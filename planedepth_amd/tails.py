@@ -349,13 +349,15 @@ def _infer_want(want):
     return want
 
 
-def _infer_no_grad(differentiable, **tensors):
-    """The inference tails build no autograd node: an input that asks for a gradient is a caller's mistake, not a silent detach."""
+def _infer_no_grad(differentiable, operator=None, **tensors):
+    """The inference tails build no autograd node: an input that asks for a gradient is a caller's mistake, not a silent detach.
+    ``operator``: the forward-only caller's name where it is not ``<differentiable>_inference`` (``render_views``)."""
     if torch.is_grad_enabled():
         for name, t in tensors.items():
             if torch.is_tensor(t) and t.requires_grad:
-                raise ValueError("%s requires grad, but %s_inference is forward-only: call it under torch.no_grad(), or use "
-                                 "ops.%s, the differentiable operator" % (name, differentiable, differentiable))
+                raise ValueError("%s requires grad, but %s is forward-only: call it under torch.no_grad(), or use "
+                                 "ops.%s, the differentiable operator" % (name, operator or differentiable + "_inference",
+                                                                           differentiable))
 
 
 def _infer_outputs(B, H, W, dev, want, stash_channels):
