@@ -457,6 +457,10 @@ enum pd_render_flags { PD_RENDER_TAIL_APPLIED = 256 };
 int pd_render_views(int B, int N, int H, int W, int V, int flags, const float* logits_in, const float* sigma_in,
                     const float* mask_rows, const float* disp_layered, const float* image, const float* baselines, float* rgb,
                     float* coverage, float* disp, pd_stream_t stream);
+/* The columns a lane owns in a pd_render_views launch of V views on rows of W pixels, answered on the host (no GPU needed): 1, or
+ * 2 for W > 1024 and for W >= 513 with V <= 2; 0 for what the entry point refuses (W < 2, W > 2048, V outside
+ * 1..PD_RENDER_MAX_VIEWS).  The entry point switches on the same function; a pixel's bits are the same in both forms. */
+int pd_render_cols_per_lane(int W, int V);
 
 /*
  * get_smooth_loss_disp (layers.py:243-256; trainer.py:768):

@@ -216,14 +216,24 @@ static int render_launch(const RenderArgs& a, hipStream_t stream) {
   return check_launch("render_views_kernel");
 }
 
+// Columns per lane of a launch of V views on rows of W pixels (pd_render_cols_per_lane reports it; render_cols switches on it: the
+// one place that holds the rule); 0: a width the staged-row layout does not take.
+// Two columns per lane: above kRenderThreadsMax pixels there is no other way; from kRenderTwoColsFrom pixels on with one or two
+// views, where half as many waves per row, each with twice the loads in flight, hide the row loads' latency better (8 x 49 x 192
+// x 640, fp32, one view: 0.146 against 0.183 ms; with four views the registers of eight states cost more than that gains,
+// 0.391 against 0.379 ms).  A pixel's arithmetic is the same in both forms.
+static int render_cols_per_lane(int W, int V) {
+  if (W < 2 || W > kRenderThreadsMax * kRenderColsMax || render_lds_bytes(W) > device_lds_bytes()) return 0;
+  return (W > kRenderThreadsMax || (W >= kRenderTwoColsFrom && V <= 2)) ? kRenderColsMax : 1;
+}
+
 template <class ST, bool MIX, int V>
 static int render_cols(const RenderArgs& a, hipStream_t stream) {
-  // Two columns per lane: above kRenderThreadsMax pixels there is no other way; from kRenderTwoColsFrom pixels on with one or two
-  // views, where half as many waves per row, each with twice the loads in flight, hide the row loads' latency better (8 x 49 x 192
-  // x 640, fp32, one view: 0.146 against 0.183 ms; with four views the registers of eight states cost more than that gains,
-  // 0.391 against 0.379 ms).  A pixel's arithmetic is the same in both forms.
-  const bool two_cols = a.W > kRenderThreadsMax || (a.W >= kRenderTwoColsFrom && V <= 2);
-  return two_cols ? render_launch<ST, MIX, V, kRenderColsMax>(a, stream) : render_launch<ST, MIX, V, 1>(a, stream);
+  switch (render_cols_per_lane(a.W, V)) {
+    case 1: return render_launch<ST, MIX, V, 1>(a, stream);
+    case kRenderColsMax: return render_launch<ST, MIX, V, kRenderColsMax>(a, stream);
+    default: pd::set_error("pd_render_views: no kernel for W = %d with %d views", a.W, V); return PD_ERR_UNSUPPORTED;
+  }
 }
 template <class ST, bool MIX>
 static int render_v(int V, const RenderArgs& a, hipStream_t stream) {
@@ -246,6 +256,10 @@ using namespace pd;
       return PD_ERR_UNSUPPORTED;         \
     }                                    \
   } while (0)
+
+extern "C" int pd_render_cols_per_lane(int W, int V) {
+  return (V >= 1 && V <= PD_RENDER_MAX_VIEWS) ? render_cols_per_lane(W, V) : 0;
+}
 
 extern "C" int pd_render_views(int B, int N, int H, int W, int V, int flags, const float* logits_in, const float* sigma_in,
                                const float* mask_rows, const float* disp_layered, const float* image, const float* baselines,
@@ -275,7 +289,7 @@ extern "C" int pd_render_views(int B, int N, int H, int W, int V, int flags, con
                 reinterpret_cast<uintptr_t>(coverage) | reinterpret_cast<uintptr_t>(disp)) & 3),
              "misaligned pointer (mask_rows, disp_layered, rgb, coverage, disp: 4-byte elements)");
   PD_REQUIRE(!(reinterpret_cast<uintptr_t>(image) & 3), "misaligned pointer (image: 4-byte elements)");
-  PD_REFUSE_UNSUPPORTED(W > kRenderThreadsMax * kRenderColsMax || render_lds_bytes(W) > device_lds_bytes(),
+  PD_REFUSE_UNSUPPORTED(render_cols_per_lane(W, V) == 0,
                         "W = %d: a row of more than %d pixels (or %zu bytes of LDS) does not fit the staged-row layout", W,
                         kRenderThreadsMax * kRenderColsMax, render_lds_bytes(W));
 

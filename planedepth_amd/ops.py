@@ -41,7 +41,7 @@ from .geometry import (  # noqa: F401
 from .pipeline import resize_crop_augment, resize_crop_depth  # noqa: F401
 from .embedding import grid_embedding, fused_grid_embedding, decoder_embedding_sizes  # noqa: F401
 from .pose import _PoseTail, pose_matrices, pose_tail, pose_conjugate  # noqa: F401
-from .render import Views, render_views  # noqa: F401
+from .render import Views, render_views, render_cols_per_lane  # noqa: F401
 
 
 class _OpsModule(types.ModuleType):

@@ -26,6 +26,12 @@ def _baselines(baselines):
     return values
 
 
+def render_cols_per_lane(W, V):
+    """The columns a lane owns in a ``pd_render_views`` launch of ``V`` views on rows of ``W`` pixels (``pd_render_cols_per_lane``,
+    the function the entry point itself switches on; answered on the host): 1 or 2, 0 for what the entry point refuses."""
+    return int(C.load().pd_render_cols_per_lane(int(W), int(V)))
+
+
 def render_views(raw_logits, raw_sigma, padding_mask, disp_layered, image, baselines, use_mixture_loss=True,
                  tail_applied=False, want=("coverage", "disp")):
     """The other camera's picture: ``rgb`` [B,V,3,H,W] of ``image`` [B,3,H,W] seen from V cameras, one per entry of

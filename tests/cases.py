@@ -137,6 +137,31 @@ def slice_report(got, ref64, plane_floor):
                 zero_ok=zero_abs <= (1e-6 * scale if scale > 0.0 else 1e-6), scale=scale)
 
 
+def px_report(got, ref64, floor):
+    """Per-PIXEL companion of rel_err for an image-shaped output (a rendered view's rgb, coverage, disp): every element is measured
+    against its own reference value, floored by ``floor`` times the tensor's largest one:
+
+      err = max |got - ref| / max(|ref|, floor * max|ref|)  over the elements whose reference is not exactly 0.
+
+    The elements whose fp64 reference IS exactly 0 (a pixel no plane reaches) are measured apart, by ``slice_report``'s rule:
+    ``zero_ok`` = ``got`` there stays within 1e-6 * max|ref| (1e-6 absolute for an all-zero tensor); ``zeros`` counts them.
+    A NaN in ``got`` is the worst error, not none.  ``worst`` is the index of the element that gives ``err``."""
+    g, r = got.detach().double().cpu(), ref64.detach().double().cpu()
+    assert g.shape == r.shape, (tuple(g.shape), tuple(r.shape))
+    scale = float(r.abs().max()) if r.numel() else 0.0
+    diff = (g - r).abs()
+    diff = torch.where(torch.isnan(diff), torch.full_like(diff, float("inf")), diff)
+    live = r != 0
+    err, worst = 0.0, None
+    if bool(live.any()):
+        q = torch.where(live, diff / torch.clamp(r.abs(), min=floor * scale), torch.zeros_like(diff))
+        flat = int(q.argmax())
+        err, worst = float(q.flatten()[flat]), tuple(int(i) for i in np.unravel_index(flat, tuple(q.shape)))
+    zero_abs = float(diff[~live].max()) if bool((~live).any()) else 0.0
+    return dict(err=err, zeros=int((~live).sum()), zero_abs=zero_abs,
+                zero_ok=zero_abs <= (1e-6 * scale if scale > 0.0 else 1e-6), scale=scale, worst=worst)
+
+
 def term_report(got, ref64, allowance):
     """Per-ELEMENT companion of rel_err for the decoder tails: every element is measured against its own ``allowance`` — the sum of
     the absolute values of the terms the fp64 formula adds to produce it, taken from the fp64 oracle's tensors (the element's

@@ -35,6 +35,11 @@ def test_header_capi_and_library_agree():
         "float* coverage", "float* disp", "pd_stream_t stream"]
     assert C.SIGNATURES["pd_render_views"] == (ctypes.c_int, [ctypes.c_int] * 6 + [P] * 10)
     assert hasattr(lib, "pd_render_views")
+    assert capi_header.params("pd_render_cols_per_lane") == ["int W", "int V"]
+    assert C.SIGNATURES["pd_render_cols_per_lane"] == (ctypes.c_int, [ctypes.c_int] * 2)
+    assert lib.pd_render_cols_per_lane(640, 1) == 2 and lib.pd_render_cols_per_lane(640, 4) == 1   # host only: no GPU asked
+    assert [lib.pd_render_cols_per_lane(W, 1) for W in (1, 2, 2048, 2049)] == [0, 1, 2, 0]
+    assert lib.pd_render_cols_per_lane(640, 0) == 0 and lib.pd_render_cols_per_lane(640, C.PD_RENDER_MAX_VIEWS + 1) == 0
 
 
 def test_constants_are_module_attributes():
