@@ -449,11 +449,12 @@ int pd_plade_tail_infer(int B, int N, int H, int W, int flags, const float* raw_
  * baseline; PD_TAIL_MASK_ROWS with a NULL mask_rows, or mask_rows without the flag; sigma_in NULL with PD_TAIL_MIXTURE;
  * N*H*W >= 2^31; H or W below 2; a pointer that is not aligned to its element (4 bytes; 2 for bf16).  PD_ERR_UNSUPPORTED:
  * PD_TAIL_DISP_DENSE (dense disparities or masks: yz planes), and a row wider than the staged-row layout takes (2048 pixels).
- * --render_probability (the PladeNet tail) and homography_warp views have no form here.
+ * --render_probability (the PladeNet tail) has no form here; homography_warp views (arbitrary camera poses) are pd_render_poses,
+ * below.
  * Forward only.
  */
 enum { PD_RENDER_MAX_VIEWS = 4 };
-enum pd_render_flags { PD_RENDER_TAIL_APPLIED = 256 };
+enum pd_render_flags { PD_RENDER_TAIL_APPLIED = 256, PD_RENDER_VISIBLE_ONLY = 512 };
 int pd_render_views(int B, int N, int H, int W, int V, int flags, const float* logits_in, const float* sigma_in,
                     const float* mask_rows, const float* disp_layered, const float* image, const float* baselines, float* rgb,
                     float* coverage, float* disp, pd_stream_t stream);
@@ -461,6 +462,45 @@ int pd_render_views(int B, int N, int H, int W, int V, int flags, const float* l
  * 2 for W > 1024 and for W >= 513 with V <= 2; 0 for what the entry point refuses (W < 2, W > 2048, V outside
  * 1..PD_RENDER_MAX_VIEWS).  The entry point switches on the same function; a pixel's bits are the same in both forms. */
 int pd_render_cols_per_lane(int W, int V);
+
+/*
+ * Novel views at inference for arbitrary camera poses: pd_render_views' counterpart for homography_warp.  From the decoder's conv
+ * outputs, the planes (distance [B,N], norm [B,N,3]) and the source image to V views, one per pose T[b,v] ([B,V,4,4]; T maps
+ * source to target, X_t = R X_s + t, as in H_s2t = K (R + t n^T / d) K^-1): the tail of DepthDecoder.forward followed by
+ * pred_novel_images with warp_type == "homography_warp" (trainer.py:556-603, layers.py:206-234).  Per view:
+ *   logits = logits_in * mask_rows[b,n,y_src]; sigma = clamp(sigmoid(sigma_in), .01, 1)     (the tail step, applied to each tap)
+ *   per plane n: p = H_t2s [x,y,1]; mask = (K^-1 [x,y,1] . (R n) > 0) and (z > 1e-7); z clamped to 1e-7; the reference's normalise /
+ *   un-normalise round trip (the training kernels' arithmetic); bilinear, zeros padding: colour_n, logit_n, sigma_n and ones_n (a
+ *   ones image), each times mask.  A masked plane keeps logit 0 and sigma 0.01 in the mixture, as in the reference.
+ *   p = softmax_N(logit); with PD_TAIL_MIXTURE p = (p / clamp(sigma, .01, 1)) / sum_N
+ *   rgb = sum_N p colour;  coverage = sum_N p ones;  disp = sum_N p disp_n(x,y) with disp_n = max(a x + b y + c, 0), the plane's
+ *   inverse depth in the NEW camera as a rig disparity (0.1 * 0.58 * W / z_t): 0.1 * 0.58 * W / disp is the new view's depth.
+ *   (a, b, c) = 0.1 * 0.58 * W * (K^-1[:3,:3])^T n_t / d_t with n_t = R n, d_t = d + n_t . t; 0 for d_t <= 0.
+ * Two launches: a setup kernel writes one 16-float record per (b, v, n) into `workspace` (pd_render_poses_workspace_floats(B, N,
+ * V) = 16 * B * V * N floats, answered on the host) — H_t2s (9) and R n (3), bit-identical to what
+ * pd_homography_matrices_fwd(PD_HMAT_PLANES) writes for that image with the pose T[b,v]; (a, b, c), formed in fp64 and rounded
+ * once; a validity word: a record whose matrix is not finite or not invertible (d_t = 0, the new camera's centre lies on the
+ * plane — a case outside the reference, whose torch.inverse fails there) masks its plane everywhere in that view.  The render
+ * kernel has one lane per target pixel and streams over the planes, the grid image-major.  Nothing [B,N,H,W]-sized is written,
+ * there are no atomics, and a view's bits do not depend on V or on the other views of the launch.
+ * Flags: PD_TAIL_MIXTURE, PD_TAIL_BF16 (logits_in / sigma_in hold bf16 and widen exactly; every output is fp32),
+ * PD_TAIL_MASK_ROWS (mask_rows is [B,N,H]; not read with PD_RENDER_TAIL_APPLIED), PD_RENDER_TAIL_APPLIED as in pd_render_views, and
+ *   PD_RENDER_VISIBLE_ONLY   a plane whose mask is off at a pixel takes no part at all (weight 0, not logit 0); a pixel where no
+ *                            plane is visible gets rgb = coverage = disp = 0.  (The reference lets masked planes enter the mixture
+ *                            with weight p / 0.01, which darkens a view in which planes leave the frustum: right for parity with
+ *                            rgb_rec, wrong for a picture.)
+ * rgb [B,V,3,H,W] is required; coverage and disp [B,V,1,H,W] may be NULL.  Every element of an output that is given is written.
+ * Refused before anything touches the device, naming the argument or flag: V < 1 or B*V > 65535; PD_TAIL_DISP_ROWS and
+ * PD_TAIL_DISP_DENSE (planes come in as distance / norm); PD_TAIL_MASK_ROWS with a NULL mask_rows, or mask_rows without the flag;
+ * sigma_in NULL with PD_TAIL_MIXTURE; a NULL workspace, T, K, inv_K, distance or norm; N*H*W >= 2^31; H or W below 2; a pointer
+ * that is not aligned to its element (4 bytes; 2 for bf16).  --render_probability and the PladeNet tail have no form here.
+ * Forward only; no allocation, no synchronisation.
+ */
+size_t pd_render_poses_workspace_floats(int B, int N, int V);
+int pd_render_poses(int B, int N, int H, int W, int V, int flags, const float* logits_in, const float* sigma_in,
+                    const float* mask_rows, const float* distance, const float* norm, const float* T, const float* K,
+                    const float* inv_K, const float* image, float* rgb, float* coverage, float* disp, float* workspace,
+                    pd_stream_t stream);
 
 /*
  * get_smooth_loss_disp (layers.py:243-256; trainer.py:768):

@@ -14,66 +14,11 @@
 //   PD_HMAT_STEREO_ROWS  identity rotation + x translation + normals without an x component: the warp is the shift
 //                    h01*y + h02 per (plane, row), the facing test is constant along x:
 //                                                                  shift [B,N,rows], mask [B,N,rows]  (H_t2s optional)
-#include "pd_common.h"
+#include "pd_homography_chain.h"
 
 namespace pd {
 
-struct M3 {
-  double m[3][3];
-};
-
-__device__ __forceinline__ M3 mul3(const M3& a, const M3& b) {
-  M3 c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c.m[i][j] = a.m[i][0] * b.m[0][j] + a.m[i][1] * b.m[1][j] + a.m[i][2] * b.m[2][j];
-  return c;
-}
-
-__device__ __forceinline__ M3 transpose3(const M3& a) {
-  M3 c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c.m[i][j] = a.m[j][i];
-  return c;
-}
-
-// adjugate / determinant in fp64: cond(H) ~ 1e3..1e4 here, far inside what 53 bits carry.  A singular matrix yields
-// inf / nan entries (torch.inverse raises instead; the sweep then masks nothing sensible either way).
-__device__ __forceinline__ M3 inverse3(const M3& a) {
-  M3 c;
-  const double c00 = a.m[1][1] * a.m[2][2] - a.m[1][2] * a.m[2][1];
-  const double c01 = a.m[1][2] * a.m[2][0] - a.m[1][0] * a.m[2][2];
-  const double c02 = a.m[1][0] * a.m[2][1] - a.m[1][1] * a.m[2][0];
-  const double det = a.m[0][0] * c00 + a.m[0][1] * c01 + a.m[0][2] * c02;
-  const double r = 1.0 / det;
-  c.m[0][0] = c00 * r;
-  c.m[1][0] = c01 * r;
-  c.m[2][0] = c02 * r;
-  c.m[0][1] = (a.m[0][2] * a.m[2][1] - a.m[0][1] * a.m[2][2]) * r;
-  c.m[1][1] = (a.m[0][0] * a.m[2][2] - a.m[0][2] * a.m[2][0]) * r;
-  c.m[2][1] = (a.m[0][1] * a.m[2][0] - a.m[0][0] * a.m[2][1]) * r;
-  c.m[0][2] = (a.m[0][1] * a.m[1][2] - a.m[0][2] * a.m[1][1]) * r;
-  c.m[1][2] = (a.m[0][2] * a.m[1][0] - a.m[0][0] * a.m[1][2]) * r;
-  c.m[2][2] = (a.m[0][0] * a.m[1][1] - a.m[0][1] * a.m[1][0]) * r;
-  return c;
-}
-
-__device__ __forceinline__ M3 load3_from44(const float* __restrict__ p) {   // the upper-left 3x3 of a [4,4] matrix
-  M3 c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c.m[i][j] = (double)p[i * 4 + j];
-  return c;
-}
-
-struct PlaneOf {   // (n, d) of homography slot j in the given mode
-  double n[3], d;
-};
-
+// (n, d) of homography slot j in the given mode
 __device__ __forceinline__ PlaneOf plane_of(int mode, int b, int j, int N, const float* __restrict__ distance,
                                             const float* __restrict__ norm) {
   PlaneOf p;
@@ -84,27 +29,6 @@ __device__ __forceinline__ PlaneOf plane_of(int mode, int b, int j, int N, const
   const long k = (long)b * N + (mode == PD_HMAT_UNIFORM ? 0 : j);
   p.n[0] = norm[k * 3 + 0], p.n[1] = norm[k * 3 + 1], p.n[2] = norm[k * 3 + 2], p.d = distance[k];
   return p;
-}
-
-struct Chain {
-  M3 K, Ki, H;      // intrinsics, their inverse as handed over, H_t2s
-  double t[3];
-};
-
-__device__ __forceinline__ Chain homography_chain(const float* __restrict__ T, const float* __restrict__ K,
-                                                  const float* __restrict__ inv_K, int b, const PlaneOf& p) {
-  Chain c;
-  c.K = load3_from44(K + (long)b * 16);
-  c.Ki = load3_from44(inv_K + (long)b * 16);
-  M3 M = load3_from44(T + (long)b * 16);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    c.t[i] = (double)T[(long)b * 16 + i * 4 + 3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) M.m[i][j] += c.t[i] * p.n[j] / p.d;   // layers.py:216
-  }
-  c.H = inverse3(mul3(c.K, mul3(M, c.Ki)));                            // layers.py:218-219
-  return c;
 }
 
 __global__ __launch_bounds__(kWave) void homography_matrices_fwd_kernel(

@@ -2,7 +2,7 @@
 and ``bench.py`` use.  The operators live in ``sweep`` (the fused plane sweep: autograd nodes, routing, homography algebra),
 ``tails`` (decoder / PladeNet tails), ``losses`` (SSIM, mixture NLL, masked photometric, smoothness, perceptual feature distance), ``postprocess``
 (self-distillation warps, batch doubling, crop grid), ``metrics`` (depth evaluation), ``geometry`` (backproject / project /
-homography grids, grid_sample), ``pipeline`` (the input pipeline: fused bicubic resize-crop and augmentation), ``embedding`` (the decoders' positional encoding of the grid: embedding and bilinear pyramid in one launch), ``pose`` (the pose path: decoder tail, rotation and conjugation with Rc in one launch), ``render`` (novel views at inference: up to four rendered views from the conv outputs in one launch) and ``_buffers`` (descriptors, pre-zeroed pools); the switches tests flip between calls (``ops.SWEEP_IMPL = ...``) are attributes
+homography grids, grid_sample), ``pipeline`` (the input pipeline: fused bicubic resize-crop and augmentation), ``embedding`` (the decoders' positional encoding of the grid: embedding and bilinear pyramid in one launch), ``pose`` (the pose path: decoder tail, rotation and conjugation with Rc in one launch), ``render`` (novel views at inference: up to four rendered views from the conv outputs in one launch, and views at arbitrary camera poses) and ``_buffers`` (descriptors, pre-zeroed pools); the switches tests flip between calls (``ops.SWEEP_IMPL = ...``) are attributes
 of ``_state`` that this module forwards both ways.  ``planeform``: the forms of ``disp_layered`` / ``padding_mask`` (per plane, rows, dense) they all read.
 
 Every function launches hand-written HIP kernels through ctypes on torch's current stream.  PyTorch is used for device
@@ -41,7 +41,7 @@ from .geometry import (  # noqa: F401
 from .pipeline import resize_crop_augment, resize_crop_depth  # noqa: F401
 from .embedding import grid_embedding, fused_grid_embedding, decoder_embedding_sizes  # noqa: F401
 from .pose import _PoseTail, pose_matrices, pose_tail, pose_conjugate  # noqa: F401
-from .render import Views, render_views, render_cols_per_lane  # noqa: F401
+from .render import Views, render_views, render_cols_per_lane, render_poses  # noqa: F401
 
 
 class _OpsModule(types.ModuleType):

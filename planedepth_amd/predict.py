@@ -102,4 +102,39 @@ def render(model, images, baselines, *, autocast=False):
         return views, _prediction(outputs, M, w, False)
 
 
-predict.render = render   # (``planedepth_amd.predict`` is the function: the package re-exports it over this module's name)
+def render_poses(model, images, poses, K=None, inv_K=None, *, autocast=False, visible_only=False):
+    """``images`` [M,3,h,w] (fp32, on the GPU) seen from the cameras at ``poses`` — [M,V,4,4], or [V,4,4] for every image; a pose
+    maps source to target coordinates, as the reference's ``inputs[("Rt", side)]`` (``ops.render_poses``) — next to the depth
+    prediction of the same forward pass.  Runs ``model(images, grids)`` once under ``torch.no_grad()`` (and ``torch.autocast`` when
+    ``autocast``) and returns ``(Views, Prediction)`` as ``render`` does.  ``K`` / ``inv_K`` [M,4,4] default to the dataset's
+    intrinsics at this size (``synthetic.dataset_intrinsics``).
+
+    The views come from ``outputs["raw_logits"]`` / ``["raw_sigma"]`` when the model kept its conv outputs, otherwise from
+    ``outputs["logits"]`` / ``["sigma"]`` (``tail_applied=True``: no mask is read, so yz-plane models are served too), exactly as
+    in ``render``; the planes are ``outputs["distance"]`` / ``["norm"]``, the mask ``outputs["padding_mask"]``."""
+    C.require_gpu_tensor("images", images)
+    if images.dim() != 4:
+        raise ValueError("images must be [M,C,h,w], got %s" % (tuple(images.shape),))
+    M, _, h, w = images.shape
+    if (K is None) != (inv_K is None):
+        raise ValueError("K and inv_K come together (both None: the dataset's intrinsics at this size)")
+    with torch.no_grad():
+        if K is None:
+            from .synthetic import dataset_intrinsics
+            K, inv_K = (t.to(images.device) for t in dataset_intrinsics(M, h, w))
+        grids = eval_grid(M, h, w, images.device)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(autocast)):
+            outputs = model(images, grids)
+        raw = "raw_logits" in outputs
+        logits = outputs["raw_logits" if raw else "logits"]
+        sigma = outputs.get("raw_sigma" if raw else "sigma")
+        if sigma is not None and sigma.dtype != logits.dtype:   # a stock tail under autocast: fp32 logits (* mask), bf16 sigma
+            logits, sigma = logits.float(), sigma.float()
+        mask = _render_mask(outputs, tuple(logits.shape)) if raw else None
+        views = ops.render_poses(logits, sigma, mask, outputs["distance"].float(), outputs["norm"].float(), images, poses, K,
+                                 inv_K, use_mixture_loss=sigma is not None, tail_applied=not raw, visible_only=visible_only)
+        return views, _prediction(outputs, M, w, False)
+
+
+predict.render = render
+predict.render_poses = render_poses   # (``planedepth_amd.predict`` is the function: the package re-exports it over this module's name)
